@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: QLinear GEMM throughput on MI355X (BASELINE.json metric: TFLOP/s and GB/s vs the roofline).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-sub] [--no-cpu-baseline] [--shard]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR] [--no-sub] [--no-cpu-baseline] [--shard]
 
 A *step* is one pass of the hot path (one ``quanto::qbytes_mm`` / ``quanto::qbits_mm`` call through the C ABI) over one
-batch of synthetic input already resident in HBM.  The default run prints ONE JSON line whose ``value`` is BASELINE.json
-``configs[1]`` (bf16 x int8, per-channel scale, (M,K,N) = (4096,4096,4096), TFLOP/s) and whose ``sub_results`` carry the
-int4 half of the headline metric, measured in the same process with the same discipline: the north-star decode shape
-(1,4096,4096), ``configs[2]`` (1,4096,11008), and the same decode GEMV over the fused q/k/v and gate/up projections of a
-Llama-3-8B layer (``quanto::qbits_mm_multi``: one launch for Linears that share their input).  Every result has its own
-``roofline`` (device events around the timed region, on the stream the kernels run on) and ``cpu_baseline``.
+batch of synthetic input already resident in HBM.  A plain run measures the headline workload alone and prints ONE JSON line
+whose ``value`` is BASELINE.json ``configs[1]`` (bf16 x int8, per-channel scale, (M,K,N) = (4096,4096,4096), TFLOP/s), with
+``ms_per_step`` (host clock per timed step, K = ``--steps`` steps) and the ``roofline`` of that time.  ``--full`` adds, in the same
+process and with the same discipline, ``sub_results`` that carry the int4 half of the headline metric: the north-star decode
+shape (1,4096,4096), ``configs[2]`` (1,4096,11008), and the same decode GEMV over the fused q/k/v and gate/up projections of a
+Llama-3-8B layer (``quanto::qbits_mm_multi``: one launch for Linears that share their input); every result of a ``--full`` run
+has its own ``roofline`` (device events around the timed region, on the stream the kernels run on), ``ref_rocm_us`` and ``cpu_baseline``.
+``--dump-outputs DIR`` writes what the headline's last timed step returned (``DIR/y.npy``, float32, see ``dump_outputs``); the
+inputs come from fixed seeds, so two builds of the project can be compared output for output.
 
 Method (same formulas as the reference's bench/kernels/benchmark_w4a16.py:44-71: TFLOP/s = 2MNK / t, GB/s = bytes / t):
   * the K timed steps are captured once in a hipGraph and replayed (a decode call is shorter than its Python issue time);
@@ -17,20 +20,20 @@ Method (same formulas as the reference's bench/kernels/benchmark_w4a16.py:44-71:
     256 MB Infinity Cache (SURVEY.md 8d "cache hygiene");
   * before the timed replay the same graph is replayed, untimed, for ``--ramp-ms`` (default 300 ms): an idle MI355X takes
     ~100 ms of sustained load to reach its steady clock / power state (``config.clock_ramp_ms``; ``--ramp-ms 0`` = cold);
-  * ``cpu_baseline`` (rank 0, N = 1 only) times the reference's own CPU path - the ATen kernels QLinear.forward reaches on
+  * ``cpu_baseline`` (``--full``, rank 0, N = 1 only) times the reference's own CPU path - the ATen kernels QLinear.forward reaches on
     CPU tensors, issued by ``oracle/reference_cpu_path.py`` exactly as the reference issues them (pinned ``torch.equal``
-    against the imported reference in tests/test_reference_integration.py) - on the FULL shape and the SAME tensors the
+    to the reference's stored outputs in tests/test_reference_integration.py) - on the FULL shape and the SAME tensors the
     GPU side just multiplied, on the GPU box's host cores: median + IQR + thread count.
 
 With N > 1 every rank runs the same workload on its own GPU: the path is embarrassingly parallel per Linear, no data-path
 collective, weak scaling; ``value`` aggregates over ranks / max-over-ranks time.  The ranks come from the launcher
 (``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``: RANK / LOCAL_RANK / WORLD_SIZE in the environment) or,
 when ``--gpus N`` is given with no launcher around it, from bench.py itself (it re-executes under torch.distributed.run on
-127.0.0.1).  At N > 1 the default run appends one more sub-result, ``cfg4_sharded``: ``configs[3]`` (fp8 weights, (512,8192,8192))
+127.0.0.1).  At N > 1 a ``--full`` run appends one more sub-result, ``cfg4_sharded``: ``configs[3]`` (fp8 weights, (512,8192,8192))
 column-sharded over the ranks with ``ColumnParallelQLinear``, compute-only and compute + ``all_gather_into_tensor`` (RCCL over xGMI),
 ``"scaling": "strong"`` - SURVEY.md 8(e); ``--shard`` makes that the headline line instead.
 
-Round 4 additions to the default line (all measured in the same process / on the same box as the headline):
+Round 4 additions to the ``--full`` line (all measured in the same process / on the same box as the headline):
   * ``roofline.frac`` is computed from the SAME host-bracketed time as ``value`` (``ms_per_step``); the device-event time of the same
     replay is ``event_us`` (r3 divided by the event time: 0.5544 next to a value that said 0.548);
   * ``kernel_us`` / ``kernel_us_min``: kernel-only duration from a ``rocprofv3 --kernel-trace`` pass of this same file (a child
@@ -53,7 +56,7 @@ Round 4 additions to the default line (all measured in the same process / on the
     method (bench/generation/metrics/latency.py:24-105: ``generate`` 512 prompt + 512 new tokens, greedy, eos disabled), tokens/s at
     batch 1 and batch 32 (``--no-cfg5`` skips it).
 
-The printed line is kept under ~7.5 KB (the driver keeps an 8 KB stdout tail): sub-results are compact records (name, shape, us,
+The ``--full`` line is kept under ~7.5 KB (the driver keeps an 8 KB stdout tail): sub-results are compact records (name, shape, us,
 kernel, fraction, algorithmic bytes / flops, counter traffic, CPU seconds), the prose that explains the CPU paths is printed once
 (``cpu_paths``); ``--verbose`` prints every sub-result in full on stderr.
 """
@@ -312,22 +315,27 @@ def make_ref_rocm_step(kind, x, wset, K, N):
     return step
 
 
-def timed_replay(step, steps, args, dist, device, warmup=None):
+def timed_replay(step, steps, args, dist, device, warmup=None, keep=None):
     """W untimed warm-up steps, the K steps captured in ONE hipGraph (or issued eagerly with --eager), the clock ramp, then the
     timed region: barrier + synchronize on both sides, host clock around it and a device-event pair on the launch stream inside it;
-    max over ranks.  Returns (elapsed_s, event_ms)."""
+    max over ranks.  Returns (elapsed_s, event_ms).  With a dict ``keep``, ``keep["out"]`` receives what the last timed step returned,
+    as a list of float32 host tensors (copied after the timed region)."""
     for _ in range(args.warmup if warmup is None else warmup):
         step()
     torch.cuda.synchronize()
     graph = None
+    last = [None]
     if not args.eager:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=side):
-                for _ in range(steps):
-                    step()
+                for i in range(steps):
+                    y = step()
+                    if i == steps - 1 and keep is not None:
+                        last[0] = y  # the graph's own output buffer: every replay rewrites it
+                    del y  # (each step's output is released before the next step allocates, as without keep)
         torch.cuda.current_stream().wait_stream(side)
         graph.replay()  # untimed: uploads the executable graph
         torch.cuda.synchronize()
@@ -336,8 +344,11 @@ def timed_replay(step, steps, args, dist, device, warmup=None):
         if graph is not None:
             graph.replay()
         else:
-            for _ in range(steps):
-                step()
+            for i in range(steps):
+                y = step()
+                if i == steps - 1 and keep is not None:
+                    last[0] = y
+                del y
 
     t_ramp = time.perf_counter()
     while (time.perf_counter() - t_ramp) * 1e3 < args.ramp_ms:
@@ -360,8 +371,39 @@ def timed_replay(step, steps, args, dist, device, warmup=None):
         tt = torch.tensor([elapsed, dev_ms], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, dev_ms = float(tt[0]), float(tt[1])
+    if keep is not None:
+        ys = last[0] if isinstance(last[0], (list, tuple)) else [last[0]]
+        keep["out"] = [y.detach().float().cpu() for y in ys]
     del graph
     return elapsed, dev_ms
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: bytes of float32 written per run at most (the rows of a larger output are sampled)
+
+
+def dump_rows(rows, cols, budget):
+    """Row indices --dump-outputs keeps of a [rows, cols] float32 output: all of them (None) when it fits ``budget`` bytes, else a fixed, seeded,
+    sorted sample of as many rows as fit."""
+    if rows * cols * 4 <= budget:
+        return None
+    import numpy as np
+
+    return np.sort(np.random.default_rng(0).choice(rows, size=max(1, budget // (cols * 4)), replace=False))
+
+
+def dump_outputs(directory, ys):
+    """``DIR/y.npy`` (``DIR/y0.npy``, ``y1.npy`` ... for a multi-Linear launch): what the last timed step returned, float32, row-sampled by
+    dump_rows when larger than its share of DUMP_BYTES."""
+    import numpy as np
+
+    if not os.path.isdir(directory):  # a directory made here ignores itself in a git checkout, as pytest's cache directory does
+        os.makedirs(directory)
+        with open(os.path.join(directory, ".gitignore"), "w") as f:
+            f.write("*\n")
+    for i, y in enumerate(ys):
+        a = y.reshape(-1, y.shape[-1]).numpy()
+        rows = dump_rows(a.shape[0], a.shape[1], DUMP_BYTES // len(ys))
+        np.save(os.path.join(directory, "y.npy" if len(ys) == 1 else f"y{i}.npy"), a if rows is None else a[rows])
 
 
 def cpu_baseline(kind, M, K, N, x, wset, budget_s):
@@ -401,7 +443,7 @@ def cpu_baseline(kind, M, K, N, x, wset, budget_s):
     return out
 
 
-def run_workload(name, args, device, rank, world, dist, steps, with_cpu):
+def run_workload(name, args, device, rank, world, dist, steps, with_cpu, dump_dir=None):
     from optimum_quanto_amd.library.hip import quanto_hip
 
     lib = quanto_hip.lib
@@ -417,9 +459,12 @@ def run_workload(name, args, device, rank, world, dist, steps, with_cpu):
     step()
     torch.cuda.synchronize()
     kernel_name = lib.last_kernel()
-    elapsed, dev_ms = timed_replay(step, steps, args, dist, device)
+    keep = {} if dump_dir is not None and rank == 0 else None
+    elapsed, dev_ms = timed_replay(step, steps, args, dist, device, keep=keep)
     if rank != 0:
         return None
+    if keep is not None:
+        dump_outputs(dump_dir, keep.pop("out"))
 
     ms_per_step = elapsed * 1e3 / steps
     launch_ms = ms_per_step     # the roofline fraction uses the SAME time as `value` (host clock around barrier + synchronize) ...
@@ -456,7 +501,7 @@ def run_workload(name, args, device, rank, world, dist, steps, with_cpu):
         "gbps": round(nbytes * world / (elapsed / steps) / 1e9, 1),
         "roofline": roof,
     }
-    if name in REF_ROCM_FOR and not args.no_ref_rocm:
+    if name in REF_ROCM_FOR and args.full and not args.no_ref_rocm:
         try:
             ref_step = make_ref_rocm_step(kind, x, sets[0], K, N)
             with torch.no_grad():
@@ -1074,7 +1119,15 @@ def main():
     ap.add_argument("--trace-child", nargs="+", default=None, help=argparse.SUPPRESS)  # the child run of collect_profiles
     ap.add_argument("--trace-mode", default="graph", choices=["graph", "eager"], help=argparse.SUPPRESS)
     ap.add_argument("--ablate-child", default=None, help=argparse.SUPPRESS)  # the child run of run_ablation
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: cpu_baseline, ref_rocm_us, the default sub_results (with the ablation, "
+                         "the QConv2d record and configs[4] end to end), cfg4_sharded at N > 1, the rocprofv3 child passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step returned to DIR/y.npy (float32; rows of an output over 32 MiB: a fixed, "
+                         "seeded sample)")
     args = ap.parse_args()
+    if args.dump_outputs is not None and (args.shard or args.stub):
+        ap.error("--dump-outputs writes the output of a --workload run (not --shard / --stub)")
 
     if args.gpus is None:  # an external launcher's WORLD_SIZE is enough (torchrun --nproc-per-node 8 bench.py --shard)
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1119,10 +1172,11 @@ def main():
     if args.shard:
         out = run_sharded(args, device, rank, world, dist)
     else:
-        with_cpu = not args.no_cpu_baseline and world == 1  # the host baseline is reported at N = 1 only
-        out = run_workload(args.workload, args, device, rank, world, dist, args.steps, with_cpu)
-        default_run = args.workload == "cfg2" and args.sub is None and not args.no_sub
-        subs = [] if args.no_sub else (args.sub if args.sub is not None else (DEFAULT_SUB if args.workload == "cfg2" else []))
+        # a plain run measures the headline workload alone; --full adds what the line carried before (CPU baseline, sub-results, ...)
+        with_cpu = args.full and not args.no_cpu_baseline and world == 1  # the host baseline is reported at N = 1 only
+        out = run_workload(args.workload, args, device, rank, world, dist, args.steps, with_cpu, dump_dir=args.dump_outputs)
+        default_run = args.full and args.workload == "cfg2" and args.sub is None and not args.no_sub
+        subs = [] if args.no_sub else (args.sub if args.sub is not None else (DEFAULT_SUB if default_run else []))
         sub_results = []
         for name in subs:
             # decode launches last a few microseconds: time at least 200 of them so that the event pair brackets milliseconds
@@ -1136,7 +1190,7 @@ def main():
                 if args.verbose:
                     print(json.dumps(r), file=sys.stderr, flush=True)
                 sub_results.append(compact(r))
-        if world > 1 and not args.no_sub and args.workload == "cfg2":
+        if world > 1 and args.full and not args.no_sub and args.workload == "cfg2":
             # N > 1: the one place the path has a collective - configs[3] column-sharded over the ranks, strong scaling
             r = run_sharded(args, device, rank, world, dist)
             if r is not None:

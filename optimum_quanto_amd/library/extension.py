@@ -44,7 +44,9 @@ class NativeLibrary:
             return self.lib_path
         if shutil.which("make") is None or not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
             raise RuntimeError(f"{self.name}: cannot build {self.lib_path}: hipcc/make not found")
-        cmd = ["make", "-C", self.make_dir, f"-j{os.cpu_count() or 4}"]
+        # MAX_JOBS when set, else at most 16 jobs: a machine-wide CPU count oversubscribes a host shared with other work
+        jobs = os.environ.get("MAX_JOBS") or min(os.cpu_count() or 4, 16)
+        cmd = ["make", "-C", self.make_dir, f"-j{jobs}"]
         if force:
             cmd.insert(1, "-B")
         proc = subprocess.run(cmd, capture_output=True, text=True)

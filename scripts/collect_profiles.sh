@@ -9,7 +9,7 @@ PMC_FOR=${PMC_FOR:-"cfg2 northstar cfg3 gateup_fused qkv_fused cfg4 int4_decode3
 for W in "$@"; do
   # 1. kernel trace + stats of the command bench.py is judged on (default steps/warmup); "default" = the driver's exact command
   #    (cfg2 + the int4 sub_results in one process), any other name = that workload alone
-  if [ "$W" = default ]; then WARGS="--no-cpu-baseline"; else WARGS="--workload $W --no-sub --no-cpu-baseline"; fi
+  if [ "$W" = default ]; then WARGS="--full --no-cpu-baseline"; else WARGS="--full --workload $W --no-sub --no-cpu-baseline"; fi
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$W -o $W -- \
       python $REPO/bench.py $WARGS > $OUT/trace_$W.bench.json 2> $OUT/trace_$W.log)
   f=$(find $OUT/trace_$W -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $OUT/${W}_kernel_stats.csv

@@ -14,12 +14,12 @@ tests)
   echo "pytest exit=$?" | tee -a $OUT/summary.txt; tail -40 $OUT/pytest_gpu.log;;
 bench)
   for w in cfg2 cfg3 northstar cfg4; do
-    timeout 600 python bench.py --workload $w --steps 50 --warmup 10 > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+    timeout 600 python bench.py --full --workload $w --steps 50 --warmup 10 > $OUT/bench_$w.json 2> $OUT/bench_$w.err
     echo "bench $w exit=$?"; cat $OUT/bench_$w.json; tail -3 $OUT/bench_$w.err
   done;;
 prof)
   for w in cfg2 cfg3; do
-    (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/prof_$w -o $w -- python $OLDPWD/bench.py --workload $w --steps 50 --warmup 10 --no-cpu-baseline > $OLDPWD/$OUT/prof_$w.log 2>&1)
+    (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/prof_$w -o $w -- python $OLDPWD/bench.py --full --workload $w --steps 50 --warmup 10 --no-cpu-baseline > $OLDPWD/$OUT/prof_$w.log 2>&1)
     echo "prof $w exit=$?"
     find $OUT/prof_$w -name "*kernel_stats*" | head -2 | while read f; do echo "== $f"; head -12 "$f"; done
   done;;

@@ -1,9 +1,12 @@
 """bench.py's launch contract, exercised where there is no GPU: `--gpus N` without a launcher spawns N ranks itself (r2's
-`--gpus` was parsed and never used), and the default line stays short enough for the driver's ~8 KB stdout tail."""
+`--gpus` was parsed and never used), the `--full` line stays short enough for the driver's ~8 KB stdout tail, and a plain run
+measures the headline alone and can dump what it computed."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -101,3 +104,78 @@ def test_world_size_from_the_launcher_is_enough():
     r = _run("--stub", "--steps", "2", "--warmup", "0", env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode == 0, r.stderr[-1500:]
     assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["n_gpus"] == 1
+
+
+def test_plain_run_options_are_there():
+    r = _run("--help")
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = _run("--stub", "--dump-outputs", "unused")
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+
+
+def _tensors(v):
+    """The tensors of a nested (x, sets) structure, in order."""
+    return [t for u in v for t in _tensors(u)] if isinstance(v, (list, tuple)) else [v]
+
+
+def test_bench_inputs_repeat_for_the_same_arguments():
+    """--dump-outputs compares two builds output for output: the inputs of a workload must be the same from run to run."""
+    import torch
+
+    import bench
+
+    for name in ("cfg2", "northstar", "qkv_fused", "w8a8", "w4a8_512"):
+        kind, M, K, N, _ = bench.WORKLOADS[name]
+        M, K = min(M, 16), min(K, 256)
+        N = tuple(min(n, 64) for n in N) if isinstance(N, tuple) else min(N, 64)
+        a, b = (_tensors(bench.build_inputs(kind, M, K, N, torch.device("cpu"), 2, seed=1234)) for _ in range(2))
+        assert len(a) == len(b) and all(torch.equal(u.view(torch.uint8), v.view(torch.uint8)) for u, v in zip(a, b)), name
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    import numpy as np
+    import torch
+
+    import bench
+
+    assert bench.dump_rows(64, 32, 1 << 20) is None  # small enough: every row
+    rows = bench.dump_rows(4096, 4096, bench.DUMP_BYTES)
+    assert rows is not None and len(rows) * 4096 * 4 <= bench.DUMP_BYTES and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, bench.dump_rows(4096, 4096, bench.DUMP_BYTES))
+    y = torch.arange(4096 * 4096, dtype=torch.float32).reshape(4096, 4096)
+    bench.dump_outputs(str(tmp_path / "one"), [y])
+    a = np.load(tmp_path / "one" / "y.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, y.numpy()[rows])
+    assert (tmp_path / "one" / ".gitignore").read_text() == "*\n"  # a dump directory made inside a checkout leaves git status clean
+    bench.dump_outputs(str(tmp_path / "two"), [y[:8], y[8:16, :100]])
+    assert np.array_equal(np.load(tmp_path / "two" / "y0.npy"), y[:8].numpy()) and np.load(tmp_path / "two" / "y1.npy").shape == (8, 100)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_headline_output(tmp_path):
+    """A plain run: the headline alone (no sub_results, CPU baseline or reference timing), K = --steps timed steps, and --dump-outputs writes
+    the last step's output, whose sampled rows are the product of the seeded inputs."""
+    import numpy as np
+    import torch
+
+    import bench
+    from helpers import assert_close_to_exact
+    from oracle import quanto_oracle as O
+
+    r = _run("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["unit"] == "TFLOP/s" and rec["higher_is_better"] is True and rec["dtype"] == "bf16"
+    assert not {"sub_results", "cpu_baseline", "ref_rocm_us", "profile_passes"} & set(rec)
+    y = np.load(tmp_path / "y.npy")
+    kind, M, K, N, _ = bench.WORKLOADS["cfg2"]
+    rows = bench.dump_rows(M, N, bench.DUMP_BYTES)
+    assert y.dtype == np.float32 and y.shape == (len(rows), N) and y.nbytes <= 64 << 20
+    x, sets = bench.build_inputs(kind, M, K, N, torch.device("cuda"), 1, seed=1234)
+    w, scale = sets[0]
+    pick = [0, len(rows) // 2, len(rows) - 1]
+    xs = x[torch.as_tensor(rows[pick], device=x.device)].float().cpu().numpy()
+    want = O.qbytes_mm_exact(xs, w.cpu().numpy(), scale.float().cpu().numpy().reshape(-1))
+    assert_close_to_exact(y[pick], want, "bf16", "bench.py --dump-outputs, cfg2")
