@@ -284,13 +284,16 @@ int quanto_hip_quantize_affine_packed(const void* base, const void* scale, const
 int quanto_hip_pack(const uint8_t* unpacked, uint8_t* packed, int64_t rows, int64_t cols, int bits, void* stream);
 
 /*
- * qbits_mm with QUANTIZED activations (W4A8, r6): F.linear(ActivationQBytesTensor, WeightQBitsTensor) - the combination the reference's
- * tests/tensor/ops/test_linear_dispatch.py:22-42 exercises and every backend of the reference serves by dequantizing the activation first
- * (tensor/weights/qbits.py:262-287 -> tensor/function.py:41-47; the CUDA subclasses: tensor/weights/awq/qbits.py:57-58).  Here the stored int8 / fp8-e4m3
- * activation values meet the stored nibbles on the 8-bit matrix instructions (csrc/qbits_a8_fused.hip):
+ * qbits_mm with QUANTIZED activations (W4A8 since r6, W2A8 and e5m2 activations since r7): F.linear(ActivationQBytesTensor, WeightQBitsTensor) - the
+ * combination the reference's tests/tensor/ops/test_linear_dispatch.py:22-42 and tests/nn/test_qlinear.py:97-113 exercise and every backend of the reference
+ * serves by dequantizing the activation first (tensor/weights/qbits.py:262-287 -> tensor/function.py:41-47; the CUDA subclasses:
+ * tensor/weights/awq/qbits.py:57-58).  Here the stored int8 / fp8 activation values meet the stored 4- or 2-bit codes on the 8-bit matrix instructions
+ * (csrc/qbits_a8_fused.hip):
  *   y[m, n] = a_scale * sum_g ( scale[n,g] * sum_{k in g} a[m,k] q[n,k] - z[n,g] * sum_{k in g} a[m,k] ) (+ bias[n]),  z = shift, or scale * zero_point
- *   a: a_dtype[M, K] (I8 or F8_E4M3FN); a_scale: ONE element of `dtype` on the device (the per-tensor activation scale, tensor/activations/qbytes.py:28-43);
- *   packed / scale / shift / bias / y as for quanto_hip_qbits_mm; dtype in {F16, BF16}; bits = 4, group_size = 128, N % 8 == 0, K % 128 == 0.
+ *   a: a_dtype[M, K] (I8, F8_E4M3FN or F8_E5M2); a_scale: ONE element of `dtype` on the device (the per-tensor activation scale,
+ *   tensor/activations/qbytes.py:28-43); packed / scale / shift / bias / y as for quanto_hip_qbits_mm; dtype in {F16, BF16}; group_size = 128, K % 128 == 0;
+ *   bits = 4 with N % 8 == 0 (packed [N/2, K]: packed row p holds features p and p + N/2), or bits = 2 with N % 16 == 0 (packed [N/4, K]: packed row p
+ *   holds features p, p + N/4, p + N/2 and p + 3N/4 in bits 0-1, 2-3, 4-5, 6-7).
  * QUANTO_HIP_ENOTSUP for every other format (the caller then dequantizes the activation and calls quanto_hip_qbits_mm, as the reference does).
  * workspace: optional split-K scratch of quanto_hip_qbits_mm_a8_workspace_size bytes, counter region zero on entry (QUANTO_HIP_WS_COUNTER_BYTES) and left
  * zero; without it the call runs unsplit.  For int8 activations the unsplit result is a pure function of the integers (fp32 fma chain over exact group sums).

@@ -95,7 +95,7 @@ bool qbytes_mm_f32_supported(int64_t, int64_t, int64_t, int, int, int);
 int qbytes_mm_gemv_f32(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, hipStream_t);
 int qbytes_mm_f32(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, hipStream_t);
 
-// quantized activations x int4 weights (r6, qbits_a8_fused.hip)
+// quantized activations x int4 / int2 weights (qbits_a8_fused.hip)
 bool qbits_a8_supported(int64_t, const PackedGeom&, int, int);
 size_t qbits_a8_workspace(int64_t, const PackedGeom&);
 int qbits_mm_a8(const void*, const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, int, bool, void*, size_t,
@@ -393,7 +393,10 @@ int quanto_hip_qbits_mm_a8(const void* a, const void* a_scale, const uint8_t* pa
   const PackedGeom g = make_geom(N, K, bits, group_size);
   const int r = qbits_mm_a8(a, a_scale, packed, scale, shift, bias, y, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes,
                             reinterpret_cast<hipStream_t>(stream));
-  if (r == QUANTO_HIP_OK) set_last_kernel(a_dtype == QUANTO_HIP_I8 ? "a8_fused_int8" : "a8_fused_fp8");
+  if (r == QUANTO_HIP_OK) {
+    static const char* const names[2][3] = {{"a8_fused_int8", "a8_fused_fp8", "a8_fused_bf8"}, {"a8_fused_int8_w2", "a8_fused_fp8_w2", "a8_fused_bf8_w2"}};
+    set_last_kernel(names[bits == 2][a_dtype == QUANTO_HIP_I8 ? 0 : a_dtype == QUANTO_HIP_F8_E4M3FN ? 1 : 2]);
+  }
   return r;
 }
 

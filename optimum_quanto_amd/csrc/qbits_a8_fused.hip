@@ -1,4 +1,4 @@
-// qbits_mm with QUANTIZED activations (W4A8, r6): int4 weights x int8 activations on v_mfma_i32_16x16x64_i8 and int4 weights x fp8-e4m3 activations on
+// qbits_mm with QUANTIZED activations (W4A8, r6; W2A8 and e5m2, r7): int4 weights x int8 activations on v_mfma_i32_16x16x64_i8 and int4 weights x fp8 activations on
 // v_mfma_scale_f32_16x16x128_f8f6f4 - the 8-bit matrix rates (2 x bf16) for the one activation x weight combination of the reference's
 // tests/tensor/ops/test_linear_dispatch.py:22-42 that still dequantized its activation (tensor/weights/awq/qbits.py:57-58 does the same on CUDA;
 // BASELINE.md lists the configuration: "W int4 / A fp8").
@@ -11,14 +11,20 @@
 // the other fused kernels.  For int8 activations the result is a pure function of the integers: bit-identical to an fp32 fma chain
 // over the exact group sums (oracle/quanto_oracle.py::qbits_mm_a8_chain), whichever tile or split computes it in the unsplit form.
 //
-// Structure = qbits_mfma_fused.hip (workgroup = 8 waves, BM tokens x 64 packed rows = 128 features, wave = all BM tokens x 16 features, K-tile = one group
-// of 128, LDS-DMA ring of two stages, scale tables parked in LDS, group accumulators double-buffered so that the fold of tile kt-1 is sliced over the matrix
-// steps of tile kt, split-K with a deterministic last-arriver reduce), with 1-byte activations (128-byte LDS rows) and:
+// Structure = qbits_mfma_fused.hip (workgroup = 8 waves, BM tokens x 128 features, wave = all BM tokens x 16 features, K-tile = one group of 128, LDS-DMA
+// ring of two stages, scale tables parked in LDS, group accumulators double-buffered so that the fold of tile kt-1 is sliced over the matrix steps of tile
+// kt, split-K with a deterministic last-arriver reduce), with 1-byte activations (128-byte LDS rows) and:
 //   * int8: a weight operand is the lane's nibble plane of 16 packed bytes - ((raw >> 4 plane) & 0x0F0F0F0F), TWO VALU per four weights (the bf16 kernel: one
 //     per weight) -, two K = 64 MFMAs per fragment and group, int32 group accumulator -> v_cvt_f32_i32 + two FMAs in the fold;
 //   * fp8: nibbles -> e4m3 codes through a 16-entry byte table (two v_perm over the low / high half of the table + one v_perm that picks by bit 3: seven
 //     VALU per four weights), ONE K = 128 MX-format MFMA (unit block scales) per fragment and group;
 //   * the group sums of a come from the matrix pipe as well (an all-ones weight operand, wave w for token fragment w), exact.
+// W2A8 (r7): int2 weights take the same tile with four planes per packed byte (packed [N/4, K], row p = features p, p + N/4, p + N/2, p + 3N/4 in bits
+// 0-1 .. 6-7): 32 packed rows = 128 features per workgroup (4 KiB of weights per tile, requested by waves 0..3), a wave's 16 matrix rows = 4 packed rows x
+// 4 planes; the operand is ((raw >> 2 plane) & 0x03030303) for int8 and ONE v_perm into the codes 0, 1, 2, 3 of the e4m3 table for fp8.  Codes 0..3 are exact
+// e4m3 values, so nothing else changes.  e5m2 activations (r7): the MX-format instruction takes its A and B formats independently - the weight operand (A)
+// stays e4m3, the activation operand (B) is read as bf8 (blgp = 1) in the product and in the all-ones group sum; an e5m2 value times an integer below 16 is
+// exact in fp32, as for e4m3.  Instantiated: {bf16, fp16} x {int8, e4m3, e5m2} x {float shift, zero-point} x {64, 128 tokens} x {int4, int2}.
 #include <type_traits>
 
 #include "qh_common.h"
@@ -26,15 +32,20 @@
 namespace qh {
 namespace a8 {
 
-constexpr int BK = 128, PR = 64, WAVES = 8, STAGES = 2;
-constexpr int W_BYTES = PR * BK;  // 8 KiB of packed bytes per tile
-template <int BM>
+constexpr int BK = 128, NF = 128, WAVES = 8, STAGES = 2;  // NF: output features per workgroup, either weight width
+// weight geometry of a workgroup: VPI features per packed byte (planes), PR packed rows (NF / VPI), RW packed rows per wave (16 features / VPI),
+// WP waves that request a weight piece of 8 rows x 128 B per tile (int4: all eight, 8 KiB; int2: waves 0..3, 4 KiB)
+template <int BITS>
+struct WGeo {
+  static constexpr int VPI = 8 / BITS, PR = NF / VPI, RW = 16 / VPI, W_BYTES = PR * BK, WP = W_BYTES / 1024;
+  static_assert((BITS == 2 || BITS == 4) && WP <= WAVES && WP * 1024 == W_BYTES, "weight geometry");
+};
+template <int BM, int BITS>
 struct Geo {
   static constexpr int MI = BM / 16;
-  static constexpr int X_BYTES = BM * BK, STAGE_BYTES = X_BYTES + W_BYTES;
+  static constexpr int X_BYTES = BM * BK, STAGE_BYTES = X_BYTES + WGeo<BITS>::W_BYTES;
   static constexpr int XP = BM / 8 / WAVES;  // activation DMA pieces (8 rows x 128 B = 1 KiB) per wave and tile
-  static constexpr int OPS = XP + 1;
-  static_assert(W_BYTES == WAVES * 1024 && XP >= 1 && (MI == 4 || MI == 8), "tile geometry");
+  static_assert(XP >= 1 && (MI == 4 || MI == 8), "tile geometry");
 };
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
@@ -51,12 +62,12 @@ __device__ __forceinline__ void glds16(const void* sbase, uint32_t voff, uint32_
       : "memory");
 }
 
-enum { A_I8 = 0, A_F8E4M3 = 1 };
+enum { A_I8 = 0, A_F8E4M3 = 1, A_F8E5M2 = 2 };
 
 struct Args {
   const uint8_t* a;      // [M, K] int8 / e4m3 activation values
   const void* a_scale;   // device scalar of the output dtype: the per-tensor activation scale
-  const uint8_t* w;      // packed [N/2, K]
+  const uint8_t* w;      // packed [N/VPI, K]
   const void* scale;     // [N*G]
   const void* shift;     // [N*G]
   const void* bias;      // [N] or null
@@ -77,21 +88,23 @@ struct Acc<A_I8> {
   using V = i32x4;
 };
 
-template <int DT, int AK, bool INT_SHIFT, int BM>
+template <int DT, int AK, bool INT_SHIFT, int BM, int BITS>
 __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Args a) {
   using E = Elem<DT>;
   using T = typename E::T;
   using GV = typename Acc<AK>::V;  // group accumulator
-  constexpr int MI = Geo<BM>::MI, XP = Geo<BM>::XP, X_BYTES = Geo<BM>::X_BYTES, STAGE_BYTES = Geo<BM>::STAGE_BYTES;
+  constexpr int MI = Geo<BM, BITS>::MI, XP = Geo<BM, BITS>::XP, X_BYTES = Geo<BM, BITS>::X_BYTES, STAGE_BYTES = Geo<BM, BITS>::STAGE_BYTES;
+  constexpr int VPI = WGeo<BITS>::VPI, PR = WGeo<BITS>::PR, RW = WGeo<BITS>::RW, WP = WGeo<BITS>::WP;
+  // B operand format of the MX-format instruction: bf8 for e5m2 activations, fp8 otherwise; the weight operand (A) is always e4m3 codes
+  constexpr int BFMT = AK == A_F8E5M2 ? 1 : 0;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   // layout: [STAGES x (activation tile | weight tile)] [xs: 2 x BM fp32 group sums of a] [sz: G x 2 x 128 features of T]
   float* xs_slot = reinterpret_cast<float*>(smem + STAGES * STAGE_BYTES);
-  constexpr int NF = 2 * PR;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int M = a.M, N = a.N, K = a.K, G = a.G;
-  const int P = N >> 1;
+  const int P = N >> (VPI == 2 ? 1 : 2);  // packed rows = features per plane
   const int p0 = blockIdx.x * PR, m0 = blockIdx.y * BM;
   const int S = a.S, sp = blockIdx.z;
   const int nk = G / S;  // one tile per group; this workgroup's groups are kt0 .. kt0 + nk - 1
@@ -111,7 +124,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
   }
   uint32_t wsrc;
   {
-    const int r = wave * 8 + (lane >> 3), c = (lane & 7) ^ (r & 7);
+    const int r = (WP == WAVES ? wave : wave & (WP - 1)) * 8 + (lane >> 3), c = (lane & 7) ^ (r & 7);  // int2: waves >= WP request nothing
     int p = p0 + r;
     p = p < P ? p : P - 1;
     wsrc = (uint32_t)((size_t)p * K + c * 16);
@@ -122,18 +135,19 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
     const uint32_t st = __builtin_amdgcn_readfirstlane(lds_base + stage * STAGE_BYTES);
 #pragma unroll
     for (int u = 0; u < XP; ++u) glds16(a.a + (size_t)(kt0 + kt_tile) * BK, xsrc[u], st + (wave * XP + u) * 1024);
-    glds16(a.w + (size_t)(kt0 + kt_tile) * BK, wsrc, st + X_BYTES + wave * 1024);
+    if (WP == WAVES || wave < WP) glds16(a.w + (size_t)(kt0 + kt_tile) * BK, wsrc, st + X_BYTES + wave * 1024);  // wave-uniform
   };
   const int last = nk - 1;
 
-  // ---- prologue: tiles 0 and 1 requested, tables parked (thread -> feature tid & 127, groups tid >> 7, + 4, ...), ONE drain ----
+  // ---- prologue: tiles 0 and 1 requested, tables parked (thread -> feature tid & 127 = plane f / PR, packed row f % PR; groups tid >> 7, + 4, ...),
+  // ONE drain ----
   issue_tile(0, 0);
   issue_tile(nk > 1 ? 1 : 0, 1);
   {
     const int f = tid & (NF - 1);
     int p = p0 + (f & (PR - 1));
     p = p < P ? p : P - 1;
-    const size_t row = (size_t)(p + (f >> 6) * P) * G + kt0;
+    const size_t row = (size_t)(p + (f / PR) * P) * G + kt0;
     for (int g = tid >> 7; g < nk; g += (WAVES * 64) >> 7) {
       sz[(g * 2 + 0) * NF + f] = reinterpret_cast<const T*>(a.scale)[row + g];
       if constexpr (INT_SHIFT)
@@ -146,21 +160,24 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // hand-counted waits start from a known state
 
   // ---- fragment read offsets: 16-byte chunk 4 h + fg of the lane's row (h = half of the 128-byte row); (row & 7) == (fi & 7) for every fragment ----
+  // weight row of matrix row fi: packed row wave * RW + fi % RW, plane fi / RW (int4: 8 rows x 2 planes, int2: 4 rows x 4 planes per wave)
   int xoff[2], woff[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) xoff[h] = fi * 128 + (((4 * h + fg) ^ (fi & 7)) << 4);
   {
-    const int r = wave * 8 + (fi & 7);
+    const int r = wave * RW + (fi & (RW - 1));
 #pragma unroll
     for (int h = 0; h < 2; ++h) woff[h] = X_BYTES + r * 128 + (((4 * h + fg) ^ (r & 7)) << 4);
   }
-  const uint32_t nib_shift = (fi >> 3) * 4;
-  const int floc = (fg >> 1) * PR + wave * 8 + 4 * (fg & 1);  // the lane's 4 consecutive features inside the block
+  const uint32_t nib_shift = (fi / RW) * BITS;
+  // the lane's 4 consecutive matrix rows 4 fg .. 4 fg + 3 = 4 consecutive packed rows of plane 4 fg / RW: 4 consecutive features inside the block
+  const int fplane = (4 * fg) / RW, froff = (4 * fg) % RW;
+  const int floc = fplane * PR + wave * RW + froff;
 
   f32x4 acc[MI];
 #pragma unroll
   for (int i = 0; i < MI; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  uint32_t nibmask = 0x0F0F0F0Fu;
+  uint32_t nibmask = BITS == 4 ? 0x0F0F0F0Fu : 0x03030303u;
   asm volatile("" : "+s"(nibmask));
   // e4m3 codes of 0..15 (bias 7): 0, 1 = 0x38, 2 = 0x40, 3 = 0x44, 4..7 = 0x48 + 2 (q - 4), 8..15 = 0x50 + (q - 8)
   uint32_t t_lo0 = 0x44403800u, t_lo1 = 0x4E4C4A48u, t_hi0 = 0x53525150u, t_hi1 = 0x57565554u;
@@ -236,6 +253,8 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
           op[d] = raw[d];
         } else if constexpr (AK == A_I8) {
           op[d] = s & nibmask;
+        } else if constexpr (BITS == 2) {
+          op[d] = __builtin_amdgcn_perm(t_lo1, t_lo0, s & nibmask);  // codes 0..3: bytes of t_lo0
         } else {
           const uint32_t q7 = s & 0x07070707u;
           const uint32_t lo = __builtin_amdgcn_perm(t_lo1, t_lo0, q7), hi = __builtin_amdgcn_perm(t_hi1, t_hi0, q7);
@@ -258,7 +277,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
         const int i = s;
         const i32x8 wa = i32x8{(int)op[0], (int)op[1], (int)op[2], (int)op[3], (int)op[4], (int)op[5], (int)op[6], (int)op[7]};
         const i32x8 xa = i32x8{(int)xl[i].x, (int)xl[i].y, (int)xl[i].z, (int)xl[i].w, (int)xh[i].x, (int)xh[i].y, (int)xh[i].z, (int)xh[i].w};
-        if (!(a.ablate & 2)) cg[i] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wa, xa, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);  // e4m3 x e4m3, scales 2^0
+        if (!(a.ablate & 2)) cg[i] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wa, xa, f32x4{0.f, 0.f, 0.f, 0.f}, 0, BFMT, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);  // e4m3 x e4m3 / bf8, scales 2^0
       }
       if constexpr (have_prev) {
         if (!(a.ablate & 1)) {
@@ -287,7 +306,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
       } else {
         const i32x8 ones = i32x8{0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838};  // e4m3 1.0
         const i32x8 xa = i32x8{(int)al.x, (int)al.y, (int)al.z, (int)al.w, (int)ah.x, (int)ah.y, (int)ah.z, (int)ah.w};
-        const f32x4 cx = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ones, xa, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
+        const f32x4 cx = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ones, xa, f32x4{0.f, 0.f, 0.f, 0.f}, 0, BFMT, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
         sum = cx[0];
       }
       // the matrix instruction must run with all 64 lanes: without this barrier hipcc sinks it into the lane < 16 branch below (EXEC = 0xFFFF), where the
@@ -366,8 +385,8 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
   // ---- epilogue: x activation scale, (+ bias), 4 consecutive features of one token per fragment: 8-byte stores ----
   T* yg = reinterpret_cast<T*>(a.y);
   const bool has_bias = a.bias != nullptr;
-  const int pl = p0 + wave * 8 + 4 * (fg & 1);
-  const int n0 = pl + (fg >> 1) * P;
+  const int pl = p0 + wave * RW + froff;
+  const int n0 = pl + fplane * P;
   float bv[4] = {0.f, 0.f, 0.f, 0.f};
   if (has_bias) {
 #pragma unroll
@@ -396,11 +415,15 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
   }
 }
 
-inline int lds_bytes(int groups, int bm) { return STAGES * (bm * BK + W_BYTES) + 2 * bm * 4 + groups * 2 * (2 * PR) * 2; }
-inline int tiles_of(int64_t M, int64_t N, int bm) { return (int)(((N / 2 + PR - 1) / PR) * ((M + bm - 1) / bm)); }
+inline int w_bytes(int bits) { return bits == 2 ? WGeo<2>::W_BYTES : WGeo<4>::W_BYTES; }
+inline int lds_bytes(int groups, int bm, int bits) { return STAGES * (bm * BK + w_bytes(bits)) + 2 * bm * 4 + groups * 2 * NF * 2; }
+// output tiles of NF features x bm tokens: the same count for either weight width (int4: 64 packed rows, int2: 32)
+inline int tiles_of(int64_t M, int64_t N, int bm) { return (int)(((N + NF - 1) / NF) * ((M + bm - 1) / bm)); }
 
 // Token tile and K split from the time model of qbits_mfma_fused.hip with this kernel's tile times (r6 sweep, profiles/r06_w4a8_*): 128-token tiles
 // once they alone give every CU a workgroup, 64-token tiles (two workgroups per CU) below; K split for few tiles.  QUANTO_HIP_A8_BM / _SPLIT force.
+// int2 runs the same model: its tile is the int4 tile with half the weight bytes (16 + 4 instead of 16 + 8 KiB through the vector L1 per group at
+// bm = 128), the tile count and the matrix steps are the same, and the model's job - which token tile and split - does not move with that.
 struct Plan {
   int bm, S;
   float us;
@@ -410,7 +433,7 @@ inline float model_us(int tiles, int nk, int bm, int S) {
   const float tail = S > 1 ? 3.5f + 0.5f * (float)wgs * (float)(bm * 512) * 1e-6f : 0.f;
   return 5.8f + (float)rounds * (float)nk * (bm == 64 ? 0.45f : 0.75f) + tail;
 }
-inline Plan make_plan(int64_t M, int64_t N, int G) {
+inline Plan make_plan(int64_t M, int64_t N, int G, int bits) {
   const int fbm = env_int("QUANTO_HIP_A8_BM", 0), fs = env_int("QUANTO_HIP_A8_SPLIT", 0);  // experiments / tests
   Plan best{0, 0, 0.f};
   for (int bm = 64; bm <= 128; bm += 64) {
@@ -420,7 +443,7 @@ inline Plan make_plan(int64_t M, int64_t N, int G) {
       if (G % S) break;
       const int nk = G / S;
       if (fs > 0 ? (S != fs) : (S > 1 && nk < 4)) continue;
-      if (lds_bytes(nk, bm) > 160 * 1024) continue;
+      if (lds_bytes(nk, bm, bits) > 160 * 1024) continue;
       if (S > 1 && (size_t)tiles * 4 > QUANTO_HIP_WS_COUNTER_BYTES) continue;
       const float us = model_us(tiles, nk, bm, S);
       if (best.bm == 0 || us < best.us * 0.97f) best = Plan{bm, S, us};
@@ -429,35 +452,51 @@ inline Plan make_plan(int64_t M, int64_t N, int G) {
   return best;
 }
 
-template <int DT, int AK, bool INT_SHIFT, int BM>
+template <int DT, int AK, bool INT_SHIFT, int BM, int BITS>
 static int launch_bm(const Args& a, hipStream_t stream) {
-  const int lds = lds_bytes(a.G / a.S, BM);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbits_a8_fused_kernel<DT, AK, INT_SHIFT, BM>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  const dim3 grid((unsigned)((a.N / 2 + PR - 1) / PR), (unsigned)((a.M + BM - 1) / BM), (unsigned)a.S);
-  hipLaunchKernelGGL((qbits_a8_fused_kernel<DT, AK, INT_SHIFT, BM>), grid, dim3(WAVES * 64), lds, stream, a);
+  const int lds = lds_bytes(a.G / a.S, BM, BITS);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbits_a8_fused_kernel<DT, AK, INT_SHIFT, BM, BITS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            lds);
+  const dim3 grid((unsigned)((a.N + NF - 1) / NF), (unsigned)((a.M + BM - 1) / BM), (unsigned)a.S);
+  hipLaunchKernelGGL((qbits_a8_fused_kernel<DT, AK, INT_SHIFT, BM, BITS>), grid, dim3(WAVES * 64), lds, stream, a);
   return launch_status();
 }
-template <int DT, int AK, bool INT_SHIFT>
-static int launch(const Args& a, int bm, hipStream_t stream) {
-  return bm == 64 ? launch_bm<DT, AK, INT_SHIFT, 64>(a, stream) : launch_bm<DT, AK, INT_SHIFT, 128>(a, stream);
+template <int DT, int AK, int BITS>
+static int launch(const Args& a, int bm, bool int_shift, hipStream_t stream) {
+  if (int_shift) return bm == 64 ? launch_bm<DT, AK, true, 64, BITS>(a, stream) : launch_bm<DT, AK, true, 128, BITS>(a, stream);
+  return bm == 64 ? launch_bm<DT, AK, false, 64, BITS>(a, stream) : launch_bm<DT, AK, false, 128, BITS>(a, stream);
 }
-template <int DT, int AK>
-static int launch_shift(const Args& a, int bm, bool int_shift, hipStream_t stream) {
-  return int_shift ? launch<DT, AK, true>(a, bm, stream) : launch<DT, AK, false>(a, bm, stream);
+template <int DT, int BITS>
+static int launch_act(const Args& a, int a_dtype, int bm, bool int_shift, hipStream_t stream) {
+  switch (a_dtype) {
+    case QUANTO_HIP_I8:
+      return launch<DT, A_I8, BITS>(a, bm, int_shift, stream);
+    case QUANTO_HIP_F8_E4M3FN:
+      return launch<DT, A_F8E4M3, BITS>(a, bm, int_shift, stream);
+    default:
+      return launch<DT, A_F8E5M2, BITS>(a, bm, int_shift, stream);
+  }
+}
+template <int DT>
+static int launch_bits(const Args& a, int bits, int a_dtype, int bm, bool int_shift, hipStream_t stream) {
+  return bits == 2 ? launch_act<DT, 2>(a, a_dtype, bm, int_shift, stream) : launch_act<DT, 4>(a, a_dtype, bm, int_shift, stream);
 }
 
 }  // namespace a8
 
+// Served: bits 4 with N % 8 == 0, bits 2 with N % 16 == 0 (N / VPI packed rows per plane, a multiple of 4: every lane's four output features are one
+// aligned 8-byte store), group size 128 (per-channel with K = 128 included), activations int8 / e4m3fn / e5m2.
 bool qbits_a8_supported(int64_t M, const PackedGeom& g, int a_dtype, int dtype) {
-  if (!(g.bits == 4 && g.C == 128 && (g.N % 8 == 0) && (g.K % 128 == 0) && M >= 1 && (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) &&
-        (a_dtype == QUANTO_HIP_I8 || a_dtype == QUANTO_HIP_F8_E4M3FN) && g.N < (1 << 30) && g.K < (1 << 30) && M * g.K < (1ll << 32) &&
-        g.N * g.K < (1ll << 33)))
+  if (!((g.bits == 4 || g.bits == 2) && g.C == 128 && (g.N % (4 * g.vpi) == 0) && (g.K % 128 == 0) && M >= 1 &&
+        (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) &&
+        (a_dtype == QUANTO_HIP_I8 || a_dtype == QUANTO_HIP_F8_E4M3FN || a_dtype == QUANTO_HIP_F8_E5M2) && g.N < (1 << 30) && g.K < (1 << 30) &&
+        M * g.K < (1ll << 32) && g.N * g.K < (1ll << 33)))
     return false;
-  return a8::make_plan(M, g.N, (int)g.G).bm != 0;
+  return a8::make_plan(M, g.N, (int)g.G, g.bits).bm != 0;
 }
 
 size_t qbits_a8_workspace(int64_t M, const PackedGeom& g) {
-  const a8::Plan p = a8::make_plan(M, g.N, (int)g.G);
+  const a8::Plan p = a8::make_plan(M, g.N, (int)g.G, g.bits);
   if (p.bm == 0 || p.S == 1) return 0;
   return QUANTO_HIP_WS_COUNTER_BYTES + (size_t)a8::tiles_of(M, g.N, p.bm) * p.S * (a8::WAVES * 64) * ((p.bm / 16) * 16);
 }
@@ -466,21 +505,18 @@ int qbits_mm_a8(const void* act, const void* act_scale, const uint8_t* packed, c
                 const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!qbits_a8_supported(M, g, a_dtype, dtype)) return QUANTO_HIP_ENOTSUP;
   if ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
-  a8::Plan p = a8::make_plan(M, g.N, (int)g.G);
+  a8::Plan p = a8::make_plan(M, g.N, (int)g.G, g.bits);
   if (p.S > 1 && (!workspace || workspace_bytes < qbits_a8_workspace(M, g) || reinterpret_cast<uintptr_t>(workspace) % 16)) {
     p.S = 1;  // no scratch: unsplit, with whichever token tile lets the whole scale table fit
-    if (a8::lds_bytes((int)g.G, p.bm) > 160 * 1024) p.bm = 64;
-    if (a8::lds_bytes((int)g.G, p.bm) > 160 * 1024) return QUANTO_HIP_EINVAL;
+    if (a8::lds_bytes((int)g.G, p.bm, g.bits) > 160 * 1024) p.bm = 64;
+    if (a8::lds_bytes((int)g.G, p.bm, g.bits) > 160 * 1024) return QUANTO_HIP_EINVAL;
   }
   const a8::Args a{reinterpret_cast<const uint8_t*>(act), act_scale, packed, scale, shift, bias, y, (int)M, (int)g.N, (int)g.K, (int)g.G, p.S,
                    reinterpret_cast<int*>(workspace),
                    p.S > 1 ? reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + QUANTO_HIP_WS_COUNTER_BYTES) : nullptr,
                    env_int("QUANTO_HIP_A8_ABLATE", 0)};
-  if (dtype == QUANTO_HIP_BF16)
-    return a_dtype == QUANTO_HIP_I8 ? a8::launch_shift<QUANTO_HIP_BF16, a8::A_I8>(a, p.bm, int_shift, stream)
-                                    : a8::launch_shift<QUANTO_HIP_BF16, a8::A_F8E4M3>(a, p.bm, int_shift, stream);
-  return a_dtype == QUANTO_HIP_I8 ? a8::launch_shift<QUANTO_HIP_F16, a8::A_I8>(a, p.bm, int_shift, stream)
-                                  : a8::launch_shift<QUANTO_HIP_F16, a8::A_F8E4M3>(a, p.bm, int_shift, stream);
+  return dtype == QUANTO_HIP_BF16 ? a8::launch_bits<QUANTO_HIP_BF16>(a, g.bits, a_dtype, p.bm, int_shift, stream)
+                                  : a8::launch_bits<QUANTO_HIP_F16>(a, g.bits, a_dtype, p.bm, int_shift, stream);
 }
 
 }  // namespace qh

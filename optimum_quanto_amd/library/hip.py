@@ -533,11 +533,11 @@ class _Bindings:
             self._check(st, "qbits_mm")
         return y if x.dim() == 2 else y.reshape(*x.shape[:-1], out_features)
 
-    # -- quanto::qbits_mm_a8 (quantized activations x int4 weights) ---------------------------------------
-    A8_DTYPES = (torch.int8, torch.float8_e4m3fn)
+    # -- quanto::qbits_mm_a8 (quantized activations x int4 / int2 weights) ---------------------------------
+    A8_DTYPES = (torch.int8, torch.float8_e4m3fn, torch.float8_e5m2)
 
     def qbits_mm_a8_workspace(self, M: int, out_features: int, in_features: int, bits: int, group_size, a_dtype, dtype) -> int:
-        """Split-K scratch bytes of the W4A8 kernel for this call shape, or a negative status when the format is not served (the caller then
+        """Split-K scratch bytes of the W4A8 / W2A8 kernel for this call shape, or a negative status when the format is not served (the caller then
         dequantizes the activation, as the reference does)."""
         adt, dt = _DTYPES.get(a_dtype), _DTYPES.get(dtype)
         if adt is None or dt is None:
@@ -550,7 +550,7 @@ class _Bindings:
         return 0
 
     def qbits_mm_a8(self, a, a_scale, packed, scale, shift, bias, bits: int, group_size, out_features: int, in_features: int):
-        """F.linear(quantized activation, int4 weight) on the 8-bit matrix instructions: ``a`` int8 / float8_e4m3fn [..., K], ``a_scale`` its
+        """F.linear(quantized activation, int4 / int2 weight) on the 8-bit matrix instructions: ``a`` int8 / float8_e4m3fn / float8_e5m2 [..., K], ``a_scale`` its
         per-tensor scale (one element).  Raises QuantoHipError(ENOTSUP) for formats the kernel does not take."""
         if not (a.is_cuda and a_scale.is_cuda and packed.is_cuda and scale.is_cuda and shift.is_cuda and (bias is None or bias.is_cuda)):
             raise QuantoHipError("quanto_hip kernels only accept tensors on a ROCm device")

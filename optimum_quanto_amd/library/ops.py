@@ -299,7 +299,7 @@ if _define("qbits_mm",
 
 
 # ------------------------------------------------------------------------------------------------
-# quanto::qbits_mm_a8 (r6): F.linear(quantized activation, int4 weight) without dequantizing the activation
+# quanto::qbits_mm_a8 (r6; int2 weights and e5m2 activations r7): F.linear(quantized activation, int4 / int2 weight) without dequantizing the activation
 # ------------------------------------------------------------------------------------------------
 def qbits_mm_a8_default(input, input_scale, packed, scale, shift, bias, bits: int, group_size: Optional[int], out_features: int, in_features: int):
     """What the reference computes (tensor/weights/awq/qbits.py:57-58, tensor/function.py:41-47): dequantize the activation, then the float product."""
@@ -312,6 +312,10 @@ def qbits_mm_a8_default(input, input_scale, packed, scale, shift, bias, bits: in
 
 
 _A8_MAX_TILES = int(os.environ.get("QUANTO_HIP_A8_MAX_TILES", "512")) if os.environ.get("QUANTO_HIP_EXPERIMENT", "0") not in ("", "0") else 512
+# int2 weights x int8 activations run 15-20 % slower than int4 x int8 on the same tiles (r7 sweep, profiles/r07_w2a8_crossover.jsonl: (512,4096,4096)
+# 35.5 vs 30.5 us) and lose to the dequantize-first sequence at the int4 cap: (512,14336,4096) = 448 tiles 111 vs 122 us, (2048,4096,4096) = 512 tiles
+# 112 vs 108.  int2 x e5m2 and int4 x e5m2 keep the int4 cap (2048,4096,4096: 98 / 89 vs 106).
+_A8_MAX_TILES_W2_INT8 = 448
 
 
 def qbits_mm_a8_hip(input, input_scale, packed, scale, shift, bias, bits: int, group_size: Optional[int], out_features: int, in_features: int):
@@ -322,8 +326,10 @@ def qbits_mm_a8_hip(input, input_scale, packed, scale, shift, bias, bits: int, g
     # ... while the output's 128 x 128 tiles are all resident at once (two workgroups per CU): the kernel moves 24 KiB through a CU's vector L1 per tile
     # and group and is bound by that, not by the matrix pipe; beyond one residency round the dequantize-first sequence on the dense bf16 GEMM is faster
     # (r6 sweep, profiles/r06_w4a8_crossover.jsonl: (2048,4096,4096) 93 vs 109 us, (4096,4096,4096) 184 vs 146, (768,14336,4096) 137 vs 114)
+    # one 128-token x 128-feature tile per workgroup for int4 (64 packed rows) and int2 (32 packed rows x 4 planes) alike
     tiles = -(-m // 128) * -(-out_features // 128)
-    if (64 < m and tiles <= _A8_MAX_TILES and input.dtype in lib.A8_DTYPES and input_scale.numel() == 1
+    cap = min(_A8_MAX_TILES, _A8_MAX_TILES_W2_INT8) if (bits == 2 and input.dtype == torch.int8) else _A8_MAX_TILES
+    if (64 < m and tiles <= cap and input.dtype in lib.A8_DTYPES and input_scale.numel() == 1
             and lib.qbits_mm_a8_workspace(m, out_features, in_features, bits, group_size, input.dtype, scale.dtype) >= 0):
         return lib.qbits_mm_a8(input, input_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features)
     return qbits_mm_a8_default(input, input_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features)
