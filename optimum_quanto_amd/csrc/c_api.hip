@@ -37,14 +37,13 @@ int qbits_conv2d_mfma(const void*, const uint8_t*, const void*, const void*, con
 size_t conv2d_workspace(int64_t, int64_t, int64_t);
 // depthwise convolution with an 8-bit weight (r6, qconv_depthwise.hip)
 int qbytes_conv2d_depthwise(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                            int64_t, int, int, int, int, int, int, int, int, int, hipStream_t);
-bool conv2d_last_was_rows();
+                            int64_t, int, int, int, int, int, int, int, int, int, hipStream_t, bool* strip);
 size_t conv2d_dense_weight_bytes(int64_t, int64_t);
 bool conv2d_rows_eligible(int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int64_t);
 int qdense_conv2d_rows(const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int,
                        int, int, int, int, int, void*, size_t, hipStream_t);
 int qbytes_conv2d_mfma(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                       int64_t, int, int, int, int, int, int, int, int, int, void*, size_t, hipStream_t);
+                       int64_t, int, int, int, int, int, int, int, int, int, void*, size_t, hipStream_t, bool* rows);
 int qbytes_mm_gemv_multi(const void*, int, const void* const*, const void* const*, const void* const*, void* const*, const int64_t*, int64_t,
                          int64_t, int, int, hipStream_t);
 bool qbytes_skinny_multi_supported(int, const int64_t*, int64_t, int64_t, int, int, int);
@@ -202,6 +201,33 @@ static int pick_qbits_kernel(int64_t M, const PackedGeom& g, int dtype, bool hav
   return QUANTO_HIP_KERNEL_NAIVE;
 }
 
+struct Plan {
+  int kernel;
+  int64_t workspace;  // bytes the kernel needs for this call (0: none, or the kernel does not take the call)
+};
+
+static int64_t qbits_kernel_workspace(int kernel, int64_t M, const PackedGeom& g, int dtype) {
+  switch (kernel) {
+    case QUANTO_HIP_KERNEL_SKINNY: return qbits_skinny_supported(M, g, dtype) ? (int64_t)qbits_skinny_workspace(M, g) : 0;
+    case QUANTO_HIP_KERNEL_MFMA: return qbits_mfma_supported(M, g, dtype) ? (int64_t)qbits_mfma_workspace(M, g) : 0;
+    case QUANTO_HIP_KERNEL_DEQUANT_MFMA: return dequant_mfma_supported(M, g, dtype) ? (int64_t)dequant_mfma_workspace(g) : 0;
+    case QUANTO_HIP_KERNEL_MFMA_FUSED4: return qbits_mfma_fused_supported(M, g, dtype) ? (int64_t)qbits_mfma_fused_workspace(M, g) : 0;
+  }
+  return 0;
+}
+
+// The kernel a qbits_mm call runs and the workspace it needs.  AUTO picks for a caller with (have_workspace) or without a workspace, then
+// steps down from the kernels that need more than workspace_bytes: the queries plan with (true, SIZE_MAX), the launch with what it was given.
+static Plan plan_qbits(int64_t M, const PackedGeom& g, int dtype, int kernel, bool have_workspace, size_t workspace_bytes) {
+  if (kernel == QUANTO_HIP_KERNEL_AUTO) {
+    kernel = pick_qbits_kernel(M, g, dtype, have_workspace);
+    if (kernel == QUANTO_HIP_KERNEL_DEQUANT_MFMA && workspace_bytes < dequant_mfma_workspace(g))
+      kernel = qbits_mfma_supported(M, g, dtype) ? QUANTO_HIP_KERNEL_MFMA : QUANTO_HIP_KERNEL_NAIVE;
+    if (kernel == QUANTO_HIP_KERNEL_MFMA && dtype != QUANTO_HIP_F32 && workspace_bytes < qbits_mfma_workspace(M, g)) kernel = QUANTO_HIP_KERNEL_NAIVE;
+  }
+  return {kernel, qbits_kernel_workspace(kernel, M, g, dtype)};
+}
+
 // The LDS-DMA pipelined kernel (256x256 or 128x128 tiles, picked inside) whenever its 128-tiles can occupy a good part of
 // the chip; the register-staged 128x128 kernel remains for what it does not support (fp32, K % 64 != 0, K < 128)
 // ... or M fills most of a 128-row tile: with the weights-direct loop a lone 128-tile workgroup streams a K-tile in 0.42 us,
@@ -267,33 +293,25 @@ int64_t quanto_hip_qbits_mm_workspace_size(int64_t M, int64_t N, int64_t K, int 
   bool int_shift = false;
   const int st = check_qbits(M, N, K, bits, group_size, dtype, dtype, &int_shift);
   if (st != QUANTO_HIP_OK) return st;
-  const PackedGeom g = make_geom(N, K, bits, group_size);
-  if (kernel == QUANTO_HIP_KERNEL_AUTO) kernel = pick_qbits_kernel(M, g, dtype, true);
-  if (kernel == QUANTO_HIP_KERNEL_SKINNY) return qbits_skinny_supported(M, g, dtype) ? (int64_t)qbits_skinny_workspace(M, g) : 0;
-  if (kernel == QUANTO_HIP_KERNEL_MFMA) return qbits_mfma_supported(M, g, dtype) ? (int64_t)qbits_mfma_workspace(M, g) : 0;
-  if (kernel == QUANTO_HIP_KERNEL_DEQUANT_MFMA) return dequant_mfma_supported(M, g, dtype) ? (int64_t)dequant_mfma_workspace(g) : 0;
-  if (kernel == QUANTO_HIP_KERNEL_MFMA_FUSED4) return qbits_mfma_fused_supported(M, g, dtype) ? (int64_t)qbits_mfma_fused_workspace(M, g) : 0;
-  return 0;
+  return plan_qbits(M, make_geom(N, K, bits, group_size), dtype, kernel, true, SIZE_MAX).workspace;
 }
 
 int quanto_hip_qbits_mm_pick(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype) {
   bool int_shift = false;
   const int st = check_qbits(M, N, K, bits, group_size, dtype, dtype, &int_shift);
   if (st != QUANTO_HIP_OK) return st;
-  return pick_qbits_kernel(M, make_geom(N, K, bits, group_size), dtype, true);
+  return plan_qbits(M, make_geom(N, K, bits, group_size), dtype, QUANTO_HIP_KERNEL_AUTO, true, SIZE_MAX).kernel;
 }
 
 int quanto_hip_qbits_mm_plan(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype, int kernel, int* kernel_out,
                              int64_t* workspace_bytes_out) {
   if (!kernel_out || !workspace_bytes_out) return QUANTO_HIP_EINVAL;
-  if (kernel == QUANTO_HIP_KERNEL_AUTO) {
-    kernel = quanto_hip_qbits_mm_pick(M, N, K, bits, group_size, dtype);
-    if (kernel < 0) return kernel;
-  }
-  const int64_t ws = quanto_hip_qbits_mm_workspace_size(M, N, K, bits, group_size, dtype, kernel);
-  if (ws < 0) return (int)ws;
-  *kernel_out = kernel;
-  *workspace_bytes_out = ws;
+  bool int_shift = false;
+  const int st = check_qbits(M, N, K, bits, group_size, dtype, dtype, &int_shift);
+  if (st != QUANTO_HIP_OK) return st;
+  const Plan p = plan_qbits(M, make_geom(N, K, bits, group_size), dtype, kernel, true, SIZE_MAX);
+  *kernel_out = p.kernel;
+  *workspace_bytes_out = p.workspace;
   return QUANTO_HIP_OK;
 }
 
@@ -307,42 +325,28 @@ int quanto_hip_qbits_mm(const void* x, const uint8_t* packed, const void* scale,
   if (!x || !packed || !scale || !shift || !y) return QUANTO_HIP_EINVAL;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const PackedGeom g = make_geom(N, K, bits, group_size);
-  if (kernel == QUANTO_HIP_KERNEL_AUTO) {
-    // the fast kernels need 16-byte aligned x / packed (views into larger buffers may not be): AUTO then takes the kernel that copes
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16) {
-      const int r = qbits_mm_naive(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("naive");
-      return r;
-    }
-    kernel = pick_qbits_kernel(M, g, dtype, workspace != nullptr);
-    if (kernel == QUANTO_HIP_KERNEL_DEQUANT_MFMA && workspace_bytes < dequant_mfma_workspace(g))
-      kernel = qbits_mfma_supported(M, g, dtype) ? QUANTO_HIP_KERNEL_MFMA : QUANTO_HIP_KERNEL_NAIVE;
-    if (kernel == QUANTO_HIP_KERNEL_MFMA && dtype != QUANTO_HIP_F32 && workspace_bytes < qbits_mfma_workspace(M, g)) kernel = QUANTO_HIP_KERNEL_NAIVE;
-  }
-  int r;
+  // the fast kernels need 16-byte aligned x / packed (views into larger buffers may not be): AUTO then takes the kernel that copes
+  if (kernel == QUANTO_HIP_KERNEL_AUTO && (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16)
+    kernel = QUANTO_HIP_KERNEL_NAIVE;
+  kernel = plan_qbits(M, g, dtype, kernel, workspace != nullptr, workspace_bytes).kernel;
+  const bool f32 = dtype == QUANTO_HIP_F32;
+  int r = QUANTO_HIP_EINVAL;
+  const char* name = "";
   switch (kernel) {
     case QUANTO_HIP_KERNEL_NAIVE:
       r = qbits_mm_naive(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("naive");
-      return r;
+      name = "naive";
+      break;
     case QUANTO_HIP_KERNEL_GEMV:
-      if (dtype == QUANTO_HIP_F32) {
-        r = qbits_mm_gemv_f32(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-        if (r == QUANTO_HIP_OK) set_last_kernel("gemv_f32");
-        return r;
-      }
-      r = qbits_mm_gemv(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("gemv");
-      return r;
-    case QUANTO_HIP_KERNEL_MFMA:
-      if (dtype == QUANTO_HIP_F32) {  // fp32 MFMA tiles: no workspace
-        r = qbits_mm_f32(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-        if (r == QUANTO_HIP_OK) set_last_kernel("mfma_f32");
-        return r;
-      }
-      r = qbits_mm_mfma(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, workspace, workspace_bytes, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("mfma");
-      return r;
+      r = f32 ? qbits_mm_gemv_f32(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream)
+              : qbits_mm_gemv(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
+      name = f32 ? "gemv_f32" : "gemv";
+      break;
+    case QUANTO_HIP_KERNEL_MFMA:  // fp32: MFMA tiles without a workspace
+      r = f32 ? qbits_mm_f32(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream)
+              : qbits_mm_mfma(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, workspace, workspace_bytes, stream);
+      name = f32 ? "mfma_f32" : "mfma";
+      break;
     case QUANTO_HIP_KERNEL_DEQUANT_MFMA:
       if (!dequant_mfma_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
       if (!workspace || workspace_bytes < dequant_mfma_workspace(g)) return QUANTO_HIP_EINVAL;
@@ -350,26 +354,27 @@ int quanto_hip_qbits_mm(const void* x, const uint8_t* packed, const void* scale,
       if (r != QUANTO_HIP_OK) return r;
       r = dense_mm_wd_supported(M, g.N, g.K, dtype) ? dense_mm_wd(x, workspace, bias, y, M, g.N, g.K, dtype, stream)
                                                     : dense_mm_large(x, workspace, bias, y, M, g.N, g.K, dtype, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("dequant_mfma");
-      return r;
+      name = "dequant_mfma";
+      break;
     case QUANTO_HIP_KERNEL_SKINNY:
       r = qbits_mm_skinny(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, workspace, workspace_bytes, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("skinny");
-      return r;
+      name = "skinny";
+      break;
     case QUANTO_HIP_KERNEL_MMV:
       r = qbits_mm_mmv(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("mmv");
-      return r;
+      name = "mmv";
+      break;
     case QUANTO_HIP_KERNEL_MFMA_FUSED4:
       r = qbits_mm_mfma_fused(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, workspace, workspace_bytes, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("mfma_fused4");
-      return r;
+      name = "mfma_fused4";
+      break;
     case QUANTO_HIP_KERNEL_MFMA_LARGE4:
       r = qbits_mm_mfma_large(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("mfma_large4");
-      return r;
+      name = "mfma_large4";
+      break;
   }
-  return QUANTO_HIP_EINVAL;
+  if (r == QUANTO_HIP_OK) set_last_kernel(name);
+  return r;
 }
 
 int64_t quanto_hip_qbits_mm_a8_workspace_size(int64_t M, int64_t N, int64_t K, int bits, int group_size, int a_dtype, int dtype) {
@@ -505,88 +510,88 @@ static int pick_qbytes_kernel(int64_t M, int64_t N, int64_t K, int a_dtype, int 
   return QUANTO_HIP_KERNEL_NAIVE;
 }
 
-int quanto_hip_qbytes_mm_pick(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
+// The kernel a qbytes_mm call runs and the workspace it needs (the kernels that split K run unsplit without one)
+static Plan plan_qbytes(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel) {
+  if (kernel == QUANTO_HIP_KERNEL_AUTO) kernel = pick_qbytes_kernel(M, N, K, a_dtype, b_dtype, out_dtype);
+  int64_t ws = 0;
+  if (kernel == QUANTO_HIP_KERNEL_SKINNY && qbytes_skinny_supported(M, N, K, a_dtype, b_dtype, out_dtype))
+    ws = (int64_t)qbytes_skinny_workspace(M, N, K);
+  else if (kernel == QUANTO_HIP_KERNEL_MFMA_LARGE && qbytes_mfma_large_supported(M, N, K, a_dtype, b_dtype, out_dtype))
+    ws = (int64_t)qbytes_mfma_large_workspace(M, N, K);
+  else if (kernel == QUANTO_HIP_KERNEL_NATIVE8)
+    ws = (int64_t)qbytes_native8_workspace(M, N, K, a_dtype, b_dtype, out_dtype);
+  return {kernel, ws};
+}
+
+static int check_qbytes(int64_t M, int64_t N, int64_t K, int out_dtype) {
   if (M < 0 || N <= 0 || K <= 0) return QUANTO_HIP_EINVAL;
-  if (!is_float_dtype(out_dtype)) return QUANTO_HIP_ENOTSUP;
-  return pick_qbytes_kernel(M, N, K, a_dtype, b_dtype, out_dtype);
+  return is_float_dtype(out_dtype) ? QUANTO_HIP_OK : QUANTO_HIP_ENOTSUP;
+}
+
+int quanto_hip_qbytes_mm_pick(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
+  const int st = check_qbytes(M, N, K, out_dtype);
+  return st != QUANTO_HIP_OK ? st : plan_qbytes(M, N, K, a_dtype, b_dtype, out_dtype, QUANTO_HIP_KERNEL_AUTO).kernel;
 }
 
 int64_t quanto_hip_qbytes_mm_workspace_size(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel) {
-  if (M < 0 || N <= 0 || K <= 0) return QUANTO_HIP_EINVAL;
-  if (!is_float_dtype(out_dtype)) return QUANTO_HIP_ENOTSUP;
-  if (kernel == QUANTO_HIP_KERNEL_AUTO) kernel = pick_qbytes_kernel(M, N, K, a_dtype, b_dtype, out_dtype);
-  if (kernel == QUANTO_HIP_KERNEL_SKINNY && qbytes_skinny_supported(M, N, K, a_dtype, b_dtype, out_dtype))
-    return (int64_t)qbytes_skinny_workspace(M, N, K);
-  if (kernel == QUANTO_HIP_KERNEL_MFMA_LARGE && qbytes_mfma_large_supported(M, N, K, a_dtype, b_dtype, out_dtype))
-    return (int64_t)qbytes_mfma_large_workspace(M, N, K);
-  if (kernel == QUANTO_HIP_KERNEL_NATIVE8) return (int64_t)qbytes_native8_workspace(M, N, K, a_dtype, b_dtype, out_dtype);
-  return 0;
+  const int st = check_qbytes(M, N, K, out_dtype);
+  return st != QUANTO_HIP_OK ? st : plan_qbytes(M, N, K, a_dtype, b_dtype, out_dtype, kernel).workspace;
 }
 
 int quanto_hip_qbytes_mm_plan(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel, int* kernel_out,
                               int64_t* workspace_bytes_out) {
   if (!kernel_out || !workspace_bytes_out) return QUANTO_HIP_EINVAL;
-  if (kernel == QUANTO_HIP_KERNEL_AUTO) {
-    kernel = quanto_hip_qbytes_mm_pick(M, N, K, a_dtype, b_dtype, out_dtype);
-    if (kernel < 0) return kernel;
-  }
-  const int64_t ws = quanto_hip_qbytes_mm_workspace_size(M, N, K, a_dtype, b_dtype, out_dtype, kernel);
-  if (ws < 0) return (int)ws;
-  *kernel_out = kernel;
-  *workspace_bytes_out = ws;
+  const int st = check_qbytes(M, N, K, out_dtype);
+  if (st != QUANTO_HIP_OK) return st;
+  const Plan p = plan_qbytes(M, N, K, a_dtype, b_dtype, out_dtype, kernel);
+  *kernel_out = p.kernel;
+  *workspace_bytes_out = p.workspace;
   return QUANTO_HIP_OK;
 }
 
 int quanto_hip_qbytes_mm_ws(const void* a, const void* b, const void* scales, const void* bias, void* y, int64_t M, int64_t N, int64_t K,
                             int a_dtype, int b_dtype, int out_dtype, int kernel, void* workspace, size_t workspace_bytes, void* stream_) {
-  if (M < 0 || N <= 0 || K <= 0) return QUANTO_HIP_EINVAL;
-  if (!is_float_dtype(out_dtype)) return QUANTO_HIP_ENOTSUP;
+  const int st = check_qbytes(M, N, K, out_dtype);
+  if (st != QUANTO_HIP_OK) return st;
   if (M == 0) return QUANTO_HIP_OK;
   if (!a || !b || !scales || !y) return QUANTO_HIP_EINVAL;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (kernel == QUANTO_HIP_KERNEL_AUTO) {
-    kernel = pick_qbytes_kernel(M, N, K, a_dtype, b_dtype, out_dtype);
-    // misaligned views: the kernel that has no alignment requirement
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) % 16) kernel = QUANTO_HIP_KERNEL_NAIVE;
-  }
-  int r;
+  // misaligned views: AUTO takes the kernel that has no alignment requirement
+  if (kernel == QUANTO_HIP_KERNEL_AUTO && (reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) % 16) kernel = QUANTO_HIP_KERNEL_NAIVE;
+  kernel = plan_qbytes(M, N, K, a_dtype, b_dtype, out_dtype, kernel).kernel;
+  const bool f32 = a_dtype == QUANTO_HIP_F32 && out_dtype == QUANTO_HIP_F32;
+  int r = QUANTO_HIP_EINVAL;
+  const char* name = "";
   switch (kernel) {
     case QUANTO_HIP_KERNEL_NAIVE:
       r = qbytes_mm_naive(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("naive");
-      return r;
+      name = "naive";
+      break;
     case QUANTO_HIP_KERNEL_GEMV:
-      if (a_dtype == QUANTO_HIP_F32 && out_dtype == QUANTO_HIP_F32) {
-        r = qbytes_mm_gemv_f32(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream);
-        if (r == QUANTO_HIP_OK) set_last_kernel("gemv_f32");
-        return r;
-      }
-      r = qbytes_mm_gemv(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("gemv");
-      return r;
+      r = f32 ? qbytes_mm_gemv_f32(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream)
+              : qbytes_mm_gemv(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream);
+      name = f32 ? "gemv_f32" : "gemv";
+      break;
     case QUANTO_HIP_KERNEL_SKINNY:
       r = qbytes_mm_skinny(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("skinny");
-      return r;
+      name = "skinny";
+      break;
     case QUANTO_HIP_KERNEL_MFMA:
-      if (a_dtype == QUANTO_HIP_F32 && out_dtype == QUANTO_HIP_F32) {
-        r = qbytes_mm_f32(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream);
-        if (r == QUANTO_HIP_OK) set_last_kernel("mfma_f32");
-        return r;
-      }
-      r = qbytes_mm_mfma(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("mfma");
-      return r;
+      r = f32 ? qbytes_mm_f32(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream)
+              : qbytes_mm_mfma(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream);
+      name = f32 ? "mfma_f32" : "mfma";
+      break;
     case QUANTO_HIP_KERNEL_MFMA_LARGE:
       r = qbytes_mm_mfma_large(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("mfma_large");
-      return r;
+      name = "mfma_large";
+      break;
     case QUANTO_HIP_KERNEL_NATIVE8:
       r = qbytes_mm_native8(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
-      if (r == QUANTO_HIP_OK) set_last_kernel("mfma_native8");
-      return r;
+      name = "mfma_native8";
+      break;
   }
-  return QUANTO_HIP_EINVAL;
+  if (r == QUANTO_HIP_OK) set_last_kernel(name);
+  return r;
 }
 
 // ---- several qbytes_mm products that share the activation (q/k/v, gate/up of an int8 / fp8 model), see quanto_hip_qbits_mm_multi -----
@@ -727,34 +732,43 @@ int64_t quanto_hip_qbits_conv2d_workspace_size_geom(int64_t B, int64_t cin, int6
   return split + (qbits_conv2d_takes_rows(B, cin, W, OC, KH, KW, OH, OW, stride_w, dil_w) ? (int64_t)conv2d_dense_weight_bytes(OC, K) : 0);
 }
 
+static int check_conv2d_args(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h,
+                             int stride_w, int pad_h, int pad_w, int dil_h, int dil_w) {
+  if (B < 0 || cin <= 0 || H <= 0 || W <= 0 || OC <= 0 || KH <= 0 || KW <= 0 || OH < 0 || OW < 0) return QUANTO_HIP_EINVAL;
+  if (stride_h <= 0 || stride_w <= 0 || pad_h < 0 || pad_w < 0 || dil_h <= 0 || dil_w <= 0) return QUANTO_HIP_EINVAL;
+  if (OH != (H + 2 * pad_h - dil_h * (KH - 1) - 1) / stride_h + 1 || OW != (W + 2 * pad_w - dil_w * (KW - 1) - 1) / stride_w + 1) return QUANTO_HIP_EINVAL;
+  return QUANTO_HIP_OK;
+}
+
 int quanto_hip_qbytes_conv2d(const void* x, const void* w, const void* scales, const void* bias, void* y, int64_t B, int64_t cin, int64_t H,
                              int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
                              int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes,
                              void* stream) {
-  if (B < 0 || cin <= 0 || H <= 0 || W <= 0 || OC <= 0 || KH <= 0 || KW <= 0 || OH < 0 || OW < 0) return QUANTO_HIP_EINVAL;
-  if (stride_h <= 0 || stride_w <= 0 || pad_h < 0 || pad_w < 0 || dil_h <= 0 || dil_w <= 0) return QUANTO_HIP_EINVAL;
-  if (OH != (H + 2 * pad_h - dil_h * (KH - 1) - 1) / stride_h + 1 || OW != (W + 2 * pad_w - dil_w * (KW - 1) - 1) / stride_w + 1) return QUANTO_HIP_EINVAL;
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+  if (geo != QUANTO_HIP_OK) return geo;
   if (!is_float_dtype(out_dtype)) return QUANTO_HIP_ENOTSUP;
   if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
   if (!x || !w || !scales || !y) return QUANTO_HIP_EINVAL;
+  bool rows = false;
   const int r = qbytes_conv2d_mfma(x, w, scales, bias, y, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, a_dtype,
-                                   b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
-  if (r == QUANTO_HIP_OK) set_last_kernel(conv2d_last_was_rows() ? "conv2d_mfma_rows" : "conv2d_mfma");
+                                   b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), &rows);
+  if (r == QUANTO_HIP_OK) set_last_kernel(rows ? "conv2d_mfma_rows" : "conv2d_mfma");
   return r;
 }
 
 int quanto_hip_qbytes_conv2d_depthwise(const void* x, const void* w, const void* scales, const void* bias, void* y, int64_t B, int64_t cin, int64_t H,
                                        int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
                                        int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype, void* stream) {
-  if (B < 0 || cin <= 0 || H <= 0 || W <= 0 || OC <= 0 || KH <= 0 || KW <= 0 || OH < 0 || OW < 0 || OC % cin != 0) return QUANTO_HIP_EINVAL;
-  if (stride_h <= 0 || stride_w <= 0 || pad_h < 0 || pad_w < 0 || dil_h <= 0 || dil_w <= 0) return QUANTO_HIP_EINVAL;
-  if (OH != (H + 2 * pad_h - dil_h * (KH - 1) - 1) / stride_h + 1 || OW != (W + 2 * pad_w - dil_w * (KW - 1) - 1) / stride_w + 1) return QUANTO_HIP_EINVAL;
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+  if (geo != QUANTO_HIP_OK) return geo;
+  if (OC % cin != 0) return QUANTO_HIP_EINVAL;
   if (!is_float_dtype(out_dtype)) return QUANTO_HIP_ENOTSUP;
   if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
   if (!x || !w || !scales || !y) return QUANTO_HIP_EINVAL;
+  bool strip = false;  // 16-byte row chunks; otherwise quads
   const int r = qbytes_conv2d_depthwise(x, w, scales, bias, y, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, a_dtype,
-                                        b_dtype, out_dtype, reinterpret_cast<hipStream_t>(stream));
-  // (the form that ran names itself: "conv2d_depthwise" = quads, "conv2d_depthwise_strip" = 16-byte row chunks)
+                                        b_dtype, out_dtype, reinterpret_cast<hipStream_t>(stream), &strip);
+  if (r == QUANTO_HIP_OK) set_last_kernel(strip ? "conv2d_depthwise_strip" : "conv2d_depthwise");
   return r;
 }
 
@@ -762,9 +776,8 @@ int quanto_hip_qbits_conv2d(const void* x, const uint8_t* packed, const void* sc
                             int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
                             int pad_w, int dil_h, int dil_w, int bits, int group_size, int dtype, int shift_dtype, void* workspace,
                             size_t workspace_bytes, void* stream) {
-  if (B < 0 || cin <= 0 || H <= 0 || W <= 0 || OC <= 0 || KH <= 0 || KW <= 0 || OH < 0 || OW < 0) return QUANTO_HIP_EINVAL;
-  if (stride_h <= 0 || stride_w <= 0 || pad_h < 0 || pad_w < 0 || dil_h <= 0 || dil_w <= 0) return QUANTO_HIP_EINVAL;
-  if (OH != (H + 2 * pad_h - dil_h * (KH - 1) - 1) / stride_h + 1 || OW != (W + 2 * pad_w - dil_w * (KW - 1) - 1) / stride_w + 1) return QUANTO_HIP_EINVAL;
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+  if (geo != QUANTO_HIP_OK) return geo;
   bool int_shift = false;
   const int64_t K = cin * KH * KW;
   const int st = check_qbits(B * OH * OW, OC, K, bits, group_size, dtype, shift_dtype, &int_shift);

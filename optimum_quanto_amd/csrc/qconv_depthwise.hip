@@ -275,7 +275,8 @@ bool qbytes_conv2d_depthwise_supported(int64_t B, int64_t C, int64_t H, int64_t 
 
 int qbytes_conv2d_depthwise(const void* x, const void* w, const void* scales, const void* bias, void* y, int64_t B, int64_t C, int64_t H, int64_t W,
                             int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int sh, int sw, int ph, int pw, int dh, int dw, int a_dtype,
-                            int b_dtype, int out_dtype, hipStream_t stream) {
+                            int b_dtype, int out_dtype, hipStream_t stream, bool* strip) {
+  *strip = false;
   if (!qbytes_conv2d_depthwise_supported(B, C, H, W, OC, KH, KW, OH, OW, sh, sw, ph, pw, dh, dw, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
   const dw::Args a{x, reinterpret_cast<const uint8_t*>(w), scales, bias, y, (int)B, (int)C, (int)H, (int)W, (int)OC, (int)(OC / C), (int)KH, (int)KW, (int)OH,
                    (int)OW, sh, sw, ph, pw, dh, dw, (int)((OW + dw::PX - 1) / dw::PX)};
@@ -284,10 +285,9 @@ int qbytes_conv2d_depthwise(const void* x, const void* w, const void* scales, co
   if (b_dtype == QUANTO_HIP_F8_E4M3FN) return dw::launch<DT, QUANTO_HIP_F8_E4M3FN>(a, stream);           \
   return dw::launch<DT, QUANTO_HIP_F8_E5M2>(a, stream)
   if (dw::strip_eligible(a)) {
-    set_last_kernel("conv2d_depthwise_strip");
+    *strip = true;
     return a_dtype == QUANTO_HIP_BF16 ? dw::launch_strip_dt<QUANTO_HIP_BF16>(a, b_dtype, stream) : dw::launch_strip_dt<QUANTO_HIP_F16>(a, b_dtype, stream);
   }
-  set_last_kernel("conv2d_depthwise");
   if (a_dtype == QUANTO_HIP_BF16) { QH_DW(QUANTO_HIP_BF16); }
   QH_DW(QUANTO_HIP_F16);
 #undef QH_DW

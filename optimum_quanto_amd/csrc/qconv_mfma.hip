@@ -993,8 +993,6 @@ __global__ void __launch_bounds__(64) qconv2d_reduce_kernel(const Args a) {
 // K split: the tile kernel is bound by its gather per K-tile (~1.9 us per workgroup and K-tile whatever M is), so what matters is how many
 // workgroups run at once: split until the grid reaches ~2 workgroups per CU, keeping at least 4 K-tiles per split (r5, after the gather and the
 // epilogue got cheaper: profiles/r05_qconv2d_split_sweep.jsonl - 3 per split over-split 26-49-tile grids by 10-14 %).  1 = no split (and no workspace).
-static thread_local bool g_last_rows = false;  // the last launch of this thread took the row form (last_kernel() name, tests)
-
 static int pick_split(int64_t M, int64_t N, int64_t K) {
   const int forced = env_int("QUANTO_HIP_CONV_SPLIT", 0);  // experiments
   const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN), nk = (K + BK - 1) / BK;
@@ -1017,7 +1015,6 @@ static bool rows_eligible(int64_t cin, int64_t KH, int64_t KW, int64_t W, int64_
 static bool rows_pairs(int64_t OW, int sw) { return sw == 1 && OW % 2 == 0 && env_int("QUANTO_HIP_CONV_ROWS", 1) != 3; }
 template <int DT, int FMT>
 static int launch_rows(Args a, int ntiles, int mtiles, hipStream_t stream) {  // a.S: the split the workspace allows; a.partials set
-  g_last_rows = true;
   const int nk_rows = (a.cin * a.KH + rows::RT - 1) / rows::RT;
   a.S = a.S < nk_rows ? a.S : nk_rows;
   // two LDS buffers where every workgroup has a CU to itself anyway (QUANTO_HIP_CONV_ROWS_DB: 0 never, 2 always - experiments)
@@ -1046,11 +1043,11 @@ static void launch_k(const Args& a, int ntiles, int mtiles, hipStream_t stream) 
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qconv2d_mfma_kernel<DT, FMT, INT_SHIFT, WIDE, PAIR>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   hipLaunchKernelGGL((qconv2d_mfma_kernel<DT, FMT, INT_SHIFT, WIDE, PAIR>), dim3(ntiles, mtiles, a.S), dim3(NT), LDS_BYTES, stream, a);
 }
+// *rows (when asked): whether the row form ran
 template <int DT, int FMT, bool INT_SHIFT, bool WIDE>
-static int launch_w(Args a, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+static int launch_w(Args a, void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows) {
   constexpr int PL = planes_of(FMT);
   const int ntiles = PL > 1 ? (a.N / PL + BN / PL - 1) / (BN / PL) : (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;
-  g_last_rows = false;
   int S = pick_split(a.M, a.N, a.K);
   if (S > 1 && (!workspace || workspace_bytes < split_workspace(a.M, a.N, S) || reinterpret_cast<uintptr_t>(workspace) % 16)) S = 1;
   a.S = S;
@@ -1058,6 +1055,7 @@ static int launch_w(Args a, void* workspace, size_t workspace_bytes, hipStream_t
   if constexpr (PL == 1 && !WIDE) {
     if (rows_eligible(a.cin, a.KH, a.KW, a.W, a.OW, a.sw, a.dw)) {
       a.S = S;
+      if (rows) *rows = true;
       return launch_rows<DT, FMT>(a, ntiles, mtiles, stream);
     }
   }
@@ -1071,9 +1069,9 @@ static int launch_w(Args a, void* workspace, size_t workspace_bytes, hipStream_t
   return launch_status();
 }
 template <int DT, int FMT, bool INT_SHIFT>
-static int launch(Args a, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  return a.KH * a.KW > 31 ? launch_w<DT, FMT, INT_SHIFT, true>(a, workspace, workspace_bytes, stream)
-                          : launch_w<DT, FMT, INT_SHIFT, false>(a, workspace, workspace_bytes, stream);
+static int launch(Args a, void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows = nullptr) {
+  return a.KH * a.KW > 31 ? launch_w<DT, FMT, INT_SHIFT, true>(a, workspace, workspace_bytes, stream, rows)
+                          : launch_w<DT, FMT, INT_SHIFT, false>(a, workspace, workspace_bytes, stream, rows);
 }
 
 static bool geometry_ok(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW) {
@@ -1084,8 +1082,6 @@ static bool geometry_ok(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC
 }
 
 }  // namespace conv
-
-bool conv2d_last_was_rows() { return conv::g_last_rows; }
 
 bool qbytes_conv2d_supported(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int a_dtype,
                              int b_dtype, int out_dtype) {
@@ -1123,12 +1119,13 @@ int qdense_conv2d_rows(const void* x, const void* wdense, const void* bias, void
 
 int qbytes_conv2d_mfma(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC,
                        int64_t KH, int64_t KW, int64_t OH, int64_t OW, int sh, int sw, int ph, int pw, int dh, int dw, int a_dtype, int b_dtype,
-                       int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+                       int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows) {
+  *rows = false;
   if (!qbytes_conv2d_supported(B, cin, H, W, OC, KH, KW, OH, OW, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
   const conv::Args a{x, reinterpret_cast<const uint8_t*>(w), s, nullptr, bias, y, (int)(B * OH * OW), (int)OC, (int)(cin * KH * KW), 0, 0,
                      (int)cin, (int)H, (int)W, (int)KH, (int)KW, (int)OH, (int)OW, sh, sw, ph, pw, dh, dw, 1, nullptr, conv::div_magic((int)(KH * KW)), conv::div_magic((int)KW), conv::div_magic((int)KH)};
   using namespace conv;
-#define QH_CASE(DT, FMT) return launch<DT, FMT, false>(a, workspace, workspace_bytes, stream)
+#define QH_CASE(DT, FMT) return launch<DT, FMT, false>(a, workspace, workspace_bytes, stream, rows)
   if (out_dtype == QUANTO_HIP_BF16) {
     if (b_dtype == QUANTO_HIP_I8) QH_CASE(QUANTO_HIP_BF16, W_I8);
     if (b_dtype == QUANTO_HIP_F8_E4M3FN) QH_CASE(QUANTO_HIP_BF16, W_F8E4M3);

@@ -74,16 +74,20 @@ except AttributeError:  # pragma: no cover - other torch builds
 
 
 class _DeviceGuard:
-    """``with torch.cuda.device(d)`` only when ``d`` is not already current: the context manager costs ~3 us per call, the check 0.2."""
+    """``with _DeviceGuard(d) as stream``: makes ``d`` the current device for the block and yields the raw handle of torch's current stream on it.
+    ``torch.cuda.device`` is entered only when ``d`` is not already current: the context manager costs ~3 us per call, the check 0.2."""
 
-    __slots__ = ("ctx",)
+    __slots__ = ("ctx", "index")
 
     def __init__(self, device: torch.device):
-        self.ctx = None if device.index is None or device.index == _current_device() else torch.cuda.device(device)
+        index, current = device.index, _current_device()
+        self.index = current if index is None else index
+        self.ctx = None if index is None or index == current else torch.cuda.device(device)
 
-    def __enter__(self):
+    def __enter__(self) -> int:
         if self.ctx is not None:
             self.ctx.__enter__()
+        return _raw_stream(self.index)
 
     def __exit__(self, *exc):
         if self.ctx is not None:
@@ -91,81 +95,57 @@ class _DeviceGuard:
         return False
 
 
+_vp, _i64, _ci, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t
+_pvp, _pi64, _pci = ctypes.POINTER(_vp), ctypes.POINTER(_i64), ctypes.POINTER(_ci)
+# name: (restype, argtypes) of every entry of include/quanto_hip.h
+_PROTOTYPES = {
+    "quanto_hip_abi_version": (_ci, None),
+    "quanto_hip_status_string": (ctypes.c_char_p, [_ci]),
+    "quanto_hip_last_kernel": (ctypes.c_char_p, None),
+    "quanto_hip_stream_capture_id": (_i64, [_vp]),
+    "quanto_hip_unpack": (_ci, [_vp, _vp, _i64, _ci, _vp]),
+    "quanto_hip_dequantize_qbits": (_ci, [_vp] * 4 + [_i64] * 2 + [_ci] * 4 + [_vp]),
+    "quanto_hip_qbits_mm": (_ci, [_vp] * 6 + [_i64] * 3 + [_ci] * 5 + [_vp, _sz, _vp]),
+    "quanto_hip_qbits_mm_multi": (_ci, [_vp, _ci] + [_pvp] * 5 + [_pi64, _i64, _i64] + [_ci] * 4 + [_vp]),
+    "quanto_hip_qbits_mm_multi_ws": (_ci, [_vp, _ci] + [_pvp] * 5 + [_pi64, _i64, _i64] + [_ci] * 4 + [_vp, _sz, _vp]),
+    "quanto_hip_qbits_mm_multi_plan": (_ci, [_ci, _pi64, _i64, _i64] + [_ci] * 3 + [_pci, _pi64]),
+    "quanto_hip_qbytes_mm_multi_ws": (_ci, [_vp, _ci] + [_pvp] * 4 + [_pi64, _i64, _i64] + [_ci] * 3 + [_vp, _sz, _vp]),
+    "quanto_hip_qbytes_mm_multi_plan": (_ci, [_ci, _pi64, _i64, _i64] + [_ci] * 3 + [_pci, _pi64]),
+    "quanto_hip_qbits_mm_workspace_size": (_i64, [_i64] * 3 + [_ci] * 4),
+    "quanto_hip_qbits_mm_plan": (_ci, [_i64] * 3 + [_ci] * 4 + [_pci, _pi64]),
+    "quanto_hip_qbits_mm_pick": (_ci, [_i64] * 3 + [_ci] * 3),
+    "quanto_hip_qbits_mm_a8": (_ci, [_vp] * 7 + [_i64] * 3 + [_ci] * 5 + [_vp, _sz, _vp]),
+    "quanto_hip_qbits_mm_a8_workspace_size": (_i64, [_i64] * 3 + [_ci] * 4),
+    "quanto_hip_qbytes_mm": (_ci, [_vp] * 5 + [_i64] * 3 + [_ci] * 4 + [_vp]),
+    "quanto_hip_qbytes_mm_ws": (_ci, [_vp] * 5 + [_i64] * 3 + [_ci] * 4 + [_vp, _sz, _vp]),
+    "quanto_hip_qbytes_mm_workspace_size": (_i64, [_i64] * 3 + [_ci] * 4),
+    "quanto_hip_qbytes_mm_plan": (_ci, [_i64] * 3 + [_ci] * 4 + [_pci, _pi64]),
+    "quanto_hip_qbytes_mm_pick": (_ci, [_i64] * 3 + [_ci] * 3),
+    "quanto_hip_quantize_symmetric": (_ci, [_vp] * 3 + [_i64] * 2 + [_ci] * 3 + [_vp]),
+    "quanto_hip_dequantize_symmetric": (_ci, [_vp] * 3 + [_i64] + [_ci] * 2 + [_vp]),
+    "quanto_hip_quantize_affine": (_ci, [_vp] * 4 + [_i64] * 2 + [_ci] * 4 + [_vp]),
+    "quanto_hip_quantize_affine_packed": (_ci, [_vp] * 4 + [_i64] * 2 + [_ci] * 4 + [_vp]),
+    "quanto_hip_pack": (_ci, [_vp, _vp, _i64, _i64, _ci, _vp]),
+    "quanto_hip_qbytes_conv2d": (_ci, [_vp] * 5 + [_i64] * 9 + [_ci] * 9 + [_vp, _sz, _vp]),
+    "quanto_hip_qbytes_conv2d_depthwise": (_ci, [_vp] * 5 + [_i64] * 9 + [_ci] * 9 + [_vp]),
+    "quanto_hip_conv2d_workspace_size": (_i64, [_i64] * 5),
+    "quanto_hip_qbits_conv2d_workspace_size": (_i64, [_i64] * 5),
+    "quanto_hip_qbits_conv2d_workspace_size_geom": (_i64, [_i64] * 8 + [_ci] * 2),
+    "quanto_hip_qbits_conv2d": (_ci, [_vp] * 6 + [_i64] * 9 + [_ci] * 10 + [_vp, _sz, _vp]),
+}
+
+
 class _Bindings:
     """Typed entry points; one instance per loaded library."""
 
     def __init__(self, cdll: ctypes.CDLL):
-        c = cdll
-        vp, i64, ci, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t
-        c.quanto_hip_abi_version.restype = ci
-        c.quanto_hip_status_string.restype = ctypes.c_char_p
-        c.quanto_hip_status_string.argtypes = [ci]
-        c.quanto_hip_last_kernel.restype = ctypes.c_char_p
-        c.quanto_hip_stream_capture_id.restype = i64
-        c.quanto_hip_stream_capture_id.argtypes = [vp]
-        c.quanto_hip_unpack.restype = ci
-        c.quanto_hip_unpack.argtypes = [vp, vp, i64, ci, vp]
-        c.quanto_hip_dequantize_qbits.restype = ci
-        c.quanto_hip_dequantize_qbits.argtypes = [vp, vp, vp, vp, i64, i64, ci, ci, ci, ci, vp]
-        c.quanto_hip_qbits_mm.restype = ci
-        c.quanto_hip_qbits_mm.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, ci, ci, ci, ci, ci, vp, sz, vp]
-        c.quanto_hip_qbits_mm_multi.restype = ci
-        c.quanto_hip_qbits_mm_multi.argtypes = [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                                ctypes.POINTER(vp), ctypes.POINTER(i64), i64, i64, ci, ci, ci, ci, vp]
-        c.quanto_hip_qbits_mm_multi_ws.restype = ci
-        c.quanto_hip_qbits_mm_multi_ws.argtypes = [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                                   ctypes.POINTER(vp), ctypes.POINTER(i64), i64, i64, ci, ci, ci, ci, vp, sz, vp]
-        c.quanto_hip_qbits_mm_multi_plan.restype = ci
-        c.quanto_hip_qbits_mm_multi_plan.argtypes = [ci, ctypes.POINTER(i64), i64, i64, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(i64)]
-        c.quanto_hip_qbytes_mm_multi_ws.restype = ci
-        c.quanto_hip_qbytes_mm_multi_ws.argtypes = [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                                    ctypes.POINTER(i64), i64, i64, ci, ci, ci, vp, sz, vp]
-        c.quanto_hip_qbytes_mm_multi_plan.restype = ci
-        c.quanto_hip_qbytes_mm_multi_plan.argtypes = [ci, ctypes.POINTER(i64), i64, i64, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(i64)]
-        c.quanto_hip_qbits_mm_workspace_size.restype = i64
-        c.quanto_hip_qbits_mm_workspace_size.argtypes = [i64, i64, i64, ci, ci, ci, ci]
-        c.quanto_hip_qbits_mm_plan.restype = ci
-        c.quanto_hip_qbits_mm_plan.argtypes = [i64, i64, i64, ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(i64)]
-        c.quanto_hip_qbytes_mm_plan.restype = ci
-        c.quanto_hip_qbytes_mm_plan.argtypes = [i64, i64, i64, ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(i64)]
-        c.quanto_hip_qbits_mm_pick.restype = ci
-        c.quanto_hip_qbits_mm_pick.argtypes = [i64, i64, i64, ci, ci, ci]
-        c.quanto_hip_qbytes_mm.restype = ci
-        c.quanto_hip_qbytes_mm.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, ci, ci, ci, ci, vp]
-        c.quanto_hip_qbits_mm_a8.restype = ci
-        c.quanto_hip_qbits_mm_a8.argtypes = [vp] * 7 + [i64] * 3 + [ci] * 5 + [vp, sz, vp]
-        c.quanto_hip_qbits_mm_a8_workspace_size.restype = i64
-        c.quanto_hip_qbits_mm_a8_workspace_size.argtypes = [i64] * 3 + [ci] * 4
-        c.quanto_hip_qbytes_mm_ws.restype = ci
-        c.quanto_hip_qbytes_mm_ws.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, ci, ci, ci, ci, vp, sz, vp]
-        c.quanto_hip_qbytes_mm_workspace_size.restype = i64
-        c.quanto_hip_qbytes_mm_workspace_size.argtypes = [i64, i64, i64, ci, ci, ci, ci]
-        c.quanto_hip_qbytes_mm_pick.restype = ci
-        c.quanto_hip_qbytes_mm_pick.argtypes = [i64, i64, i64, ci, ci, ci]
-        c.quanto_hip_quantize_symmetric.restype = ci
-        c.quanto_hip_quantize_symmetric.argtypes = [vp, vp, vp, i64, i64, ci, ci, ci, vp]
-        c.quanto_hip_quantize_affine.restype = ci
-        c.quanto_hip_quantize_affine.argtypes = [vp, vp, vp, vp, i64, i64, ci, ci, ci, ci, vp]
-        c.quanto_hip_quantize_affine_packed.restype = ci
-        c.quanto_hip_quantize_affine_packed.argtypes = [vp, vp, vp, vp, i64, i64, ci, ci, ci, ci, vp]
-        c.quanto_hip_pack.restype = ci
-        c.quanto_hip_pack.argtypes = [vp, vp, i64, i64, ci, vp]
-        c.quanto_hip_qbytes_conv2d.restype = ci
-        c.quanto_hip_qbytes_conv2d.argtypes = [vp, vp, vp, vp, vp] + [i64] * 9 + [ci] * 9 + [vp, ctypes.c_size_t, vp]
-        c.quanto_hip_dequantize_symmetric.restype = ci
-        c.quanto_hip_dequantize_symmetric.argtypes = [vp, vp, vp, i64, ci, ci, vp]
-        c.quanto_hip_qbytes_conv2d_depthwise.restype = ci
-        c.quanto_hip_qbytes_conv2d_depthwise.argtypes = [vp, vp, vp, vp, vp] + [i64] * 9 + [ci] * 9 + [vp]
-        c.quanto_hip_conv2d_workspace_size.restype = i64
-        c.quanto_hip_conv2d_workspace_size.argtypes = [i64] * 5
-        c.quanto_hip_qbits_conv2d_workspace_size.restype = i64
-        c.quanto_hip_qbits_conv2d_workspace_size.argtypes = [i64] * 5
-        c.quanto_hip_qbits_conv2d_workspace_size_geom.restype = i64
-        c.quanto_hip_qbits_conv2d_workspace_size_geom.argtypes = [i64] * 8 + [ci] * 2
-        c.quanto_hip_qbits_conv2d.restype = ci
-        c.quanto_hip_qbits_conv2d.argtypes = [vp] * 6 + [i64] * 9 + [ci] * 10 + [vp, ctypes.c_size_t, vp]
-        self._c = c
-        if c.quanto_hip_abi_version() != 1:
+        for name, (restype, argtypes) in _PROTOTYPES.items():
+            fn = getattr(cdll, name)
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
+        self._c = cdll
+        if cdll.quanto_hip_abi_version() != 1:
             raise QuantoHipError("libquanto_hip.so ABI version mismatch: rebuild with __graft_entry__.build()")
 
     # -- helpers ----------------------------------------------------------------------------------
@@ -175,24 +155,18 @@ class _Bindings:
             raise QuantoHipError(f"quanto_hip.{what} failed: {msg} (status {status})")
 
     @staticmethod
-    def _stream(t: torch.Tensor):
-        return ctypes.c_void_p(_raw_stream(t.device.index if t.device.index is not None else _current_device()))
-
-    @staticmethod
     def _require_cuda(*tensors):
         for t in tensors:
             if t is not None and not t.is_cuda:
                 raise QuantoHipError("quanto_hip kernels only accept tensors on a ROCm device")
 
-    def _zeroed_workspace(self, device: torch.device, nbytes: int, stream) -> torch.Tensor:
-        """Split-K workspace: [QUANTO_HIP_WS_COUNTER_BYTES of arrival counters | fp32 partial sums] (include/quanto_hip.h).
-        One buffer per (device, stream, capture): its counter region zero-filled once when (re)allocated and only ever handed to kernels that
-        restore the counter words they use.  Launches on one stream reuse it in stream order; launches on different streams
-        of one device may overlap, so each stream gets its own counters.  A buffer allocated while the stream is being
-        captured lives in that graph's memory pool and its zero-fill is a node of that graph (re-run on every replay): it is
+    def _stream_buffer(self, pool: str, device: torch.device, nbytes: int, stream: int, zero_counters: bool) -> torch.Tensor:
+        """One growing buffer per (device, stream, capture) in ``pool`` instead of an allocation per call.  Launches on one stream use it in
+        stream order; launches on different streams of one device may overlap, so each stream gets its own.  A buffer allocated while the
+        stream is being captured lives in that graph's memory pool (and a zero-fill is a node of that graph, re-run on every replay): it is
         keyed by the capture id so that neither eager launches nor another capture ever see it."""
-        cache = self.__dict__.setdefault("_zero_ws", {})
-        capture = self._c.quanto_hip_stream_capture_id(ctypes.c_void_p(stream))
+        cache = self.__dict__.setdefault(pool, {})
+        capture = self._c.quanto_hip_stream_capture_id(stream)
         if capture < 0:
             self._check(int(capture), "stream_capture_id")
         key = (device, stream, capture)
@@ -201,29 +175,51 @@ class _Bindings:
             if len(cache) > 64:  # stream handles / capture ids come and go: do not keep dead buffers alive forever
                 for k in [k for k in cache if k[2] != 0 and k != key]:
                     del cache[k]
-            # only the counter region has to be zero (include/quanto_hip.h: QUANTO_HIP_WS_COUNTER_BYTES; the kernels restore what they
-            # use, the partial sums behind it are never read before they are written): 4 KiB of fill - under capture a 4 KiB memset
-            # node per replay instead of one over the whole buffer (8-17 MB)
-            buf = torch.empty((max(nbytes, 8 << 20),), dtype=torch.uint8, device=device)
-            buf[:WS_COUNTER_BYTES].zero_()
+            if zero_counters:
+                # only the counter region has to be zero (include/quanto_hip.h: QUANTO_HIP_WS_COUNTER_BYTES; the kernels restore what they
+                # use, the partial sums behind it are never read before they are written): 4 KiB of fill - under capture a 4 KiB memset
+                # node per replay instead of one over the whole buffer (8-17 MB)
+                buf = torch.empty((max(nbytes, 8 << 20),), dtype=torch.uint8, device=device)
+                buf[:WS_COUNTER_BYTES].zero_()
+            else:
+                buf = torch.empty((nbytes,), dtype=torch.uint8, device=device)
             cache[key] = buf
         return buf
 
-    def _scratch(self, device: torch.device, nbytes: int, stream) -> torch.Tensor:
-        """Uninitialised scratch (the dequantized weight of the prefill path, the row sums of the 128x128 kernel): one growing
-        buffer per (device, stream, capture) instead of an allocation per call; calls on one stream use it in stream order."""
-        cache = self.__dict__.setdefault("_scratch_ws", {})
-        capture = self._c.quanto_hip_stream_capture_id(ctypes.c_void_p(stream))
-        if capture < 0:
-            self._check(int(capture), "stream_capture_id")
-        key = (device, stream, capture)
-        buf = cache.get(key)
-        if buf is None or buf.numel() < nbytes:
-            if len(cache) > 64:
-                for k in [k for k in cache if k[2] != 0 and k != key]:
-                    del cache[k]
-            buf = cache[key] = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-        return buf
+    def _zeroed_workspace(self, device: torch.device, nbytes: int, stream: int) -> torch.Tensor:
+        """Split-K workspace: [QUANTO_HIP_WS_COUNTER_BYTES of arrival counters | fp32 partial sums] (include/quanto_hip.h), its counter region
+        zero-filled once when (re)allocated and only ever handed to kernels that restore the counter words they use.  A pool of its own: the
+        kernels that take scratch write from offset 0, over what would be the counter region."""
+        return self._stream_buffer("_zero_ws", device, nbytes, stream, True)
+
+    def _scratch(self, device: torch.device, nbytes: int, stream: int) -> torch.Tensor:
+        """Uninitialised scratch (the dequantized weight of the prefill path, the row sums of the 128x128 kernel, the convolutions' K split)."""
+        return self._stream_buffer("_scratch_ws", device, nbytes, stream, False)
+
+    def _plan(self, which: str, key, call):
+        """(kernel, workspace bytes) of a call shape, asked from the library once per (shape, format, dtype, forced kernel) and kept: the
+        choice is a pure function of those (csrc/c_api.hip: plan_q*; with QUANTO_HIP_EXPERIMENT the knobs may change between calls, so
+        nothing is kept then).  ``call()`` asks: (status, kernel, workspace bytes); a failed status raises and is not kept."""
+        cache = self.__dict__.setdefault("_plans", {})
+        hit = cache.get((which, key))
+        if hit is not None:
+            return hit
+        st, kernel, ws = call()
+        if st != 0:
+            self._check(st, which + "_plan")
+        plan = (kernel, ws)
+        if not _EXPERIMENT:
+            if len(cache) > 4096:
+                cache.clear()
+            cache[(which, key)] = plan
+        return plan
+
+    @staticmethod
+    def _ask(entry, *args):
+        """(status, kernel, workspace bytes) from one of the C ``*_plan`` entries."""
+        k_out, ws_out = ctypes.c_int(0), ctypes.c_int64(0)
+        st = entry(*args, ctypes.byref(k_out), ctypes.byref(ws_out))
+        return st, k_out.value, ws_out.value
 
     def last_kernel(self) -> str:
         return self._c.quanto_hip_last_kernel().decode()
@@ -245,9 +241,8 @@ class _Bindings:
             mode, inner = 1, (base.numel() // base.shape[0] if base.numel() else 1)
         else:
             mode, inner = 2, base.shape[-1]
-        with torch.cuda.device(base.device):
-            st = self._c.quanto_hip_quantize_symmetric(_ptr(base), _ptr(scale), _ptr(out), base.numel(), inner, mode, _dt(base),
-                                                       _dt(out), self._stream(base))
+        with _DeviceGuard(base.device) as stream:
+            st = self._c.quanto_hip_quantize_symmetric(_ptr(base), _ptr(scale), _ptr(out), base.numel(), inner, mode, _dt(base), _dt(out), stream)
         self._check(st, "quantize_symmetric")
         return out
 
@@ -262,8 +257,8 @@ class _Bindings:
             return out
         if (data.data_ptr() | out.data_ptr()) % 16:
             return None
-        with torch.cuda.device(data.device):
-            st = self._c.quanto_hip_dequantize_symmetric(_ptr(data), _ptr(scale), _ptr(out), data.numel(), _dt(data), _dt(out), self._stream(data))
+        with _DeviceGuard(data.device) as stream:
+            st = self._c.quanto_hip_dequantize_symmetric(_ptr(data), _ptr(scale), _ptr(out), data.numel(), _dt(data), _dt(out), stream)
         self._check(st, "dequantize_symmetric")
         return out
 
@@ -276,9 +271,9 @@ class _Bindings:
         shift = shift.contiguous() if not shift.dtype.is_floating_point else shift.to(base.dtype).contiguous()
         C = group_size or K
         out = torch.empty((N * K // C, C), dtype=torch.uint8, device=base.device)
-        with torch.cuda.device(base.device):
+        with _DeviceGuard(base.device) as stream:
             st = self._c.quanto_hip_quantize_affine(_ptr(base), _ptr(scale), _ptr(shift), _ptr(out), N, K, bits, group_size or 0,
-                                                    _dt(base), _dt(shift), self._stream(base))
+                                                    _dt(base), _dt(shift), stream)
         self._check(st, "quantize_affine")
         return out
 
@@ -294,9 +289,9 @@ class _Bindings:
         rows = N * K // C
         vpi = 8 // bits
         out = torch.empty(((rows + vpi - 1) // vpi, C), dtype=torch.uint8, device=base.device)
-        with torch.cuda.device(base.device):
+        with _DeviceGuard(base.device) as stream:
             st = self._c.quanto_hip_quantize_affine_packed(_ptr(base), _ptr(scale), _ptr(shift), _ptr(out), N, K, bits,
-                                                           group_size or 0, _dt(base), _dt(shift), self._stream(base))
+                                                           group_size or 0, _dt(base), _dt(shift), stream)
         self._check(st, "quantize_affine_packed")
         return out
 
@@ -309,8 +304,8 @@ class _Bindings:
         cols = t.numel() // rows if rows else 0
         row_dim = (rows + 8 // bits - 1) // (8 // bits)
         out = torch.empty((row_dim,) + tuple(t.shape[1:]), dtype=torch.uint8, device=t.device)
-        with torch.cuda.device(t.device):
-            self._check(self._c.quanto_hip_pack(_ptr(t), _ptr(out), rows, cols, bits, self._stream(t)), "pack")
+        with _DeviceGuard(t.device) as stream:
+            self._check(self._c.quanto_hip_pack(_ptr(t), _ptr(out), rows, cols, bits, stream), "pack")
         return out
 
     # -- quanto::qbytes_conv2d (implicit GEMM) -----------------------------------------------------------
@@ -318,7 +313,7 @@ class _Bindings:
     def conv2d_out_size(size, k, stride, pad, dil):
         return (size + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
-    def _conv2d_scratch(self, x, B, OH, OW, OC, K, geom=None):
+    def _conv2d_scratch(self, x, B, OH, OW, OC, K, stream, geom=None):
         """(buffer, bytes) for the convolution kernels' K split - plain scratch, nothing to zero; (None, 0) when the problem needs none.  ``geom`` =
         (cin, W, KH, KW, stride_w, dil_w) of a sub-byte weight: plus the dense weight of the row form, when THIS geometry can take it."""
         if geom is None:
@@ -328,7 +323,21 @@ class _Bindings:
             nbytes = int(self._c.quanto_hip_qbits_conv2d_workspace_size_geom(B, cin, W, OC, KH, KW, max(OH, 0), max(OW, 0), sw, dw))
         if nbytes <= 0:
             return None, 0
-        return self._scratch(x.device, nbytes, self._stream(x).value), nbytes
+        return self._scratch(x.device, nbytes, stream), nbytes
+
+    def _conv2d_output(self, x, OC, KH, KW, stride, padding, dilation, bias, scales=None):
+        """What the three convolutions share: output sizes, the per-channel scales (one per OC, in x's dtype; None when not given), the bias in
+        x's dtype and the output tensor."""
+        B, _, H, W = x.shape
+        OH = self.conv2d_out_size(H, KH, stride[0], padding[0], dilation[0])
+        OW = self.conv2d_out_size(W, KW, stride[1], padding[1], dilation[1])
+        if scales is not None:
+            scales = scales.reshape(-1).to(x.dtype).contiguous()
+            if scales.numel() == 1:
+                scales = scales.expand(OC).contiguous()
+        if bias is not None:
+            bias = bias.to(x.dtype).contiguous()
+        return OH, OW, scales, bias, torch.empty((B, OC, max(OH, 0), max(OW, 0)), dtype=x.dtype, device=x.device)
 
     @classmethod
     def conv2d_geometry_ok(cls, x_shape, w_shape, stride, padding, dilation) -> bool:
@@ -344,17 +353,20 @@ class _Bindings:
         return (B >= 1 and OH >= 1 and OW >= 1 and K >= 1 and K < (1 << 24) and KH * KW <= 127 and B * C * H * W < (1 << 30) and B * OC * OH * OW < (1 << 31)
                 and OC * K < (1 << 31) and (B * OH * OW + 127) // 128 <= 65535)
 
+    @staticmethod
+    def _qbytes_conv2d_dtypes_ok(x, w) -> bool:
+        """NCHW 16-bit activations and an 8-bit OCP weight."""
+        return (x.is_cuda and x.dim() == 4 and w.dim() == 4 and x.dtype in (torch.float16, torch.bfloat16) and
+                w.dtype in (torch.int8, torch.float8_e4m3fn, torch.float8_e5m2))
+
     def qbytes_conv2d_supported(self, x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1)) -> bool:
         """What the kernel takes: NCHW 16-bit activations, an 8-bit OCP weight, and a geometry within ``conv2d_geometry_ok`` (windows of up
         to 127 taps, 31-bit offsets; any C * KH * KW: the last K-tile may be ragged, any weight alignment)."""
-        return (x.is_cuda and x.dim() == 4 and w.dim() == 4 and x.dtype in (torch.float16, torch.bfloat16) and
-                w.dtype in (torch.int8, torch.float8_e4m3fn, torch.float8_e5m2) and
-                self.conv2d_geometry_ok(tuple(x.shape), tuple(w.shape), stride, padding, dilation))
+        return self._qbytes_conv2d_dtypes_ok(x, w) and self.conv2d_geometry_ok(tuple(x.shape), tuple(w.shape), stride, padding, dilation)
 
     def qbytes_conv2d_depthwise_supported(self, x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1)) -> bool:
         """Depthwise layers (r6): weight [OC, 1, KH, KW] on an input of C > 1 channels with OC a multiple of C; NCHW 16-bit activations, 8-bit OCP weight."""
-        if not (x.is_cuda and x.dim() == 4 and w.dim() == 4 and x.dtype in (torch.float16, torch.bfloat16) and
-                w.dtype in (torch.int8, torch.float8_e4m3fn, torch.float8_e5m2)):
+        if not self._qbytes_conv2d_dtypes_ok(x, w):
             return False
         B, C, H, W = x.shape
         OC, wc, KH, KW = w.shape
@@ -368,44 +380,20 @@ class _Bindings:
         """Dense convolution with an 8-bit weight [OC, C, KH, KW] and per-channel scales: im2col happens inside the kernel's staging loads.  A weight
         [OC, 1, KH, KW] on an input of C > 1 channels is the depthwise layer (groups = C): the stencil kernel of csrc/qconv_depthwise.hip."""
         self._require_cuda(x, w, scales, bias)
+        x, w = x.contiguous(), w.contiguous()
         B, C, H, W = x.shape
         OC, wc, KH, KW = w.shape
-        if wc == 1 and C > 1:
-            return self._qbytes_conv2d_depthwise(x, w, scales, bias, stride, padding, dilation)
-        OH = self.conv2d_out_size(H, KH, stride[0], padding[0], dilation[0])
-        OW = self.conv2d_out_size(W, KW, stride[1], padding[1], dilation[1])
-        x, w = x.contiguous(), w.contiguous()
-        s = scales.reshape(-1).to(x.dtype).contiguous()
-        if s.numel() == 1:
-            s = s.expand(OC).contiguous()
-        if bias is not None:
-            bias = bias.to(x.dtype).contiguous()
-        y = torch.empty((B, OC, max(OH, 0), max(OW, 0)), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            ws, ws_bytes = self._conv2d_scratch(x, B, OH, OW, OC, C * KH * KW)
-            st = self._c.quanto_hip_qbytes_conv2d(_ptr(x), _ptr(w), _ptr(s), _ptr(bias), _ptr(y), B, C, H, W, OC, KH, KW, OH, OW, stride[0], stride[1],
-                                                  padding[0], padding[1], dilation[0], dilation[1], _dt(x), _dt(w), _dt(y), _ptr(ws), ws_bytes,
-                                                  self._stream(x))
-        self._check(st, "qbytes_conv2d")
-        return y
-
-    def _qbytes_conv2d_depthwise(self, x, w, scales, bias, stride, padding, dilation):
-        B, C, H, W = x.shape
-        OC, _, KH, KW = w.shape
-        OH = self.conv2d_out_size(H, KH, stride[0], padding[0], dilation[0])
-        OW = self.conv2d_out_size(W, KW, stride[1], padding[1], dilation[1])
-        x, w = x.contiguous(), w.contiguous()
-        s = scales.reshape(-1).to(x.dtype).contiguous()
-        if s.numel() == 1:
-            s = s.expand(OC).contiguous()
-        if bias is not None:
-            bias = bias.to(x.dtype).contiguous()
-        y = torch.empty((B, OC, max(OH, 0), max(OW, 0)), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            st = self._c.quanto_hip_qbytes_conv2d_depthwise(_ptr(x), _ptr(w), _ptr(s), _ptr(bias), _ptr(y), B, C, H, W, OC, KH, KW, OH, OW, stride[0],
-                                                            stride[1], padding[0], padding[1], dilation[0], dilation[1], _dt(x), _dt(w), _dt(y),
-                                                            self._stream(x))
-        self._check(st, "qbytes_conv2d_depthwise")
+        depthwise = wc == 1 and C > 1
+        OH, OW, s, bias, y = self._conv2d_output(x, OC, KH, KW, stride, padding, dilation, bias, scales)
+        args = (_ptr(x), _ptr(w), _ptr(s), _ptr(bias), _ptr(y), B, C, H, W, OC, KH, KW, OH, OW, stride[0], stride[1], padding[0], padding[1],
+                dilation[0], dilation[1], _dt(x), _dt(w), _dt(y))
+        with _DeviceGuard(x.device) as stream:
+            if depthwise:
+                st = self._c.quanto_hip_qbytes_conv2d_depthwise(*args, stream)
+            else:
+                ws, ws_bytes = self._conv2d_scratch(x, B, OH, OW, OC, C * KH * KW, stream)
+                st = self._c.quanto_hip_qbytes_conv2d(*args, _ptr(ws), ws_bytes, stream)
+        self._check(st, "qbytes_conv2d_depthwise" if depthwise else "qbytes_conv2d")
         return y
 
     # -- quanto::qbits_conv2d (implicit GEMM, int4 dequantized while staged) -----------------------------------
@@ -425,19 +413,15 @@ class _Bindings:
         self._require_cuda(x, packed, scale, shift, bias)
         if x.dtype != scale.dtype:
             x = x.to(scale.dtype)
+        x, packed, scale, shift = x.contiguous(), packed.contiguous(), scale.contiguous(), shift.contiguous()
         B, C, H, W = x.shape
         OC, _, KH, KW = weight_size
-        OH = self.conv2d_out_size(H, KH, stride[0], padding[0], dilation[0])
-        OW = self.conv2d_out_size(W, KW, stride[1], padding[1], dilation[1])
-        x, packed, scale, shift = x.contiguous(), packed.contiguous(), scale.contiguous(), shift.contiguous()
-        if bias is not None:
-            bias = bias.to(x.dtype).contiguous()
-        y = torch.empty((B, OC, max(OH, 0), max(OW, 0)), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            ws, ws_bytes = self._conv2d_scratch(x, B, OH, OW, OC, C * KH * KW, geom=(C, W, KH, KW, stride[1], dilation[1]))
+        OH, OW, _, bias, y = self._conv2d_output(x, OC, KH, KW, stride, padding, dilation, bias)
+        with _DeviceGuard(x.device) as stream:
+            ws, ws_bytes = self._conv2d_scratch(x, B, OH, OW, OC, C * KH * KW, stream, geom=(C, W, KH, KW, stride[1], dilation[1]))
             st = self._c.quanto_hip_qbits_conv2d(_ptr(x), _ptr(packed), _ptr(scale), _ptr(shift), _ptr(bias), _ptr(y), B, C, H, W, OC, KH, KW, OH, OW,
                                                  stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], bits, group_size or 0, _dt(x),
-                                                 _dt(shift), _ptr(ws), ws_bytes, self._stream(x))
+                                                 _dt(shift), _ptr(ws), ws_bytes, stream)
         self._check(st, "qbits_conv2d")
         return y
 
@@ -452,8 +436,8 @@ class _Bindings:
         vpi = 8 // bits
         out_shape = (t.shape[0] * vpi,) + tuple(t.shape[1:]) if t.ndim > 0 else (vpi,)
         out = torch.empty(out_shape, dtype=torch.uint8, device=t.device)
-        with torch.cuda.device(t.device):
-            self._check(self._c.quanto_hip_unpack(_ptr(t), _ptr(out), t.numel(), bits, self._stream(t)), "unpack")
+        with _DeviceGuard(t.device) as stream:
+            self._check(self._c.quanto_hip_unpack(_ptr(t), _ptr(out), t.numel(), bits, stream), "unpack")
         return out
 
     # -- fused unpack + dequantize ------------------------------------------------------------------
@@ -461,33 +445,13 @@ class _Bindings:
         self._require_cuda(packed, scale, shift)
         packed, scale, shift = packed.contiguous(), scale.contiguous(), shift.contiguous()
         out = torch.empty((out_features, in_features), dtype=scale.dtype, device=packed.device)
-        with torch.cuda.device(packed.device):
-            st = self._c.quanto_hip_dequantize_qbits(
-                _ptr(packed), _ptr(scale), _ptr(shift), _ptr(out), out_features, in_features, bits, group_size or 0,
-                _dt(scale), _dt(shift), self._stream(packed))
+        with _DeviceGuard(packed.device) as stream:
+            st = self._c.quanto_hip_dequantize_qbits(_ptr(packed), _ptr(scale), _ptr(shift), _ptr(out), out_features, in_features, bits,
+                                                     group_size or 0, _dt(scale), _dt(shift), stream)
         self._check(st, "dequantize_qbits")
         return out
 
     # -- quanto::qbits_mm ---------------------------------------------------------------------------
-    def _plan(self, which: str, key, call):
-        """(kernel, workspace bytes) of a call shape, asked from the library once per (shape, format, dtype, forced kernel) and kept: the
-        choice is a pure function of those (csrc/c_api.hip: pick_q*_kernel; with QUANTO_HIP_EXPERIMENT the knobs may change between calls, so
-        nothing is kept then)."""
-        cache = self.__dict__.setdefault("_plans", {})
-        hit = cache.get((which, key))
-        if hit is not None:
-            return hit
-        k_out, ws_out = ctypes.c_int(0), ctypes.c_int64(0)
-        st = call(ctypes.byref(k_out), ctypes.byref(ws_out))
-        if st != 0:
-            self._check(st, which + "_plan")
-        plan = (k_out.value, ws_out.value)
-        if not _EXPERIMENT:
-            if len(cache) > 4096:
-                cache.clear()
-            cache[(which, key)] = plan
-        return plan
-
     def qbits_mm(self, x, packed, scale, shift, bias, bits: int, group_size, out_features: int, in_features: int,
                  kernel: str = "auto"):
         if not (x.is_cuda and packed.is_cuda and scale.is_cuda and shift.is_cuda and (bias is None or bias.is_cuda)):
@@ -514,13 +478,11 @@ class _Bindings:
         y = torch.empty((M, out_features), dtype=sdt, device=x.device)
         c = self._c
         k, ws_bytes = self._plan("qbits_mm", (M, out_features, in_features, bits, gs, dt, kernel),
-                                 lambda ko, wo: c.quanto_hip_qbits_mm_plan(M, out_features, in_features, bits, gs, dt, KERNELS[kernel], ko, wo))
+                                 lambda: self._ask(c.quanto_hip_qbits_mm_plan, M, out_features, in_features, bits, gs, dt, KERNELS[kernel]))
         xp, pp = x2.data_ptr(), packed.data_ptr()
         if kernel == "auto" and (xp | pp) % 16:
             k, ws_bytes = KERNEL_NAIVE, 0  # misaligned view: the kernel without an alignment requirement (what AUTO does in C)
-        index = x.device.index
-        with _DeviceGuard(x.device):
-            stream = _raw_stream(index if index is not None else _current_device())
+        with _DeviceGuard(x.device) as stream:
             if ws_bytes == 0:
                 wp = 0
             elif k in (KERNEL_SKINNY, KERNEL_MFMA_FUSED4):
@@ -542,12 +504,10 @@ class _Bindings:
         adt, dt = _DTYPES.get(a_dtype), _DTYPES.get(dtype)
         if adt is None or dt is None:
             return -2
-        return self._plan("qbits_mm_a8", (M, out_features, in_features, bits, group_size or 0, adt, dt),
-                          lambda ko, wo: self._a8_plan(M, out_features, in_features, bits, group_size or 0, adt, dt, ko, wo))[1]
-
-    def _a8_plan(self, M, N, K, bits, gs, adt, dt, kernel_out, ws_out):
-        ws_out._obj.value = int(self._c.quanto_hip_qbits_mm_a8_workspace_size(M, N, K, bits, gs, adt, dt))
-        return 0
+        gs = group_size or 0
+        # one kernel: the size entry alone is the plan (its negative statuses are kept as the answer, not raised)
+        return self._plan("qbits_mm_a8", (M, out_features, in_features, bits, gs, adt, dt),
+                          lambda: (0, 0, int(self._c.quanto_hip_qbits_mm_a8_workspace_size(M, out_features, in_features, bits, gs, adt, dt))))[1]
 
     def qbits_mm_a8(self, a, a_scale, packed, scale, shift, bias, bits: int, group_size, out_features: int, in_features: int):
         """F.linear(quantized activation, int4 / int2 weight) on the 8-bit matrix instructions: ``a`` int8 / float8_e4m3fn / float8_e5m2 [..., K], ``a_scale`` its
@@ -569,9 +529,7 @@ class _Bindings:
         if ws_bytes < 0:
             self._check(int(ws_bytes), "qbits_mm_a8")
         y = torch.empty((M, out_features), dtype=sdt, device=a.device)
-        index = a.device.index
-        with _DeviceGuard(a.device):
-            stream = _raw_stream(index if index is not None else _current_device())
+        with _DeviceGuard(a.device) as stream:
             wp = self._zeroed_workspace(a.device, ws_bytes, stream).data_ptr() if ws_bytes > 0 else 0
             st = self._c.quanto_hip_qbits_mm_a8(a2.data_ptr(), a_scale.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                                                 0 if bias is None else bias.data_ptr(), y.data_ptr(), M, out_features, in_features, bits,
@@ -600,28 +558,36 @@ class _Bindings:
         x2 = x.reshape(-1, in_features).contiguous()
         M = x2.shape[0]
         kernel, ws_bytes = KERNEL_AUTO, 0
-        nfs = (ctypes.c_int64 * n)(*out_features)
         if 1 <= M <= 64 and n <= self.MAX_MULTI and all(s.dtype == sdt for s in scale) and len({sh.dtype for sh in shift}) == 1:
-            k_out, ws_out = ctypes.c_int(0), ctypes.c_int64(0)
-            with torch.cuda.device(x.device):
-                st = self._c.quanto_hip_qbits_mm_multi_plan(n, nfs, M, in_features, bits, group_size or 0, _dt(scale[0]), ctypes.byref(k_out),
-                                                            ctypes.byref(ws_out))
-            if st == 0:
-                kernel, ws_bytes = k_out.value, ws_out.value
+            kernel, ws_bytes = self._multi_plan("qbits_mm_multi", self._c.quanto_hip_qbits_mm_multi_plan, out_features, M, in_features, bits,
+                                                group_size or 0, _dt(scale[0]))
         if kernel == KERNEL_AUTO:
             return [self.qbits_mm(x, packed[i], scale[i], shift[i], bias[i], bits, group_size, out_features[i], in_features)
                     for i in range(n)]
-        packed = [t.contiguous() for t in packed]
-        scale = [t.contiguous() for t in scale]
-        shift = [t.contiguous() for t in shift]
-        bias = [None if b is None else b.to(sdt).contiguous() for b in bias]
-        ys = [torch.empty((M, nf), dtype=sdt, device=x.device) for nf in out_features]
-        arr = lambda ts: (ctypes.c_void_p * n)(*[0 if t is None else t.data_ptr() for t in ts])  # noqa: E731
-        with torch.cuda.device(x.device):
-            ws = self._zeroed_workspace(x.device, ws_bytes, self._stream(x).value) if ws_bytes else None  # split-K arrival counters
-            st = self._c.quanto_hip_qbits_mm_multi_ws(_ptr(x2), n, arr(packed), arr(scale), arr(shift), arr(bias), arr(ys), nfs, M, in_features,
-                                                      bits, group_size or 0, _dt(scale[0]), _dt(shift[0]), _ptr(ws), ws_bytes, self._stream(x))
-        self._check(st, "qbits_mm_multi")
+        lists = ([t.contiguous() for t in packed], [t.contiguous() for t in scale], [t.contiguous() for t in shift],
+                 [None if b is None else b.to(sdt).contiguous() for b in bias])
+        return self._multi_launch("qbits_mm_multi", self._c.quanto_hip_qbits_mm_multi_ws, x2, lead, lists, out_features,
+                                  (bits, group_size or 0, _dt(scale[0]), _dt(shift[0])), ws_bytes)
+
+    def _multi_plan(self, which: str, entry, out_features, M: int, K: int, *args):
+        """(kernel, workspace bytes) of the one launch that serves a group of products, from ``entry`` (a C ``*_multi_plan``); KERNEL_AUTO
+        when none does (separate calls, each with its own plan), failed statuses included."""
+        def ask():
+            st, kernel, ws = self._ask(entry, len(out_features), (ctypes.c_int64 * len(out_features))(*out_features), M, K, *args)
+            return (0, kernel, ws) if st == 0 else (0, KERNEL_AUTO, 0)
+
+        return self._plan(which, (tuple(out_features), M, K) + args, ask)
+
+    def _multi_launch(self, which: str, entry, x2, lead, lists, out_features, args, ws_bytes: int):
+        """One launch of a C ``*_multi_ws`` entry over the members: x2 [M, K], one pointer array per tensor list (``lists``, then the outputs),
+        ``args`` between K and the workspace; the outputs in x2's dtype, shaped as ``lead + (out_features[i],)``."""
+        n, (M, K) = len(out_features), x2.shape
+        ys = [torch.empty((M, nf), dtype=x2.dtype, device=x2.device) for nf in out_features]
+        arrays = [(ctypes.c_void_p * n)(*[_ptr(t) for t in ts]) for ts in (*lists, ys)]
+        with _DeviceGuard(x2.device) as stream:
+            ws = self._zeroed_workspace(x2.device, ws_bytes, stream) if ws_bytes else None  # split-K arrival counters
+            st = entry(_ptr(x2), n, *arrays, (ctypes.c_int64 * n)(*out_features), M, K, *args, _ptr(ws), ws_bytes, stream)
+        self._check(st, which)
         return [y.reshape(*lead, nf) for y, nf in zip(ys, out_features)]
 
     # -- quanto::qbytes_mm_multi --------------------------------------------------------------------
@@ -639,33 +605,22 @@ class _Bindings:
                     and all(w.dtype == weights[0].dtype for w in weights) and all(s.dtype == sdt for s in scales)
                     and all(s.numel() == w.shape[0] for s, w in zip(scales, weights)))
         kernel, ws_bytes = KERNEL_AUTO, 0
+        out_features = [w.shape[0] for w in weights]
         if one_call:
             if a.dtype != sdt:
                 a = a.to(sdt)
             lead = a.shape[:-1]
             a2 = a.reshape(-1, K).contiguous()
             M = a2.shape[0]
-            nfs = (ctypes.c_int64 * n)(*[w.shape[0] for w in weights])
             if 1 <= M <= 64:
-                k_out, ws_out = ctypes.c_int(0), ctypes.c_int64(0)
-                with torch.cuda.device(a.device):
-                    st = self._c.quanto_hip_qbytes_mm_multi_plan(n, nfs, M, K, _dt(a2), _dt(weights[0]), _dt(scales[0]), ctypes.byref(k_out),
-                                                                 ctypes.byref(ws_out))
-                if st == 0:
-                    kernel, ws_bytes = k_out.value, ws_out.value
+                kernel, ws_bytes = self._multi_plan("qbytes_mm_multi", self._c.quanto_hip_qbytes_mm_multi_plan, out_features, M, K, _dt(a2),
+                                                    _dt(weights[0]), _dt(scales[0]))
         if kernel == KERNEL_AUTO:
             return [self.qbytes_mm(a, weights[i], scales[i], bias[i]) for i in range(n)]
-        weights = [w.contiguous() for w in weights]
-        scales = [s.reshape(-1).contiguous() for s in scales]
-        bias = [None if b is None else b.to(sdt).contiguous() for b in bias]
-        ys = [torch.empty((M, w.shape[0]), dtype=sdt, device=a.device) for w in weights]
-        arr = lambda ts: (ctypes.c_void_p * n)(*[0 if t is None else t.data_ptr() for t in ts])  # noqa: E731
-        with torch.cuda.device(a.device):
-            ws = self._zeroed_workspace(a.device, ws_bytes, self._stream(a).value) if ws_bytes else None  # split-K arrival counters
-            st = self._c.quanto_hip_qbytes_mm_multi_ws(_ptr(a2), n, arr(weights), arr(scales), arr(bias), arr(ys), nfs, M, K, _dt(a2),
-                                                       _dt(weights[0]), _dt(scales[0]), _ptr(ws), ws_bytes, self._stream(a))
-        self._check(st, "qbytes_mm_multi")
-        return [y.reshape(*lead, w.shape[0]) for y, w in zip(ys, weights)]
+        lists = ([w.contiguous() for w in weights], [s.reshape(-1).contiguous() for s in scales],
+                 [None if b is None else b.to(sdt).contiguous() for b in bias])
+        return self._multi_launch("qbytes_mm_multi", self._c.quanto_hip_qbytes_mm_multi_ws, a2, lead, lists, out_features,
+                                  (_dt(a2), _dt(weights[0]), _dt(scales[0])), ws_bytes)
 
     # -- quanto::qbytes_mm --------------------------------------------------------------------------
     def qbytes_mm(self, a, b, scales, bias=None, kernel: str = "auto"):
@@ -692,13 +647,11 @@ class _Bindings:
         y = torch.empty((M, N), dtype=sdt, device=a.device)
         c = self._c
         k, ws_bytes = self._plan("qbytes_mm", (M, N, K, adt, bdt, odt, kernel),
-                                 lambda ko, wo: c.quanto_hip_qbytes_mm_plan(M, N, K, adt, bdt, odt, KERNELS[kernel], ko, wo))
+                                 lambda: self._ask(c.quanto_hip_qbytes_mm_plan, M, N, K, adt, bdt, odt, KERNELS[kernel]))
         ap, bp = a2.data_ptr(), b.data_ptr()
         if kernel == "auto" and (ap | bp) % 16:
             k, ws_bytes = KERNEL_NAIVE, 0  # misaligned view: the kernel without an alignment requirement (what AUTO does in C)
-        index = a.device.index
-        with _DeviceGuard(a.device):
-            stream = _raw_stream(index if index is not None else _current_device())
+        with _DeviceGuard(a.device) as stream:
             wp = self._zeroed_workspace(a.device, ws_bytes, stream).data_ptr() if ws_bytes > 0 else 0  # split-K arrival counters: zero on entry, left zero
             st = c.quanto_hip_qbytes_mm_ws(ap, bp, s.data_ptr(), 0 if bias is None else bias.data_ptr(), y.data_ptr(), M, N, K, adt, bdt, odt, k, wp,
                                            max(ws_bytes, 0), stream)

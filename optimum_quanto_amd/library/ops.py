@@ -30,6 +30,7 @@ import torch
 
 from ..tensor.dtypes import dtype_info
 from ..tensor.grouping import group, ungroup
+from . import hip
 from .hip import quanto_hip
 
 __all__ = []
@@ -45,26 +46,27 @@ def _op_exists(name: str) -> bool:
         return False
 
 
-def _define(name: str, schema: str) -> bool:
-    """Define ``quanto::name`` unless another definer (the reference package) already did. Returns True if we own it."""
-    if _op_exists(name):
-        return False
-    _lib_def.define(name + schema)
-    return True
+# the reference's own ops: when it defined them already, their CUDA implementation is replaced by ours (plug-in mode)
+_REFERENCE_OPS = ("unpack", "qbytes_mm", "quantize_symmetric", "quantize_affine")
 
 
-def _impl(name: str, key: str, fn, owned: bool):
-    if owned:
-        _lib_impl.impl(name, fn, key)
-    else:  # plug-in mode: replace the reference's registration for this key (intended: silence torch's override notice)
+def _register(name: str, schema: str, cuda, default=None, cpu=None):
+    """Define ``quanto::name`` with its ``default`` (CompositeExplicitAutograd), ``cpu`` and ``cuda`` implementations, unless another definer
+    (the reference package) already did: then only a reference op gets ``cuda`` registered, over the reference's own."""
+    if not _op_exists(name):
+        _lib_def.define(name + schema)
+        for key, fn in (("CompositeExplicitAutograd", default), ("CPU", cpu), ("CUDA", cuda)):
+            if fn is not None:
+                _lib_impl.impl(name, fn, key)
+    elif name in _REFERENCE_OPS:
         import warnings
 
-        with warnings.catch_warnings():
+        with warnings.catch_warnings():  # intended: silence torch's override notice
             warnings.simplefilter("ignore")
             try:
-                _lib_impl.impl(name, fn, key, allow_override=True)
+                _lib_impl.impl(name, cuda, "CUDA", allow_override=True)
             except TypeError:  # older torch without allow_override
-                _lib_impl.impl(name, fn, key)
+                _lib_impl.impl(name, cuda, "CUDA")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -80,10 +82,7 @@ def unpack_hip(packed: torch.Tensor, bits: int) -> torch.Tensor:
     return quanto_hip.lib.unpack(packed, bits)
 
 
-_owned = _define("unpack", "(Tensor self, int bits) -> Tensor")
-if _owned:
-    _impl("unpack", "CompositeExplicitAutograd", unpack_default, True)
-_impl("unpack", "CUDA", unpack_hip, _owned)
+_register("unpack", "(Tensor self, int bits) -> Tensor", unpack_hip, default=unpack_default)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -142,16 +141,10 @@ def qbytes_mm_bias_hip(activations, weights, output_scales, bias):
     return qbytes_mm_hip(activations, weights, output_scales, bias)
 
 
-_owned = _define("qbytes_mm", "(Tensor A, Tensor B, Tensor scales) -> Tensor")
-if _owned:
-    _impl("qbytes_mm", "CompositeExplicitAutograd", qbytes_mm_default, True)
-    _impl("qbytes_mm", "CPU", qbytes_mm_cpu, True)
-_impl("qbytes_mm", "CUDA", qbytes_mm_hip, _owned)
+_register("qbytes_mm", "(Tensor A, Tensor B, Tensor scales) -> Tensor", qbytes_mm_hip, default=qbytes_mm_default, cpu=qbytes_mm_cpu)
 # new op: the same product with the bias of the Linear fused into the kernel epilogue (rounded product + bias, rounded again:
 # bit-identical to the two-op sequence) - saves one elementwise kernel per biased Linear
-if _define("qbytes_mm_bias", "(Tensor A, Tensor B, Tensor scales, Tensor? bias) -> Tensor"):
-    _impl("qbytes_mm_bias", "CompositeExplicitAutograd", qbytes_mm_bias_default, True)
-    _impl("qbytes_mm_bias", "CUDA", qbytes_mm_bias_hip, True)
+_register("qbytes_mm_bias", "(Tensor A, Tensor B, Tensor scales, Tensor? bias) -> Tensor", qbytes_mm_bias_hip, default=qbytes_mm_bias_default)
 
 
 def qbytes_conv2d_default(input, weight, scales, bias, stride, padding, dilation):
@@ -166,9 +159,8 @@ def qbytes_conv2d_hip(input, weight, scales, bias, stride, padding, dilation):
 
 
 # new op: dense convolution with an int8 / fp8 weight as an implicit GEMM on the device (csrc/qconv_mfma.hip): no im2col tensor
-if _define("qbytes_conv2d", "(Tensor input, Tensor weight, Tensor scales, Tensor? bias, int[] stride, int[] padding, int[] dilation) -> Tensor"):
-    _impl("qbytes_conv2d", "CompositeExplicitAutograd", qbytes_conv2d_default, True)
-    _impl("qbytes_conv2d", "CUDA", qbytes_conv2d_hip, True)
+_register("qbytes_conv2d", "(Tensor input, Tensor weight, Tensor scales, Tensor? bias, int[] stride, int[] padding, int[] dilation) -> Tensor",
+          qbytes_conv2d_hip, default=qbytes_conv2d_default)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -231,11 +223,10 @@ def quantize_affine(base: torch.Tensor, bits: int, axis: int, group_size: Union[
     return torch.clamp(data, min=0, max=2**bits - 1).to(torch.uint8)
 
 
-if _define("quantize_symmetric", "(Tensor base, ScalarType dtype, int? axis, Tensor scale) -> Tensor"):
-    _impl("quantize_symmetric", "CompositeExplicitAutograd", quantize_symmetric, True)
-    _impl("quantize_symmetric", "CUDA", quantize_symmetric_hip, True)
-else:
-    _impl("quantize_symmetric", "CUDA", quantize_symmetric_hip, False)
+_register("quantize_symmetric", "(Tensor base, ScalarType dtype, int? axis, Tensor scale) -> Tensor", quantize_symmetric_hip,
+          default=quantize_symmetric)
+
+
 def quantize_affine_hip(base: torch.Tensor, bits: int, axis: int, group_size: Union[int, None], scale: torch.Tensor,
                         shift: torch.Tensor) -> torch.Tensor:
     """Device tensors: the one-pass kernel (csrc/quantize.hip) for the layout of the hot path - axis-0 2-D weights with
@@ -250,11 +241,8 @@ def quantize_affine_hip(base: torch.Tensor, bits: int, axis: int, group_size: Un
     return quantize_affine(base, bits, axis, group_size, scale, shift)
 
 
-if _define("quantize_affine", "(Tensor base, int bits, int axis, int? group_size, Tensor scale, Tensor shift) -> Tensor"):
-    _impl("quantize_affine", "CompositeExplicitAutograd", quantize_affine, True)
-    _impl("quantize_affine", "CUDA", quantize_affine_hip, True)
-else:
-    _impl("quantize_affine", "CUDA", quantize_affine_hip, False)
+_register("quantize_affine", "(Tensor base, int bits, int axis, int? group_size, Tensor scale, Tensor shift) -> Tensor", quantize_affine_hip,
+          default=quantize_affine)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -287,15 +275,10 @@ def qbits_mm_hip(input, packed, scale, shift, bias, bits: int, group_size: Optio
     return quanto_hip.lib.qbits_mm(input, packed, scale, shift, bias, bits, group_size, out_features, in_features)
 
 
-if _define("dequantize_qbits",
-           "(Tensor packed, Tensor scale, Tensor shift, int bits, int? group_size, int out_features, int in_features) -> Tensor"):
-    _impl("dequantize_qbits", "CompositeExplicitAutograd", dequantize_qbits_default, True)
-    _impl("dequantize_qbits", "CUDA", dequantize_qbits_hip, True)
-if _define("qbits_mm",
-           "(Tensor input, Tensor packed, Tensor scale, Tensor shift, Tensor? bias, int bits, int? group_size, "
-           "int out_features, int in_features) -> Tensor"):
-    _impl("qbits_mm", "CompositeExplicitAutograd", qbits_mm_default, True)
-    _impl("qbits_mm", "CUDA", qbits_mm_hip, True)
+_register("dequantize_qbits", "(Tensor packed, Tensor scale, Tensor shift, int bits, int? group_size, int out_features, int in_features) -> Tensor",
+          dequantize_qbits_hip, default=dequantize_qbits_default)
+_register("qbits_mm", "(Tensor input, Tensor packed, Tensor scale, Tensor shift, Tensor? bias, int bits, int? group_size, "
+          "int out_features, int in_features) -> Tensor", qbits_mm_hip, default=qbits_mm_default)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -311,7 +294,12 @@ def qbits_mm_a8_default(input, input_scale, packed, scale, shift, bias, bits: in
     return torch.ops.quanto.qbits_mm(x, packed, scale, shift, bias, bits, group_size, out_features, in_features)
 
 
-_A8_MAX_TILES = int(os.environ.get("QUANTO_HIP_A8_MAX_TILES", "512")) if os.environ.get("QUANTO_HIP_EXPERIMENT", "0") not in ("", "0") else 512
+def _a8_max_tiles() -> int:
+    """The tile cap below; QUANTO_HIP_A8_MAX_TILES overrides it while experiments are on, read on every call with C's atoi rules like the
+    library's own knobs."""
+    return hip._c_atoi(os.environ.get("QUANTO_HIP_A8_MAX_TILES", "512")) if hip._EXPERIMENT else 512
+
+
 # int2 weights x int8 activations run 15-20 % slower than int4 x int8 on the same tiles (r7 sweep, profiles/r07_w2a8_crossover.jsonl: (512,4096,4096)
 # 35.5 vs 30.5 us) and lose to the dequantize-first sequence at the int4 cap: (512,14336,4096) = 448 tiles 111 vs 122 us, (2048,4096,4096) = 512 tiles
 # 112 vs 108.  int2 x e5m2 and int4 x e5m2 keep the int4 cap (2048,4096,4096: 98 / 89 vs 106).
@@ -322,24 +310,23 @@ def qbits_mm_a8_hip(input, input_scale, packed, scale, shift, bias, bits: int, g
     lib = quanto_hip.lib
     m = input.numel() // in_features if in_features else 0
     # batched-decode sizes keep the weight-streaming kernels (the activation is dequantized: M x K elements, nothing next to the weight stream);
-    # from 64 rows on the stored integers / fp8 values go to the 8-bit matrix instructions
+    # above 64 rows the stored integers / fp8 values go to the 8-bit matrix instructions
     # ... while the output's 128 x 128 tiles are all resident at once (two workgroups per CU): the kernel moves 24 KiB through a CU's vector L1 per tile
     # and group and is bound by that, not by the matrix pipe; beyond one residency round the dequantize-first sequence on the dense bf16 GEMM is faster
     # (r6 sweep, profiles/r06_w4a8_crossover.jsonl: (2048,4096,4096) 93 vs 109 us, (4096,4096,4096) 184 vs 146, (768,14336,4096) 137 vs 114)
     # one 128-token x 128-feature tile per workgroup for int4 (64 packed rows) and int2 (32 packed rows x 4 planes) alike
     tiles = -(-m // 128) * -(-out_features // 128)
-    cap = min(_A8_MAX_TILES, _A8_MAX_TILES_W2_INT8) if (bits == 2 and input.dtype == torch.int8) else _A8_MAX_TILES
+    cap = _a8_max_tiles()
+    if bits == 2 and input.dtype == torch.int8:
+        cap = min(cap, _A8_MAX_TILES_W2_INT8)
     if (64 < m and tiles <= cap and input.dtype in lib.A8_DTYPES and input_scale.numel() == 1
             and lib.qbits_mm_a8_workspace(m, out_features, in_features, bits, group_size, input.dtype, scale.dtype) >= 0):
         return lib.qbits_mm_a8(input, input_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features)
     return qbits_mm_a8_default(input, input_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features)
 
 
-if _define("qbits_mm_a8",
-           "(Tensor input, Tensor input_scale, Tensor packed, Tensor scale, Tensor shift, Tensor? bias, int bits, int? group_size, "
-           "int out_features, int in_features) -> Tensor"):
-    _impl("qbits_mm_a8", "CompositeExplicitAutograd", qbits_mm_a8_default, True)
-    _impl("qbits_mm_a8", "CUDA", qbits_mm_a8_hip, True)
+_register("qbits_mm_a8", "(Tensor input, Tensor input_scale, Tensor packed, Tensor scale, Tensor shift, Tensor? bias, int bits, int? group_size, "
+          "int out_features, int in_features) -> Tensor", qbits_mm_a8_hip, default=qbits_mm_a8_default)
 
 
 def qbits_conv2d_default(input, packed, scale, shift, bias, bits: int, group_size: Optional[int], weight_size, stride, padding, dilation):
@@ -356,11 +343,8 @@ def qbits_conv2d_hip(input, packed, scale, shift, bias, bits: int, group_size: O
 
 # new op: dense convolution with a packed int4 weight as an implicit GEMM on the device (csrc/qconv_mfma.hip, W_I4R staging): no im2col tensor,
 # no dequantized weight in memory
-if _define("qbits_conv2d",
-           "(Tensor input, Tensor packed, Tensor scale, Tensor shift, Tensor? bias, int bits, int? group_size, int[] weight_size, "
-           "int[] stride, int[] padding, int[] dilation) -> Tensor"):
-    _impl("qbits_conv2d", "CompositeExplicitAutograd", qbits_conv2d_default, True)
-    _impl("qbits_conv2d", "CUDA", qbits_conv2d_hip, True)
+_register("qbits_conv2d", "(Tensor input, Tensor packed, Tensor scale, Tensor shift, Tensor? bias, int bits, int? group_size, int[] weight_size, "
+          "int[] stride, int[] padding, int[] dilation) -> Tensor", qbits_conv2d_hip, default=qbits_conv2d_default)
 
 
 # several Linears applied to the same input in one launch (q/k/v, gate/up of a decoder layer at decode time)
@@ -373,11 +357,8 @@ def qbits_mm_multi_hip(input, packed, scale, shift, bias, bits: int, group_size:
     return quanto_hip.lib.qbits_mm_multi(input, packed, scale, shift, bias, bits, group_size, list(out_features), in_features)
 
 
-if _define("qbits_mm_multi",
-           "(Tensor input, Tensor[] packed, Tensor[] scale, Tensor[] shift, Tensor?[] bias, int bits, int? group_size, "
-           "int[] out_features, int in_features) -> Tensor[]"):
-    _impl("qbits_mm_multi", "CompositeExplicitAutograd", qbits_mm_multi_default, True)
-    _impl("qbits_mm_multi", "CUDA", qbits_mm_multi_hip, True)
+_register("qbits_mm_multi", "(Tensor input, Tensor[] packed, Tensor[] scale, Tensor[] shift, Tensor?[] bias, int bits, int? group_size, "
+          "int[] out_features, int in_features) -> Tensor[]", qbits_mm_multi_hip, default=qbits_mm_multi_default)
 
 
 def qbytes_mm_multi_default(activations, weights, output_scales, bias):
@@ -389,6 +370,5 @@ def qbytes_mm_multi_hip(activations, weights, output_scales, bias):
 
 
 # the 8-bit counterpart: several WeightQBytes Linears applied to the same (float) input in one launch
-if _define("qbytes_mm_multi", "(Tensor A, Tensor[] B, Tensor[] scales, Tensor?[] bias) -> Tensor[]"):
-    _impl("qbytes_mm_multi", "CompositeExplicitAutograd", qbytes_mm_multi_default, True)
-    _impl("qbytes_mm_multi", "CUDA", qbytes_mm_multi_hip, True)
+_register("qbytes_mm_multi", "(Tensor A, Tensor[] B, Tensor[] scales, Tensor?[] bias) -> Tensor[]", qbytes_mm_multi_hip,
+          default=qbytes_mm_multi_default)

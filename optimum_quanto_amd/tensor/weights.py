@@ -365,8 +365,8 @@ class WeightQBitsLinearFunction(QuantizedLinearFunction):
         ctx.save_for_backward(input, other)
         n, k = other.shape
         if type(input) is not torch.Tensor:
-            # r6: a per-tensor quantized activation meets the packed weight as stored (quanto::qbits_mm_a8: the 8-bit matrix instructions from 64
-            # rows on, the reference's dequantize-first sequence below that and for the formats the kernel does not take)
+            # r6: a per-tensor quantized activation meets the packed weight as stored (quanto::qbits_mm_a8: the 8-bit matrix instructions above 64
+            # rows, the reference's dequantize-first sequence up to that and for the formats the kernel does not take)
             if isinstance(input, QBytesTensor) and input.axis is None and input._data.is_cuda and input._scale.numel() == 1:
                 return _op("qbits_mm_a8")(input._data, input._scale, other._data._data, other._scale, other._shift, bias, other._data.bits,
                                           other._group_size, n, k)
