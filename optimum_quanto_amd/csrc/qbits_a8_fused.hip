@@ -27,7 +27,7 @@
 // exact in fp32, as for e4m3.  Instantiated: {bf16, fp16} x {int8, e4m3, e5m2} x {float shift, zero-point} x {64, 128 tokens} x {int4, int2}.
 #include <type_traits>
 
-#include "qh_common.h"
+#include "qh_mfma.h"
 
 namespace qh {
 namespace a8 {
@@ -51,16 +51,6 @@ struct Geo {
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-
-__device__ __forceinline__ void glds16(const void* sbase, uint32_t voff, uint32_t lds_dst) {
-  asm volatile(  // M0 is written and not restored (qmm_large_common.h: nothing else in this kernel needs it)
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, %1"
-      :
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
 
 enum { A_I8 = 0, A_F8E4M3 = 1, A_F8E5M2 = 2 };
 

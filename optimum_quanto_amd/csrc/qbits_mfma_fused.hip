@@ -27,7 +27,7 @@
 // them in split order - the protocol of qbits_skinny.hip.
 #include <type_traits>
 
-#include "qh_common.h"
+#include "qh_mfma.h"
 
 namespace qh {
 namespace fused4 {
@@ -50,38 +50,6 @@ struct Geo {
 };
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// LDS-DMA, 16 bytes per lane: wave-uniform 64-bit base in SGPRs + per-lane 32-bit byte offset
-__device__ __forceinline__ void glds16(const void* sbase, uint32_t voff, uint32_t lds_dst) {
-  // M0 is written and not restored (qmm_large_common.h: nothing else in this kernel needs it; 2 SALU instructions per piece)
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, %1"
-      :
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
-
-template <int DT>
-struct Mma;
-template <>
-struct Mma<QUANTO_HIP_BF16> {
-  using V8 = bf16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-  static constexpr uint32_t MAGIC = 0x43004300u;
-  static constexpr float OFFSET = 128.f;
-};
-template <>
-struct Mma<QUANTO_HIP_F16> {
-  using V8 = f16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-  static constexpr uint32_t MAGIC = 0x64006400u;
-  static constexpr float OFFSET = 1024.f;
-};
-
-template <int DT>
-__device__ __forceinline__ uint32_t ONE2() { return DT == QUANTO_HIP_BF16 ? 0x3F803F80u : 0x3C003C00u; }  // (1.0, 1.0)
 
 struct Args {
   const void* x;       // [M, K]
@@ -249,7 +217,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
   uint32_t nibmask = 0x0F0F0F0Fu, kmagic = Mma<DT>::MAGIC;
   asm volatile("" : "+s"(nibmask));
   asm volatile("" : "+v"(kmagic));
-  const V8 ones = __builtin_bit_cast(V8, make_uint4(ONE2<DT>(), ONE2<DT>(), ONE2<DT>(), ONE2<DT>()));
+  const V8 ones = __builtin_bit_cast(V8, make_uint4(Mma<DT>::ONE2, Mma<DT>::ONE2, Mma<DT>::ONE2, Mma<DT>::ONE2));
 
   // Group accumulators are double-buffered: while tile kt accumulates into one set, the fold of tile kt-1 (scale / shift applied to
   // the other set) is sliced over the MFMA steps of tile kt - the two waves of a SIMD, re-synchronised by the barrier of every tile,

@@ -41,9 +41,7 @@ namespace qh {
 namespace l4 {
 
 using lt::BK;  // 64
-using lt::glds16;
 using lt::lds_ptr_t;
-using lt::Mma;
 using lt::swz_a;
 using lt::swz_w;
 
@@ -89,7 +87,7 @@ __device__ __forceinline__ float round_to_T(float v) {
     return (float)(_Float16)v;
 }
 
-// two fp32 -> one dword of T, round to nearest even (lt::Mma<F16>::pack rounds toward zero: exact only for the 8-bit formats it serves)
+// two fp32 -> one dword of T, round to nearest even (qh_mfma.h's pack_exact rounds fp16 toward zero: exact only for the 8-bit codes it serves)
 template <int DT>
 __device__ __forceinline__ uint32_t pack_rne(float a, float b) {
   if constexpr (DT == QUANTO_HIP_BF16) {

@@ -17,43 +17,12 @@
 //   * the four waves' sums are added through LDS in wave order; no workspace, deterministic.
 // Cost: every block reads all of x (M x K x 2 bytes, L2 hits) for 16 FG features - the reason this is for M <= 32 only and
 // why FG grows with N.
-#include "qh_common.h"
+#include "qh_mfma.h"
 
 namespace qh {
 namespace mmv {
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-
-template <int DT>
-struct Mma;
-template <>
-struct Mma<QUANTO_HIP_BF16> {
-  using V8 = bf16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-  static constexpr uint32_t MAGIC = 0x43004300u, ONE2 = 0x3F803F80u;
-  static constexpr float OFFSET = 128.f;
-};
-template <>
-struct Mma<QUANTO_HIP_F16> {
-  using V8 = f16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-  static constexpr uint32_t MAGIC = 0x64006400u, ONE2 = 0x3C003C00u;
-  static constexpr float OFFSET = 1024.f;
-};
-
-// s_waitcnt vmcnt(n * PER), n = 0 .. MAXN / PER (the immediate must be a literal)
-template <int MAXN, int PER>
-__device__ __forceinline__ void wait_vmcnt(int younger_tiles) {
-  if constexpr (MAXN > 0) {
-    if (younger_tiles * PER >= MAXN) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MAXN) : "memory");
-      return;
-    }
-    wait_vmcnt<MAXN - PER, PER>(younger_tiles);
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-}
 
 // Asm loads: the result register is written when the data ARRIVES - every target is "touched" behind the covering
 // s_waitcnt before its first use and no load is issued whose result is not consumed (qbits_mfma_fused.hip, lesson 1).

@@ -20,7 +20,7 @@
 // chunk ^ (row & 15).
 #include <cstdlib>
 
-#include "qh_common.h"
+#include "qh_mfma.h"
 
 namespace qh {
 namespace skinny {
@@ -28,61 +28,6 @@ namespace skinny {
 constexpr int BK = 128;  // byte-columns (= k) per tile = one group
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
-  asm volatile(  // M0 is written and not restored (qmm_large_common.h: nothing else in this kernel needs it)
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off"
-      :
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-// non-temporal flavour for the weight stream: every weight byte is read once per pass (MI355X_MICROARCH.md "nt-weights":
-// issued -> landed 18 % sooner on one-shot streams)
-__device__ __forceinline__ void glds16_nt(const void* gsrc, uint32_t lds_dst) {
-  asm volatile(  // M0 is written and not restored (qmm_large_common.h: nothing else in this kernel needs it)
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off nt"
-      :
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-
-template <int DT>
-struct Mma;
-template <>
-struct Mma<QUANTO_HIP_BF16> {
-  using V8 = bf16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-  static constexpr uint32_t MAGIC = 0x43004300u;
-  static constexpr float OFFSET = 128.f;
-};
-template <>
-struct Mma<QUANTO_HIP_F16> {
-  using V8 = f16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-  static constexpr uint32_t MAGIC = 0x64006400u;
-  static constexpr float OFFSET = 1024.f;
-};
-
-template <int DT>
-__device__ __forceinline__ uint32_t ONE2() { return DT == QUANTO_HIP_BF16 ? 0x3F803F80u : 0x3C003C00u; }  // (1.0, 1.0)
-
-// s_waitcnt vmcnt(n * PER) for n = 0 .. MAXN/PER: the immediate must be a literal, hence the ladder
-template <int MAXN, int PER>
-__device__ __forceinline__ void wait_vmcnt(int younger_tiles) {
-  if constexpr (MAXN > 0) {
-    if (younger_tiles * PER >= MAXN) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MAXN) : "memory");
-      return;
-    }
-    wait_vmcnt<MAXN - PER, PER>(younger_tiles);
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-}
 
 struct Args {
   const void* x;        // [M, K]
@@ -324,7 +269,7 @@ __global__ void __launch_bounds__(WAVES * SETS * 64) qbits_skinny_kernel(Args a,
 
   // all-ones operand: one extra MFMA per k-step returns sum_k x[token, k] (the XS term of the group fold) in fp32,
   // without any VALU work or a pre-kernel; the matrix pipe is idle most of the time in this HBM-bound kernel.
-  const V8 ones = __builtin_bit_cast(V8, make_uint4(ONE2<DT>(), ONE2<DT>(), ONE2<DT>(), ONE2<DT>()));
+  const V8 ones = __builtin_bit_cast(V8, make_uint4(Mma<DT>::ONE2, Mma<DT>::ONE2, Mma<DT>::ONE2, Mma<DT>::ONE2));
 
   // One tile = 128 k = GPT groups: read the wave's weight bytes, 4 k-steps x (TF + TF) MFMAs, one fold into acc per group (after
   // 4 / GPT k-steps: group sizes 128, 64, 32)

@@ -14,7 +14,7 @@
 //     same workspace contract (zeroed arrival counters, system-coherent partial sums) as qbits_skinny.hip.
 #include <cstdlib>
 
-#include "qh_common.h"
+#include "qh_mfma.h"
 
 namespace qh {
 namespace skinny8 {
@@ -23,88 +23,7 @@ constexpr int BK = 128;  // k per tile = bytes per weight row and tile
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
-  asm volatile(  // M0 is written and not restored (qmm_large_common.h: nothing else in this kernel needs it)
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off"
-      :
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-// non-temporal flavour for the weight stream: every weight byte is read once per pass (MI355X_MICROARCH.md "nt-weights":
-// issued -> landed 18 % sooner on one-shot streams)
-__device__ __forceinline__ void glds16_nt(const void* gsrc, uint32_t lds_dst) {
-  asm volatile(  // M0 is written and not restored (qmm_large_common.h: nothing else in this kernel needs it)
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off nt"
-      :
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-
-template <int DT>
-struct Mma;
-template <>
-struct Mma<QUANTO_HIP_BF16> {
-  using V8 = bf16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ uint32_t pack(float a, float b) {
-    bf16x2 r;
-    r.x = (__bf16)a;
-    r.y = (__bf16)b;
-    return __builtin_bit_cast(uint32_t, r);
-  }
-};
-template <>
-struct Mma<QUANTO_HIP_F16> {
-  using V8 = f16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ uint32_t pack(float a, float b) { return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b)); }
-};
-
-enum { W_I8 = 0, W_F8E4M3 = 1, W_F8E5M2 = 2, W_F8E4M3FNUZ = 3 };
-
-// bytes (2p, 2p+1) of `word` -> two 16-bit elements (exact: every int8 / fp8 value is representable in bf16 and fp16);
-// fp8 / bf8 in one op with gfx950's v_cvt_scalef32_pk_{bf16,f16}_{fp8,bf8} at scale 1.0 (see qmm_large_common.h)
-template <int DT, int FMT>
-__device__ __forceinline__ uint32_t convert_pair(uint32_t word, int p) {
-  if constexpr (FMT == W_I8) {
-    const float f0 = p == 0 ? (float)(int8_t)(word & 0xFFu) : (float)(int8_t)((word >> 16) & 0xFFu);
-    const float f1 = p == 0 ? (float)(int8_t)((word >> 8) & 0xFFu) : (float)(int8_t)(word >> 24);
-    return Mma<DT>::pack(f0, f1);
-  } else if constexpr (FMT == W_F8E4M3FNUZ) {
-    return DT == QUANTO_HIP_BF16 ? fnuz_pair_bf16(word, p) : fnuz_pair_f16(word, p);  // qh_common.h
-  } else if constexpr (FMT == W_F8E4M3) {
-    if constexpr (DT == QUANTO_HIP_BF16)
-      return __builtin_bit_cast(uint32_t, p == 0 ? __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)word, 1.0f, false)
-                                                 : __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)word, 1.0f, true));
-    else
-      return __builtin_bit_cast(uint32_t, p == 0 ? __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)word, 1.0f, false)
-                                                 : __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)word, 1.0f, true));
-  } else {
-    if constexpr (DT == QUANTO_HIP_BF16)
-      return __builtin_bit_cast(uint32_t, p == 0 ? __builtin_amdgcn_cvt_scalef32_pk_bf16_bf8((int)word, 1.0f, false)
-                                                 : __builtin_amdgcn_cvt_scalef32_pk_bf16_bf8((int)word, 1.0f, true));
-    else
-      return __builtin_bit_cast(uint32_t, p == 0 ? __builtin_amdgcn_cvt_scalef32_pk_f16_bf8((int)word, 1.0f, false)
-                                                 : __builtin_amdgcn_cvt_scalef32_pk_f16_bf8((int)word, 1.0f, true));
-  }
-}
-
-template <int MAXN, int PER>
-__device__ __forceinline__ void wait_vmcnt(int younger_tiles) {
-  if constexpr (MAXN > 0) {
-    if (younger_tiles * PER >= MAXN) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MAXN) : "memory");
-      return;
-    }
-    wait_vmcnt<MAXN - PER, PER>(younger_tiles);
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-}
+using namespace w8;  // qh_mfma.h: W_I8 .. W_F8E4M3FNUZ, convert_pair
 
 struct Args {
   const void* x;      // [M, K] activations (M <= 64 per launch)

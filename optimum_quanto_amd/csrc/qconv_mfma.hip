@@ -29,7 +29,7 @@
 // gather, pixel pairs, magic-number table, 8-byte epilogue stores (r5): ~1.2 us per K-tile; DESIGN.md 4.8.
 #include <type_traits>
 
-#include "qh_common.h"
+#include "qh_mfma.h"
 
 #ifndef QH_CONV_ABLATE
 #define QH_CONV_ABLATE 0  // timing experiments only (scripts/probes/conv_ablate.hip; WRONG results): 1 no gather loads, 2 no MFMAs / fragment reads, 4 no weight
@@ -57,36 +57,9 @@ struct __attribute__((packed, aligned(1))) U1u { uint32_t x; };
 __device__ __forceinline__ int lds_off(int row, int kc) { return row * (BK * 2) + ((kc ^ (row & 7)) << 4); }
 
 template <int DT>
-struct Mma;
-template <>
-struct Mma<QUANTO_HIP_BF16> {
-  using V8 = bf16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <>
-struct Mma<QUANTO_HIP_F16> {
-  using V8 = f16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-
-template <int DT>
 __device__ __forceinline__ uint32_t pack_rne(float a, float b) {
   using E = Elem<DT>;
   return (uint32_t)__builtin_bit_cast(uint16_t, E::from_f32(a)) | ((uint32_t)__builtin_bit_cast(uint16_t, E::from_f32(b)) << 16);
-}
-
-// two floats that are EXACT in the 16-bit type (int8 / fp8 weights) -> one dword with one instruction (v_cvt_pk_bf16_f32 / v_cvt_pkrtz_f16_f32);
-// pack_rne converts element by element and ors the halves (two conversions + shift + or)
-template <int DT>
-__device__ __forceinline__ uint32_t pack_exact(float a, float b) {
-  if constexpr (DT == QUANTO_HIP_BF16) {
-    bf16x2 r;
-    r.x = (__bf16)a;
-    r.y = (__bf16)b;
-    return __builtin_bit_cast(uint32_t, r);
-  } else {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
-  }
 }
 
 // two 16-bit elements -> one dword.  As a two-element vector of 16-bit integers: hipcc emits ONE v_perm_b32 that takes the low halves of both

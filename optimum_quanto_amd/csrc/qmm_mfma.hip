@@ -15,7 +15,7 @@
 //     exact-math product of the reference's integers and scales up to fp32 accumulation order.
 // Weight tiles are read from HBM exactly once per (m-tile, n-tile); the dense dequantized weight the reference
 // materialises on every call (library/qbytes_mm.py:25-33, tensor/qbits.py:27-49) never exists.
-#include "qh_common.h"
+#include "qh_mfma.h"
 
 namespace qh {
 
@@ -25,32 +25,6 @@ constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_BYTES = BM * BK * 2;  // one operand tile in LDS (16 KiB)
 
 __device__ __forceinline__ int lds_off(int row, int kc) { return row * (BK * 2) + ((kc ^ (row & 7)) << 4); }
-
-template <int DT>
-struct Mma;
-template <>
-struct Mma<QUANTO_HIP_BF16> {
-  using V8 = bf16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ uint32_t pack(float a, float b) {
-    bf16x2 r;
-    r.x = (__bf16)a;
-    r.y = (__bf16)b;
-    return __builtin_bit_cast(uint32_t, r);
-  }
-  static constexpr uint32_t MAGIC = 0x43004300u;
-  static constexpr float OFFSET = 128.f;
-};
-template <>
-struct Mma<QUANTO_HIP_F16> {
-  using V8 = f16x8;
-  static __device__ __forceinline__ f32x4 run(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ uint32_t pack(float a, float b) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));  // exact for every int8 / fp8 value
-  }
-  static constexpr uint32_t MAGIC = 0x64006400u;
-  static constexpr float OFFSET = 1024.f;
-};
 
 // 16 one-byte weights -> 16 elements of the activation dtype (two 16-byte LDS chunks)
 template <int DT, int FMT>
@@ -72,8 +46,8 @@ __device__ __forceinline__ void convert16(const uint4& w, uint4& c0, uint4& c1) 
       const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)in[d], false), hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)in[d], true);
       f0 = lo.x; f1 = lo.y; f2 = hi.x; f3 = hi.y;
     }
-    out[2 * d] = Mma<DT>::pack(f0, f1);
-    out[2 * d + 1] = Mma<DT>::pack(f2, f3);
+    out[2 * d] = pack_exact<DT>(f0, f1);
+    out[2 * d + 1] = pack_exact<DT>(f2, f3);
   }
   c0 = make_uint4(out[0], out[1], out[2], out[3]);
   c1 = make_uint4(out[4], out[5], out[6], out[7]);

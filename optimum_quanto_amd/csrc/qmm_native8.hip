@@ -13,7 +13,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "qh_common.h"
+#include "qh_mfma.h"
 
 #ifndef QH_N8_ABLATE
 #define QH_N8_ABLATE 0  // timing experiments only: 1 = no DMA inside the K loop
@@ -34,21 +34,6 @@ constexpr int STAGES = 4;
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-// M0 is written and not restored (see qmm_mfma_large.hip: nothing else in these kernels reads it, and every scalar
-// instruction in the K loop takes an MFMA issue gap).
-#ifndef QH_GLDS_POLICY
-#define QH_GLDS_POLICY ""  // cache policy bits of the operand DMA (probes: " sc1", " nt", " sc0 sc1": profiles/r06_glds_cache_policy_ab.jsonl)
-#endif
-__device__ __forceinline__ void glds16(const void* sbase, uint32_t voff, uint32_t lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, %1" QH_GLDS_POLICY
-      :
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
 
 __device__ __forceinline__ int swz64(int row) { return (-(row >> 2)) & 3; }  // 64-byte rows, lanes read chunk lane>>4
 

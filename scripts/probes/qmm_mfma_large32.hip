@@ -36,7 +36,7 @@ namespace lt32 {
 using lt::Args;
 using lt::BK;
 using lt::convert_pair;
-using lt::glds16;
+using qh::glds16;
 using lt::lds_ptr_t;
 using lt::STAGES;
 using lt::tile_coords;
