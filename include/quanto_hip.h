@@ -334,6 +334,36 @@ int quanto_hip_qbytes_conv2d_depthwise(const void* x, const void* w, const void*
                                        int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype, void* stream);
 
 /*
+ * F.conv2d with QUANTIZED activations (an ActivationQBytesTensor input of QConv2d) and an 8-bit weight, on the 8-bit matrix instructions - where the
+ * reference dequantizes both and runs a float convolution.  Dense convolution (groups = 1) as an implicit GEMM over the stored 1-byte codes (no im2col,
+ * no dequantized activation or weight), with the W8A8 QLinear arithmetic (qbytes_mm_bias(x_q, w_q, x_scale * w_scale, bias)) on the im2col:
+ *   sc[n] = round_dtype(fp32(a_scale[0]) * fp32(w_scale[n]))
+ *   v     = round_dtype(fp32(acc[m, n]) * sc[n]),  acc = sum_{c,i,j} x[b, c, oh*sh - ph + i*dh, ow*sw - pw + j*dw] * w[n, c, i, j]
+ *   y     = bias ? round_dtype(v + fp32(bias[n])) : v
+ *   acc: exact int32 for int8 x int8 (bit-identical split or unsplit); the fp32 matrix-pipe sum of exact products for fp8.
+ *   x: a_dtype[B, cin, H, W] (NCHW, contiguous); w: b_dtype[OC, cin, KH, KW]; a_scale: out_dtype[1]; w_scale: out_dtype[OC]; bias: out_dtype[OC] or
+ *   NULL; y: out_dtype[B, OC, OH, OW] with OH, OW as for quanto_hip_qbytes_conv2d.  Served (a_dtype, b_dtype): (I8, I8), (F8_E4M3FN | F8_E5M2,
+ *   F8_E4M3FN | F8_E5M2), (F8_E4M3FN | F8_E5M2, I8); out_dtype in {F32, F16, BF16}.  Geometry limits of quanto_hip_qbytes_conv2d (windows of up to
+ *   127 taps, any stride / dilation / padding, any K below 2^24, 31-bit offsets).  QUANTO_HIP_ENOTSUP otherwise (e4m3fnuz on either side, int8
+ *   activations with fp8 weights, other output dtypes).  B OH OW = 0: QUANTO_HIP_OK, nothing launched.  Kernel: csrc/qconv_a8.hip; last_kernel():
+ *   "conv2d_a8_int8", "conv2d_a8_fp8" or "conv2d_a8_fp8_w8".
+ *   workspace / workspace_bytes: optional K-split scratch of quanto_hip_qbytes_conv2d_a8_workspace_size (16-byte aligned; NULL, 0: unsplit).
+ */
+int quanto_hip_qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, int64_t B, int64_t cin,
+                                int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
+                                int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
+/*
+ * Scratch bytes quanto_hip_qbytes_conv2d_a8 wants for its K split (0: unsplit, or B OH OW = 0): partial tiles that a separate kernel adds in split
+ * order (deterministic, no atomics, nothing to zero).  QUANTO_HIP_EINVAL for inconsistent geometry, QUANTO_HIP_ENOTSUP for a format or geometry the
+ * kernel does not serve.  Needs no device.
+ */
+int64_t quanto_hip_qbytes_conv2d_a8_workspace_size(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW,
+                                                   int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype,
+                                                   int out_dtype);
+
+/*
  * Scratch bytes the convolution kernels want for their K split (0: the problem is not split): when the 128 x 128 output tiles alone cannot
  * occupy the chip the K-tiles are dealt over up to 64 workgroups per tile, whose fp32 sums a second kernel adds in split order (deterministic,
  * no atomics, nothing to zero).  K = cin * KH * KW.  Both quanto_hip_q*_conv2d entries take the buffer (16-byte aligned); with NULL / too few

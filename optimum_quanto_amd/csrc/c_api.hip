@@ -42,6 +42,12 @@ size_t conv2d_dense_weight_bytes(int64_t, int64_t);
 bool conv2d_rows_eligible(int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int64_t);
 int qdense_conv2d_rows(const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int,
                        int, int, int, int, int, void*, size_t, hipStream_t);
+// convolution with quantized activations on the 8-bit matrix instructions (qconv_a8.hip)
+int qbytes_conv2d_a8_kind(int, int, int);
+bool qbytes_conv2d_a8_geometry_ok(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t);
+size_t conv2d_a8_workspace(int64_t, int64_t, int64_t);
+int qbytes_conv2d_a8(const void*, const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                     int64_t, int64_t, int, int, int, int, int, int, int, int, int, void*, size_t, hipStream_t, int*);
 int qbytes_conv2d_mfma(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                        int64_t, int, int, int, int, int, int, int, int, int, void*, size_t, hipStream_t, bool* rows);
 int qbytes_mm_gemv_multi(const void*, int, const void* const*, const void* const*, const void* const*, void* const*, const int64_t*, int64_t,
@@ -753,6 +759,34 @@ int quanto_hip_qbytes_conv2d(const void* x, const void* w, const void* scales, c
   const int r = qbytes_conv2d_mfma(x, w, scales, bias, y, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, a_dtype,
                                    b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), &rows);
   if (r == QUANTO_HIP_OK) set_last_kernel(rows ? "conv2d_mfma_rows" : "conv2d_mfma");
+  return r;
+}
+
+int64_t quanto_hip_qbytes_conv2d_a8_workspace_size(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW,
+                                                   int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype,
+                                                   int out_dtype) {
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+  if (geo != QUANTO_HIP_OK) return geo;
+  if (qbytes_conv2d_a8_kind(a_dtype, b_dtype, out_dtype) < 0) return QUANTO_HIP_ENOTSUP;
+  if (B == 0 || OH == 0 || OW == 0) return 0;
+  if (!qbytes_conv2d_a8_geometry_ok(B, cin, H, W, OC, KH, KW, OH, OW)) return QUANTO_HIP_ENOTSUP;
+  return (int64_t)conv2d_a8_workspace(B * OH * OW, OC, cin * KH * KW);
+}
+
+int quanto_hip_qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, int64_t B, int64_t cin,
+                                int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
+                                int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+  if (geo != QUANTO_HIP_OK) return geo;
+  if (qbytes_conv2d_a8_kind(a_dtype, b_dtype, out_dtype) < 0) return QUANTO_HIP_ENOTSUP;
+  if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
+  if (!x || !a_scale || !w || !w_scale || !y) return QUANTO_HIP_EINVAL;
+  int kind = -1;
+  const int r = qbytes_conv2d_a8(x, a_scale, w, w_scale, bias, y, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, a_dtype,
+                                 b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), &kind);
+  static const char* const names[3] = {"conv2d_a8_int8", "conv2d_a8_fp8", "conv2d_a8_fp8_w8"};
+  if (r == QUANTO_HIP_OK) set_last_kernel(names[kind]);
   return r;
 }
 

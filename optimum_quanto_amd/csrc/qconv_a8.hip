@@ -1,0 +1,458 @@
+// F.conv2d with QUANTIZED activations and an 8-bit weight as an IMPLICIT GEMM on the 8-bit matrix instructions: QConv2d.forward (nn/qconv2d.py:54-55)
+// with an ActivationQBytesTensor input, which the reference dequantizes (activation and weight) and convolves in float.
+//
+//   sc[n] = round_dtype(fp32(a_scale) * fp32(w_scale[n]))                     (= torch's product of the two scale tensors in their dtype)
+//   v     = round_dtype(fp32(acc[m, n]) * fp32(sc[n])),   acc[m, n] = sum_{c,i,j} xq[b, c, oh*sh - ph + i*dh, ow*sw - pw + j*dw] * wq[n, c, i, j]
+//   y     = bias ? round_dtype(fp32(v) + fp32(bias[n])) : v
+//
+// - the W8A8 QLinear arithmetic (qbytes_mm_bias(x_q, w_q, x_scale * w_scale, bias), qmm_native8.hip's epilogue) applied to the im2col of the stored
+// codes.  acc is exact int32 for int8 x int8 (the result is a pure function of the integers, split or not) and the fp32 matrix-pipe sum of exact
+// products for fp8.
+//
+// GEMM view, tiles and gather = qconv_mfma.hip's tap kernel: M = B*OH*OW pixels, N = OC, K = cin*KH*KW in the weight's (c, i, j)
+// order; one workgroup = 128 pixels x 128 channels, eight waves (2 x 4, 64 pixels x 32 channels each), two LDS buffers.  A K-tile is 128 ONE-byte
+// elements - again a 128-byte LDS row, so lds_off's swizzle and the conflict-free fragment reads carry over unchanged:
+//   * a thread stages one pixel (tile row tid & 127) and two 16-byte chunks of it per K-tile, kc = (tid >> 7) + 4 j: k is uniform across a wave;
+//   * the k-only part of an address (byte offset of tap (c, i, j) relative to the window's top-left tap, and the tap's number) comes from a
+//     128-entry LDS table per K-tile; the pixel-only part (base offset, one validity bit per tap) lives in registers; an element is one
+//     range-checked BUFFER byte load whose offset is forced to 0xFFFFFFFF for a padding tap or a k behind K: it reads 0 (int8 0, fp8 +0.0), nothing
+//     is masked afterwards;
+//   * fragments: lane (row lane & 15, 16-byte chunk lane >> 4 of each 64-byte half of the row) - the maps of qmm_native8.hip (one K = 64 int8
+//     MFMA per half: v_mfma_i32_16x16x64_i8) and of its paired fp8 form (both halves as ONE K = 128 v_mfma_scale_f32_16x16x128_f8f6f4, the same k
+//     assignment in both operands, A and B formats independent, block scales 2^0).
+// fp8 activations x int8 weights: q = 16 hi + lo with hi = q >> 4 in [-8, 7] and lo = q & 15 in [0, 15], both exact e4m3 codes, built from the
+// LDS fragment by v_perm over 16-entry code tables (qbits_a8_fused.hip's nibble scheme).  Two MX-format MFMAs per fragment into the SAME fp32
+// accumulator: lo with weight block scale 2^0, hi with 2^4 - the fold 16 hi + lo happens exactly inside the matrix pipe (an e4m3 / e5m2 value times
+// an integer of magnitude <= 128 is exact in fp32), no extra accumulator set, no fp32 math between the MFMAs.
+// K split (grids that cannot fill the chip): qconv_mfma.hip's scheme - split z parks its int32 / fp32 tile in `partials`, a separate kernel adds the
+// splits in split order (deterministic; int32: bit-identical to the unsplit result) and runs the epilogue.
+#include <type_traits>
+
+#include "qh_mfma.h"
+
+namespace qh {
+namespace conv8 {
+
+constexpr int BM = 128, BN = 128, BK = 128, NT = 512;
+constexpr int TILE_BYTES = BM * BK;                              // one operand tile in LDS (16 KiB)
+constexpr int LDS_BYTES = 2 * 2 * TILE_BYTES + 2 * BK * 8;       // two buffers + two tap tables
+
+enum Kind { K_I8 = 0, K_F8 = 1, K_F8W8 = 2 };  // int8 x int8, fp8 x fp8, fp8 activations x int8 weights
+enum { F_E4M3 = 0, F_E5M2 = 1 };              // cbsz / blgp codes of the MX-format instruction
+
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+
+struct __attribute__((packed, aligned(1))) U4u { uint32_t x, y, z, w; };  // byte-aligned 16-byte load (K need not be a multiple of anything)
+
+__device__ __forceinline__ int lds_off(int row, int kc) { return row * BK + ((kc ^ (row & 7)) << 4); }
+
+struct Args {
+  const uint8_t* x;       // [B, cin, H, W] int8 / fp8 codes
+  const void* a_scale;    // one element, out dtype
+  const uint8_t* w;       // [OC, K] int8 / fp8 codes
+  const void* w_scale;    // [OC], out dtype
+  const void* bias;       // [OC] or null
+  void* y;                // [B, OC, OH, OW] out dtype
+  int M, N, K;            // M = B OH OW, N = OC, K = cin KH KW
+  int cin, H, W, KH, KW, OH, OW, sh, sw, ph, pw, dh, dw;
+  int out_dtype;          // QUANTO_HIP_{F32, F16, BF16}
+  int S;                  // K split over blockIdx.z
+  void* partials;         // [S][tiles][8 waves][8 fragments][64 lanes] 16 bytes (int32 / fp32)
+  uint32_t khw_magic, kw_magic;  // ceil(2^32 / (KH KW)), ceil(2^32 / KW); 0 when the divisor is 1
+};
+static uint32_t div_magic(int d) { return d <= 1 ? 0u : (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d); }
+
+// ---- epilogue: the lane's 4 x 2 fragments (D row = pixel (lane >> 4) * 4 + r of fragment i, column = channel lane & 15 of fragment j) -> NCHW;
+// the lane's four rows are four neighbouring pixels of one channel plane: one 8- / 16-byte store when they lie in one image and are aligned
+template <int DT, typename AV>
+__device__ __forceinline__ void store_tile_dt(const Args& a, const AV (&acc)[4][2], int m0, int nt, int wm, int wn, int lane) {
+  using E = Elem<DT>;
+  using T = typename E::T;
+  T* yg = reinterpret_cast<T*>(a.y);
+  const int M = a.M, N = a.N, L = a.OH * a.OW;
+  const bool vec = (L & 3) == 0 && (reinterpret_cast<uintptr_t>(a.y) & (4 * sizeof(T) - 1)) == 0;
+  const float as = E::to_f32(*reinterpret_cast<const T*>(a.a_scale));
+  int bq[4], lq[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
+    const int b = m / L;
+    bq[i] = b;
+    lq[i] = m - b * L;
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int n = nt * BN + wn * 32 + j * 16 + (lane & 15);
+    if (n >= N) continue;
+    const float sc = E::to_f32(E::from_f32(as * E::to_f32(reinterpret_cast<const T*>(a.w_scale)[n])));  // the scale product in the dtype
+    const bool has_bias = a.bias != nullptr;
+    const float bv = has_bias ? E::to_f32(reinterpret_cast<const T*>(a.bias)[n]) : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
+      if (m >= M) continue;
+      T out[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = (float)acc[i][j][r] * sc;
+        asm volatile("" : "+v"(v));  // product rounded to fp32 first (no single-rounding v_fma_mixlo_f16)
+        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv;
+        out[r] = E::from_f32(v);
+      }
+      T* dst = yg + ((size_t)bq[i] * N + n) * L + lq[i];
+      if (vec && m + 3 < M) {
+        if constexpr (sizeof(T) == 2)
+          *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(out);
+        else
+          *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(out);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (m + r < M) {
+            int bb = bq[i], ll = lq[i] + r;
+            while (ll >= L) {  // an image ends inside the lane's four pixels
+              ll -= L;
+              ++bb;
+            }
+            yg[((size_t)bb * N + n) * L + ll] = out[r];
+          }
+      }
+    }
+  }
+}
+template <typename AV>
+__device__ __forceinline__ void store_tile(const Args& a, const AV (&acc)[4][2], int m0, int nt, int wm, int wn, int lane) {
+  if (a.out_dtype == QUANTO_HIP_BF16)
+    store_tile_dt<QUANTO_HIP_BF16>(a, acc, m0, nt, wm, wn, lane);
+  else if (a.out_dtype == QUANTO_HIP_F16)
+    store_tile_dt<QUANTO_HIP_F16>(a, acc, m0, nt, wm, wn, lane);
+  else
+    store_tile_dt<QUANTO_HIP_F32>(a, acc, m0, nt, wm, wn, lane);
+}
+
+// int8 weight codes (4 per dword) -> e4m3 codes of lo = q & 15 and of hi = q >> 4 (16-entry tables, three v_perm each)
+__device__ __forceinline__ uint32_t nibble_codes(uint32_t s, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3) {
+  const uint32_t q7 = s & 0x07070707u;
+  const uint32_t lo = __builtin_amdgcn_perm(t1, t0, q7), hi = __builtin_amdgcn_perm(t3, t2, q7);
+  return __builtin_amdgcn_perm(hi, lo, ((s >> 1) & 0x04040404u) | 0x03020100u);  // byte i from hi when bit 3 of nibble i is set
+}
+
+template <int KIND, int AF, int BF, bool WIDE>
+__global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
+  constexpr int NO_TAP = WIDE ? 127 : 31;
+  using AV = typename std::conditional<KIND == K_I8, i32x4, f32x4>::type;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // [2 buffers][A tile | B tile] [2 tap tables]
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  const int m0 = blockIdx.y * BM, nt = blockIdx.x;
+  const int M = a.M, N = a.N, K = a.K;
+  const int S = a.S, sp = blockIdx.z;
+  const int nk_all = (K + BK - 1) / BK;
+  const int kt_lo = (int)((long)sp * nk_all / S), nk = (int)((long)(sp + 1) * nk_all / S) - kt_lo;
+  // x as a raw buffer whose range is its true size (< 2^30 bytes): an offset of 0xFFFFFFFF reads as 0
+  const __amdgpu_buffer_rsrc_t xrsrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.x), 0, (int)(((long)M / (a.OH * a.OW)) * a.cin * a.H * a.W), 0x00020000);
+
+  // ---- the thread's pixel: byte offset of element (b, 0, oh sh, ow sw) and one validity bit per tap (set: inside the image) ----
+  uint32_t px_off;
+  uint64_t ok0 = 0, ok1 = 0;
+  {
+    const int L = a.OH * a.OW;
+    int m = m0 + (tid & 127);
+    m = m < M ? m : M - 1;
+    const int b = m / L, l = m - b * L, oh = l / a.OW, ow = l - oh * a.OW;
+    const int ih0 = oh * a.sh - a.ph, iw0 = ow * a.sw - a.pw;
+    px_off = (uint32_t)(b * a.cin * a.H * a.W + oh * a.sh * a.W + ow * a.sw);
+    for (int ki = 0; ki < a.KH; ++ki)
+      for (int kj = 0; kj < a.KW; ++kj) {
+        const int ih = ih0 + ki * a.dh, iw = iw0 + kj * a.dw;
+        const int t = ki * a.KW + kj;
+        const uint64_t bit = 1ull << (t & 63);
+        if (ih >= 0 && ih < a.H && iw >= 0 && iw < a.W) {
+          if (WIDE && t >= 64)
+            ok1 |= bit;
+          else
+            ok0 |= bit;
+        }
+      }
+  }
+  auto tap_ok = [&](int tp) -> int {  // -1: tap tp lies inside the image
+    if constexpr (WIDE)
+      return -(int)((((tp & 64) ? ok1 : ok0) >> (tp & 63)) & 1ull);
+    else
+      return __builtin_amdgcn_sbfe((uint32_t)ok0, tp, 1);
+  };
+  int2* ktab = reinterpret_cast<int2*>(smem + 2 * 2 * TILE_BYTES);  // [2][128] {byte offset relative to px_off, tap number}
+  auto div_small = [](int n, int d, uint32_t magic, int& rem) {  // exact for n < 2^24, d <= 127 (qconv_mfma.hip)
+    const int q = magic ? (int)__umulhi((uint32_t)n, magic) : n;
+    rem = n - q * d;
+    return q;
+  };
+  auto fill_ktab = [&](int t) {
+    if (tid < BK) {
+      const int k = (kt_lo + t) * BK + tid;
+      int rem, kj;
+      const int ci = div_small(k, a.KH * a.KW, a.khw_magic, rem);
+      const int ki = div_small(rem, a.KW, a.kw_magic, kj);
+      ktab[(t & 1) * BK + tid] = k < K ? make_int2((ci * a.H + ki * a.dh) * a.W + kj * a.dw - (a.ph * a.W + a.pw), rem) : make_int2(0, NO_TAP);
+    }
+  };
+
+  // ---- staging registers: 2 x 16 gathered bytes, 32 weight bytes (channel tid >> 2, bytes 32 (tid & 3) ..) ----
+  uint8_t g[2][16];
+  uint4 rw[2];
+  auto issue_loads = [&](int t) {
+    const int k0 = (kt_lo + t) * BK;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int kc = __builtin_amdgcn_readfirstlane(tid >> 7) + 4 * j;
+      const int4* tp = reinterpret_cast<const int4*>(ktab + (t & 1) * BK + kc * 16);
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        const int4 t0 = tp[2 * h], t1 = tp[2 * h + 1];
+        const int off[4] = {t0.x, t0.z, t1.x, t1.z}, tap[4] = {t0.y, t0.w, t1.y, t1.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          g[j][4 * h + q] = __builtin_amdgcn_raw_buffer_load_b8(xrsrc, (px_off + (uint32_t)off[q]) | ~(uint32_t)tap_ok(tap[q]), 0, 0);
+      }
+    }
+    int n = nt * BN + (tid >> 2);
+    n = n < N ? n : N - 1;
+    const int kb = k0 + (tid & 3) * 32;
+    const uint8_t* src = a.w + (size_t)n * K + kb;
+    if (kb + 32 <= K) {
+      const U4u u0 = reinterpret_cast<const U4u*>(src)[0], u1 = reinterpret_cast<const U4u*>(src)[1];
+      rw[0] = make_uint4(u0.x, u0.y, u0.z, u0.w);
+      rw[1] = make_uint4(u1.x, u1.y, u1.z, u1.w);
+    } else {  // ragged end of the last K-tile: zero bytes behind K, nothing is read beyond the row
+      uint32_t d[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+      for (int b = 0; b < 32; ++b)
+        if (kb + b < K) d[b >> 2] |= (uint32_t)src[b] << (8 * (b & 3));
+      rw[0] = make_uint4(d[0], d[1], d[2], d[3]);
+      rw[1] = make_uint4(d[4], d[5], d[6], d[7]);
+    }
+  };
+  auto pack4 = [](uint8_t b0, uint8_t b1, uint8_t b2, uint8_t b3) -> uint32_t {
+    return (uint32_t)b0 | ((uint32_t)b1 << 8) | ((uint32_t)b2 << 16) | ((uint32_t)b3 << 24);
+  };
+  auto write_lds = [&](int buf) {
+    uint8_t* sa = smem + buf * 2 * TILE_BYTES;
+    uint8_t* sb = sa + TILE_BYTES;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      *reinterpret_cast<uint4*>(sa + lds_off(tid & 127, (tid >> 7) + 4 * j)) =
+          make_uint4(pack4(g[j][0], g[j][1], g[j][2], g[j][3]), pack4(g[j][4], g[j][5], g[j][6], g[j][7]),
+                     pack4(g[j][8], g[j][9], g[j][10], g[j][11]), pack4(g[j][12], g[j][13], g[j][14], g[j][15]));
+    const int row = tid >> 2, part = tid & 3;
+    *reinterpret_cast<uint4*>(sb + lds_off(row, 2 * part)) = rw[0];
+    *reinterpret_cast<uint4*>(sb + lds_off(row, 2 * part + 1)) = rw[1];
+  };
+
+  AV acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = AV{0, 0, 0, 0};
+
+  auto mma_phase = [&](const uint8_t* sa, const uint8_t* sb) {
+    // fragment halves h = 0, 1: 16 bytes of chunk 4 h + (lane >> 4) of the fragment's row
+    uint4 fa[2][4], fb[2][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int kc = h * 4 + (lane >> 4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) fa[h][i] = *reinterpret_cast<const uint4*>(sa + lds_off(wm * 64 + i * 16 + (lane & 15), kc));
+#pragma unroll
+      for (int j = 0; j < 2; ++j) fb[h][j] = *reinterpret_cast<const uint4*>(sb + lds_off(wn * 32 + j * 16 + (lane & 15), kc));
+    }
+    auto cat = [](const uint4& lo, const uint4& hi) { return i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w}; };
+    if constexpr (KIND == K_I8) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, fa[h][i]), __builtin_bit_cast(i32x4, fb[h][j]), acc[i][j], 0, 0, 0);
+    } else if constexpr (KIND == K_F8) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const i32x8 b = cat(fb[0][j], fb[1][j]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(cat(fa[0][i], fa[1][i]), b, acc[i][j], AF, BF, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
+      }
+    } else {
+      // e4m3 codes of 0..15 (lo) and of the signed nibbles 0..7, -8..-1 (hi), four per dword
+      constexpr uint32_t L0 = 0x44403800u, L1 = 0x4E4C4A48u, L2 = 0x53525150u, L3 = 0x57565554u;  // 0 1 2 3 | 4 5 6 7 | 8 .. 11 | 12 .. 15
+      constexpr uint32_t H2 = 0xCACCCED0u, H3 = 0xB8C0C4C8u;                                        // -8 -7 -6 -5 | -4 -3 -2 -1
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        uint32_t w[8] = {fb[0][j].x, fb[0][j].y, fb[0][j].z, fb[0][j].w, fb[1][j].x, fb[1][j].y, fb[1][j].z, fb[1][j].w};
+        uint32_t lo[8], hi[8];
+#pragma unroll
+        for (int d = 0; d < 8; ++d) {
+          lo[d] = nibble_codes(w[d], L0, L1, L2, L3);
+          hi[d] = nibble_codes(w[d] >> 4, L0, L1, H2, H3);
+        }
+        const i32x8 bl = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)lo[4], (int)lo[5], (int)lo[6], (int)lo[7]};
+        const i32x8 bh = i32x8{(int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3], (int)hi[4], (int)hi[5], (int)hi[6], (int)hi[7]};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const i32x8 av = cat(fa[0][i], fa[1][i]);
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bl, acc[i][j], AF, F_E4M3, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);  // lo x 2^0
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bh, acc[i][j], AF, F_E4M3, 0, 0x7F7F7F7F, 0, 0x83838383);  // hi x 2^4
+        }
+      }
+    }
+  };
+
+  fill_ktab(0);
+  if (nk > 1) fill_ktab(1);
+  __syncthreads();
+  issue_loads(0);
+  write_lds(0);
+  __syncthreads();
+  int cur = 0;
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt + 1 < nk) issue_loads(kt + 1);
+    if (kt + 2 < nk) fill_ktab(kt + 2);  // into the table buffer tile kt's gather last read; visible after this iteration's barrier
+    const uint8_t* sa = smem + cur * 2 * TILE_BYTES;
+    mma_phase(sa, sa + TILE_BYTES);
+    if (kt + 1 < nk) write_lds(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  if (S > 1) {  // park the partial sums: one 1 KiB store per wave and fragment
+    AV* mine = reinterpret_cast<AV*>(a.partials) + ((size_t)(sp * gridDim.y + blockIdx.y) * gridDim.x + nt) * (8 * 8 * 64) + (wave * 8) * 64 + lane;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) mine[(i * 2 + j) * 64] = acc[i][j];
+    return;
+  }
+  store_tile(a, acc, m0, nt, wm, wn, lane);
+}
+
+// split-K tail: one wave per (output tile, wave slot) adds that slot's eight fragments over the S partial tiles in split order, then the epilogue
+template <bool INT>
+__global__ void __launch_bounds__(64) qconv2d_a8_reduce_kernel(const Args a) {
+  using AV = typename std::conditional<INT, i32x4, f32x4>::type;
+  const int lane = threadIdx.x, wave = blockIdx.z, S = a.S;
+  AV acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = AV{0, 0, 0, 0};
+  const AV* base = reinterpret_cast<const AV*>(a.partials) + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (8 * 8 * 64) + (wave * 8) * 64 + lane;
+  const size_t split_stride = (size_t)gridDim.y * gridDim.x * (8 * 8 * 64);
+  for (int sp0 = 0; sp0 < S; sp0 += 4) {
+    AV v[4][8];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int sp = sp0 + u < S ? sp0 + u : S - 1;
+#pragma unroll
+      for (int f = 0; f < 8; ++f) v[u][f] = base[sp * split_stride + f * 64];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (sp0 + u < S) {
+#pragma unroll
+        for (int f = 0; f < 8; ++f) acc[f >> 1][f & 1] += v[u][f];
+      }
+  }
+  store_tile(a, acc, blockIdx.y * BM, blockIdx.x, wave >> 2, wave & 3, lane);
+}
+
+// K split: qconv_mfma.hip's rule on this kernel's 128-deep K-tiles - split until the grid reaches ~2 workgroups per CU, at least 4 K-tiles per split
+static int pick_split(int64_t M, int64_t N, int64_t K) {
+  const int forced = env_int("QUANTO_HIP_CONV_SPLIT", 0);  // experiments
+  const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN), nk = (K + BK - 1) / BK;
+  if (forced > 0) return (int)(forced <= nk ? forced : nk);
+  if (tiles > 128) return tiles <= 256 && nk >= 32 ? 2 : 1;
+  int s = 1;
+  while (tiles * (s + 1) <= 512 && nk / (s + 1) >= 4 && s < 64) ++s;
+  return s;
+}
+static size_t split_workspace(int64_t M, int64_t N, int S) { return S <= 1 ? 0 : (size_t)S * ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * (BM * BN * 4); }
+
+// conv::geometry_ok of qconv_mfma.hip (one validity bit per tap, 31-bit offsets, grid.y), with one-byte activations
+static bool geometry_ok(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW) {
+  const int64_t K = cin * KH * KW;
+  return B >= 1 && OH >= 1 && OW >= 1 && K >= 1 && K < (1ll << 24) && KH * KW <= 127 && B * cin * H * W < (1ll << 30) && B * OC * OH * OW < (1ll << 31) &&
+         OC * K < (1ll << 31) && (B * OH * OW + BM - 1) / BM <= 65535;
+}
+
+template <int KIND, int AF, int BF, bool WIDE>
+static void launch_k(const Args& a, int ntiles, int mtiles, hipStream_t stream) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qconv2d_a8_kernel<KIND, AF, BF, WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  hipLaunchKernelGGL((qconv2d_a8_kernel<KIND, AF, BF, WIDE>), dim3(ntiles, mtiles, a.S), dim3(NT), LDS_BYTES, stream, a);
+}
+template <int KIND, int AF, int BF>
+static void launch_w(const Args& a, int ntiles, int mtiles, hipStream_t stream) {
+  if (a.KH * a.KW > 31)
+    launch_k<KIND, AF, BF, true>(a, ntiles, mtiles, stream);
+  else
+    launch_k<KIND, AF, BF, false>(a, ntiles, mtiles, stream);
+}
+
+}  // namespace conv8
+
+// the served (activation, weight, output) formats: int8 x int8, {e4m3fn, e5m2} x {e4m3fn, e5m2, int8}; F32 / F16 / BF16 out
+int qbytes_conv2d_a8_kind(int a_dtype, int b_dtype, int out_dtype) {
+  if (out_dtype != QUANTO_HIP_F32 && out_dtype != QUANTO_HIP_F16 && out_dtype != QUANTO_HIP_BF16) return -1;
+  const bool af8 = a_dtype == QUANTO_HIP_F8_E4M3FN || a_dtype == QUANTO_HIP_F8_E5M2;
+  const bool bf8 = b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2;
+  if (a_dtype == QUANTO_HIP_I8 && b_dtype == QUANTO_HIP_I8) return conv8::K_I8;
+  if (af8 && bf8) return conv8::K_F8;
+  if (af8 && b_dtype == QUANTO_HIP_I8) return conv8::K_F8W8;
+  return -1;
+}
+
+bool qbytes_conv2d_a8_geometry_ok(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW) {
+  return conv8::geometry_ok(B, cin, H, W, OC, KH, KW, OH, OW);
+}
+
+size_t conv2d_a8_workspace(int64_t M, int64_t N, int64_t K) { return conv8::split_workspace(M, N, conv8::pick_split(M, N, K)); }
+
+// *kind: the conv8::Kind that ran.  The caller has validated the arguments and the format (qbytes_conv2d_a8_kind >= 0, geometry_ok).
+int qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, int64_t B, int64_t cin, int64_t H,
+                     int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int sh, int sw, int ph, int pw, int dh, int dw, int a_dtype,
+                     int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
+  using namespace conv8;
+  const int k = qbytes_conv2d_a8_kind(a_dtype, b_dtype, out_dtype);
+  if (k < 0 || !geometry_ok(B, cin, H, W, OC, KH, KW, OH, OW)) return QUANTO_HIP_ENOTSUP;
+  Args a{reinterpret_cast<const uint8_t*>(x), a_scale, reinterpret_cast<const uint8_t*>(w), w_scale, bias, y, (int)(B * OH * OW), (int)OC,
+         (int)(cin * KH * KW), (int)cin, (int)H, (int)W, (int)KH, (int)KW, (int)OH, (int)OW, sh, sw, ph, pw, dh, dw, out_dtype, 1, nullptr,
+         div_magic((int)(KH * KW)), div_magic((int)KW)};
+  int S = pick_split(a.M, a.N, a.K);
+  if (S > 1 && (!workspace || workspace_bytes < split_workspace(a.M, a.N, S) || reinterpret_cast<uintptr_t>(workspace) % 16)) S = 1;
+  a.S = S;
+  a.partials = workspace;
+  const int ntiles = (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;
+  const bool ae5 = a_dtype == QUANTO_HIP_F8_E5M2, be5 = b_dtype == QUANTO_HIP_F8_E5M2;
+  if (k == K_I8) {
+    launch_w<K_I8, 0, 0>(a, ntiles, mtiles, stream);
+  } else if (k == K_F8) {
+    if (ae5)
+      be5 ? launch_w<K_F8, F_E5M2, F_E5M2>(a, ntiles, mtiles, stream) : launch_w<K_F8, F_E5M2, F_E4M3>(a, ntiles, mtiles, stream);
+    else
+      be5 ? launch_w<K_F8, F_E4M3, F_E5M2>(a, ntiles, mtiles, stream) : launch_w<K_F8, F_E4M3, F_E4M3>(a, ntiles, mtiles, stream);
+  } else {
+    ae5 ? launch_w<K_F8W8, F_E5M2, F_E4M3>(a, ntiles, mtiles, stream) : launch_w<K_F8W8, F_E4M3, F_E4M3>(a, ntiles, mtiles, stream);
+  }
+  if (S > 1) {
+    if (k == K_I8)
+      hipLaunchKernelGGL((qconv2d_a8_reduce_kernel<true>), dim3(ntiles, mtiles, 8), dim3(64), 0, stream, a);
+    else
+      hipLaunchKernelGGL((qconv2d_a8_reduce_kernel<false>), dim3(ntiles, mtiles, 8), dim3(64), 0, stream, a);
+  }
+  *kind = k;
+  return launch_status();
+}
+
+}  // namespace qh

@@ -128,6 +128,8 @@ _PROTOTYPES = {
     "quanto_hip_pack": (_ci, [_vp, _vp, _i64, _i64, _ci, _vp]),
     "quanto_hip_qbytes_conv2d": (_ci, [_vp] * 5 + [_i64] * 9 + [_ci] * 9 + [_vp, _sz, _vp]),
     "quanto_hip_qbytes_conv2d_depthwise": (_ci, [_vp] * 5 + [_i64] * 9 + [_ci] * 9 + [_vp]),
+    "quanto_hip_qbytes_conv2d_a8": (_ci, [_vp] * 6 + [_i64] * 9 + [_ci] * 9 + [_vp, _sz, _vp]),
+    "quanto_hip_qbytes_conv2d_a8_workspace_size": (_i64, [_i64] * 9 + [_ci] * 9),
     "quanto_hip_conv2d_workspace_size": (_i64, [_i64] * 5),
     "quanto_hip_qbits_conv2d_workspace_size": (_i64, [_i64] * 5),
     "quanto_hip_qbits_conv2d_workspace_size_geom": (_i64, [_i64] * 8 + [_ci] * 2),
@@ -394,6 +396,63 @@ class _Bindings:
                 ws, ws_bytes = self._conv2d_scratch(x, B, OH, OW, OC, C * KH * KW, stream)
                 st = self._c.quanto_hip_qbytes_conv2d(*args, _ptr(ws), ws_bytes, stream)
         self._check(st, "qbytes_conv2d_depthwise" if depthwise else "qbytes_conv2d")
+        return y
+
+    # -- quanto::qbytes_conv2d_a8 (quantized activations, 8-bit matrix instructions) ------------------------------
+    def _conv2d_a8_workspace(self, x_shape, w_shape, a_dtype, b_dtype, out_dtype, stride, padding, dilation) -> int:
+        """Split-K scratch bytes of csrc/qconv_a8.hip for this call, or a negative status (format / geometry not served, bad geometry); asked
+        once per shape and kept."""
+        adt, bdt, odt = _DTYPES.get(a_dtype), _DTYPES.get(b_dtype), _DTYPES.get(out_dtype)
+        if adt is None or bdt is None or odt is None:
+            return -2
+        B, C, H, W = x_shape
+        OC, _, KH, KW = w_shape
+        OH = self.conv2d_out_size(H, KH, stride[0], padding[0], dilation[0])
+        OW = self.conv2d_out_size(W, KW, stride[1], padding[1], dilation[1])
+        args = (B, C, H, W, OC, KH, KW, max(OH, 0), max(OW, 0), stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], adt, bdt, odt)
+        return self._plan("qbytes_conv2d_a8", args, lambda: (0, 0, int(self._c.quanto_hip_qbytes_conv2d_a8_workspace_size(*args))))[1]
+
+    def qbytes_conv2d_a8_supported(self, x_data, w_data, out_dtype, stride=(1, 1), padding=(0, 0), dilation=(1, 1)) -> bool:
+        """What csrc/qconv_a8.hip takes: NCHW int8 / e4m3fn / e5m2 activation codes on a ROCm device, an [OC, C, KH, KW] int8 (any activation
+        format but int8 x fp8) or e4m3fn / e5m2 weight (fp8 activations), output dtype float32 / float16 / bfloat16, geometry within
+        ``conv2d_geometry_ok``."""
+        if not (x_data.is_cuda and x_data.dim() == 4 and w_data.dim() == 4 and x_data.shape[1] == w_data.shape[1]):
+            return False
+        if min(stride) <= 0 or min(dilation) <= 0 or min(padding) < 0:
+            return False
+        if not self.conv2d_geometry_ok(tuple(x_data.shape), tuple(w_data.shape), stride, padding, dilation):
+            return False
+        return self._conv2d_a8_workspace(tuple(x_data.shape), tuple(w_data.shape), x_data.dtype, w_data.dtype, out_dtype, stride, padding, dilation) >= 0
+
+    def qbytes_conv2d_a8(self, x, x_scale, w, w_scale, bias, stride, padding, dilation):
+        """Dense convolution of quantized activation codes ``x`` (per-tensor scale ``x_scale``, one element) with an 8-bit weight [OC, C, KH, KW]
+        (per-channel scales ``w_scale``): y = conv(x, w) * round(x_scale * w_scale) (+ bias), in w_scale's dtype.  Raises QuantoHipError(ENOTSUP)
+        for formats the kernel does not take."""
+        self._require_cuda(x, x_scale, w, w_scale, bias)
+        if x_scale.numel() != 1:
+            raise QuantoHipError("qbytes_conv2d_a8 expects a per-tensor activation scale")
+        x, w = x.contiguous(), w.contiguous()
+        B, C, H, W = x.shape
+        OC, _, KH, KW = w.shape
+        odt = w_scale.dtype
+        ws_bytes = self._conv2d_a8_workspace(tuple(x.shape), tuple(w.shape), x.dtype, w.dtype, odt, stride, padding, dilation)
+        if ws_bytes < 0:
+            self._check(int(ws_bytes), "qbytes_conv2d_a8")
+        OH = self.conv2d_out_size(H, KH, stride[0], padding[0], dilation[0])
+        OW = self.conv2d_out_size(W, KW, stride[1], padding[1], dilation[1])
+        s = w_scale.reshape(-1).contiguous()
+        if s.numel() == 1:
+            s = s.expand(OC).contiguous()
+        xs = x_scale.reshape(1).to(odt).contiguous()
+        if bias is not None:
+            bias = bias.to(odt).contiguous()
+        y = torch.empty((B, OC, max(OH, 0), max(OW, 0)), dtype=odt, device=x.device)
+        with _DeviceGuard(x.device) as stream:
+            ws = self._scratch(x.device, ws_bytes, stream) if ws_bytes > 0 else None
+            st = self._c.quanto_hip_qbytes_conv2d_a8(_ptr(x), _ptr(xs), _ptr(w), _ptr(s), _ptr(bias), _ptr(y), B, C, H, W, OC, KH, KW, OH, OW,
+                                                     stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], _dt(x), _dt(w), _dt(y),
+                                                     _ptr(ws), ws_bytes, stream)
+        self._check(st, "qbytes_conv2d_a8")
         return y
 
     # -- quanto::qbits_conv2d (implicit GEMM, int4 dequantized while staged) -----------------------------------
@@ -669,7 +728,7 @@ class QuantoHipExtension(NativeLibrary):
             "quanto_hip",
             root_dir=csrc,
             lib_path=os.path.join(_PKG_DIR, "lib", "libquanto_hip.so"),
-            sources=["c_api.hip", "unpack.hip", "naive_mm.hip", "qbits_gemv.hip", "qbytes_gemv.hip", "qmm_mfma.hip", "qconv_mfma.hip", "qconv_depthwise.hip", "qmm_mfma_large.hip", "qmm_large_common.h", "qbits_skinny.hip", "qbits_mmv.hip", "qbits_mfma_fused.hip", "qbits_a8_fused.hip", "qbits_mfma_large.hip", "qbytes_skinny.hip", "qmm_native8.hip", "qmm_f32.hip", "quantize.hip",
+            sources=["c_api.hip", "unpack.hip", "naive_mm.hip", "qbits_gemv.hip", "qbytes_gemv.hip", "qmm_mfma.hip", "qconv_mfma.hip", "qconv_a8.hip", "qconv_depthwise.hip", "qmm_mfma_large.hip", "qmm_large_common.h", "qbits_skinny.hip", "qbits_mmv.hip", "qbits_mfma_fused.hip", "qbits_a8_fused.hip", "qbits_mfma_large.hip", "qbytes_skinny.hip", "qmm_native8.hip", "qmm_f32.hip", "quantize.hip",
                      "qh_common.h", "qh_mfma.h", os.path.join("..", "..", "include", "quanto_hip.h")],
         )
         self._bindings = None

@@ -163,6 +163,29 @@ _register("qbytes_conv2d", "(Tensor input, Tensor weight, Tensor scales, Tensor?
           qbytes_conv2d_hip, default=qbytes_conv2d_default)
 
 
+def qbytes_conv2d_a8_default(input, input_scale, weight, weight_scale, bias, stride, padding, dilation):
+    """What the reference computes for F.conv2d(ActivationQBytesTensor, WeightQBytesTensor) (qfallback): both dequantized, float convolution in the
+    weight scale's dtype."""
+    dt = weight_scale.dtype
+    x = input.to(dt) * input_scale.to(dt)
+    w = weight.to(dt) * weight_scale.reshape(-1, 1, 1, 1).to(dt)
+    return torch.nn.functional.conv2d(x, w, None if bias is None else bias.to(dt), tuple(stride), tuple(padding), tuple(dilation), 1)
+
+
+def qbytes_conv2d_a8_hip(input, input_scale, weight, weight_scale, bias, stride, padding, dilation):
+    lib = quanto_hip.lib
+    stride, padding, dilation = tuple(stride), tuple(padding), tuple(dilation)
+    if input_scale.numel() == 1 and lib.qbytes_conv2d_a8_supported(input, weight, weight_scale.dtype, stride, padding, dilation):
+        return lib.qbytes_conv2d_a8(input, input_scale, weight, weight_scale, bias, stride, padding, dilation)
+    return qbytes_conv2d_a8_default(input, input_scale, weight, weight_scale, bias, stride, padding, dilation)
+
+
+# new op: dense convolution of quantized activation codes with an 8-bit weight on the 8-bit matrix instructions (csrc/qconv_a8.hip): no im2col, no
+# dequantized activation or weight
+_register("qbytes_conv2d_a8", "(Tensor input, Tensor input_scale, Tensor weight, Tensor weight_scale, Tensor? bias, int[] stride, int[] padding, "
+          "int[] dilation) -> Tensor", qbytes_conv2d_a8_hip, default=qbytes_conv2d_a8_default)
+
+
 # ------------------------------------------------------------------------------------------------
 # quanto::quantize_symmetric / quantize_affine (quantize-time, plain torch on every device)
 # ------------------------------------------------------------------------------------------------

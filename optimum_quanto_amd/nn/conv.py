@@ -6,6 +6,13 @@ tensors intercept ``F.conv2d`` (tensor/weights.py, ``conv2d_as_gemm``): on a ROC
 convolution is lowered to im2col + the same fused ``quanto::qbytes_mm`` / ``quanto::qbits_mm`` kernels that serve QLinear -
 the [N, C, kh, kw] weight *is* the [N, C*kh*kw] GEMM operand, byte for byte, in both storage formats.  Everything else
 (grouped convolutions, CPU tensors) keeps the reference behaviour.
+
+QConv2d with quantized activations: when the input reaching ``F.conv2d`` is an ``ActivationQBytesTensor`` (per-tensor scale) and the weight
+is int8 / e4m3fn / e5m2, a dense convolution on a ROCm device runs ``quanto::qbytes_conv2d_a8`` (csrc/qconv_a8.hip): the stored 1-byte codes of
+both go to the 8-bit matrix instructions, gathered inside the kernel - no dequantized activation, no im2col - with the W8A8 QLinear arithmetic
+(integer / fp8 products scaled by ``input_scale * weight_scale``).  Served pairs: int8 x int8, fp8 x fp8 and fp8 x int8.  Int8 activations
+with fp8 weights, e4m3fnuz, int4 / int2 weights, grouped convolutions, fp16 outputs with e5m2 activations and calls that want a gradient
+keep the dequantizing route.
 """
 from typing import Optional
 

@@ -102,6 +102,29 @@ def _implicit_conv2d(input, weight, scale, bias, stride, padding, dilation, grou
     return torch.ops.quanto.qbytes_conv2d(input, weight._data, scale, bias, pair(stride), pair(padding), pair(dilation))
 
 
+def _implicit_conv2d_a8(input, weight, bias, stride, padding, dilation, groups):
+    """``quanto::qbytes_conv2d_a8`` - quantized activation codes x 8-bit weight codes on the 8-bit matrix instructions, im2col inside the kernel's
+    staging loads, no dequantized activation - when the call is eligible: a per-tensor quantized 4-D input (QBytesTensor) on a ROCm device, dense
+    (groups = 1), no gradient wanted, a served (activation, weight) format pair (int8 x int8, fp8 x fp8, fp8 x int8).  None otherwise: the caller
+    keeps today's route (dequantize + im2col + GEMM, or the reference behaviour)."""
+    from ..library.hip import quanto_hip
+
+    if groups != 1 or isinstance(padding, str) or not isinstance(input, QBytesTensor) or input.dim() != 4 or input.device.type != "cuda":
+        return None
+    if input.axis is not None or input._scale.numel() != 1 or weight.dim() != 4:
+        return None
+    # the op's scale is the product of both scales rounded to the output dtype (the W8A8 QLinear contract); an e5m2 activation scale (absmax / 57344)
+    # times a weight scale lies below fp16's normal range (~5e-8 against 6.1e-5) and would lose all or most of its bits: that pair keeps dequantizing
+    if input._data.dtype == torch.float8_e5m2 and weight._scale.dtype == torch.float16:
+        return None
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, weight, bias)):
+        return None
+    stride, padding, dilation = _pair(stride), _pair(padding), _pair(dilation)
+    if not quanto_hip.lib.qbytes_conv2d_a8_supported(input._data, weight._data, weight._scale.dtype, stride, padding, dilation):
+        return None
+    return torch.ops.quanto.qbytes_conv2d_a8(input._data, input._scale, weight._data, weight._scale, bias, stride, padding, dilation)
+
+
 def _implicit_conv2d_qbits(input, weight, bias, stride, padding, dilation, groups):
     """``quanto::qbits_conv2d`` - the same implicit GEMM for a packed int4 weight, dequantized with the reference's roundings while it is staged
     (r4) - under the conditions of _implicit_conv2d; None otherwise (im2col + qbits_mm, or the reference behaviour)."""
@@ -257,6 +280,9 @@ class WeightQBytesTensor(QBytesTensor):
                 if not isinstance(weight, WeightQBytesTensor) or weight.axis not in (0, None):
                     return None
                 n = weight.shape[0]
+                a8 = _implicit_conv2d_a8(input, weight, bias, stride, padding, dilation, groups)
+                if a8 is not None:
+                    return a8
                 scale = weight._scale.reshape(-1, 1).expand(n, 1).contiguous()  # per-channel [N,1,1,1] or per-tensor
                 implicit = _implicit_conv2d(input, weight, scale, bias, stride, padding, dilation, groups)
                 if implicit is not None:
