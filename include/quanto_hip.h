@@ -72,10 +72,11 @@ typedef enum {
                                          weight), 256 x 256 tiles, no workspace, no dense weight in memory */
 } quanto_hip_kernel;
 
-/* Split-K workspaces (SKINNY and MFMA_LARGE kernels) all share ONE layout: the first QUANTO_HIP_WS_COUNTER_BYTES bytes are
- * arrival counters - zero on entry, restored to zero by the kernel - and the fp32 partial sums start right behind them,
- * whatever the problem size.  A buffer whose counter region was zeroed once can therefore serve any sequence of calls on one
- * stream; a kernel never splits a problem that needs more counters than the region holds. */
+/* Split-K workspaces (SKINNY, MFMA_LARGE, MFMA_FUSED4 and NATIVE8 kernels, quanto_hip_qbits_mm_a8) all share ONE layout:
+ * the first QUANTO_HIP_WS_COUNTER_BYTES bytes are arrival counters - zero on entry, restored to zero by the kernel - and the
+ * partial sums start right behind them, whatever the problem size.  A buffer whose counter region was zeroed once can
+ * therefore serve any sequence of calls on one stream; a kernel never splits a problem that needs more counters than the
+ * region holds. */
 #define QUANTO_HIP_WS_COUNTER_BYTES 4096
 
 #define QUANTO_HIP_MAX_MULTI 4           /* Linears per quanto_hip_qbits_mm_multi call                        */

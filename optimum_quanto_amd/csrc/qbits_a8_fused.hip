@@ -331,45 +331,13 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the re-requested last tile: nothing may land in LDS after the kernel moved on
 
-  // ---- split-K: the protocol of qbits_mfma_fused.hip / qbits_skinny.hip (write-through partial tiles, arrival counter, last arriver adds in split order) ----
+  // ---- split-K: the tail of qh_mfma.h (write-through partial tiles, arrival counter, last arriver adds in split order) ----
   if (S > 1) {
     const int tile_id = blockIdx.y * gridDim.x + blockIdx.x;
-    float* mine = a.partials + ((size_t)(tile_id * S + sp) * MI * (WAVES * 64) + tid) * 4;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-      asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(mine + i * (WAVES * 64 * 4)), "v"(acc[i]) : "memory");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
     int* flag = reinterpret_cast<int*>(smem);
-    if (tid == 0) *flag = __hip_atomic_fetch_add(a.counters + tile_id, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __syncthreads();
+    QH_SPLITK_ARRIVE(MI, WAVES * 64, a.partials, tile_id * S + sp, acc, a.counters + tile_id, flag, tid, (void)0, (void)0);
     if (*flag != S - 1) return;
-    if (tid == 0) __hip_atomic_store(a.counters + tile_id, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#pragma unroll
-    for (int i = 0; i < MI; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    constexpr int QB = BM == 64 ? 4 : 2;
-    for (int q0 = 0; q0 < S; q0 += QB) {
-      f32x4 v[QB][MI];
-#pragma unroll
-      for (int j = 0; j < QB; ++j) {
-        const int q = q0 + j < S ? q0 + j : S - 1;
-        const float* theirs = a.partials + ((size_t)(tile_id * S + q) * MI * (WAVES * 64) + tid) * 4;
-#pragma unroll
-        for (int e = 0; e < MI; ++e) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(v[j][e]) : "v"(theirs + e * (WAVES * 64 * 4)) : "memory");
-      }
-#pragma unroll
-      for (int j = 0; j < QB; ++j)
-#pragma unroll
-        for (int e = 0; e < MI; ++e) asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[j][e])::"memory");
-#pragma unroll
-      for (int j = 0; j < QB; ++j)
-        if (q0 + j < S) {
-#pragma unroll
-          for (int e = 0; e < MI; ++e)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[e][r] += v[j][e][r];
-        }
-    }
+    QH_SPLITK_SUM(MI, WAVES * 64, (BM == 64 ? 4 : 2), MI, a.partials, tile_id, S, acc, a.counters + tile_id, tid, (void)0);
   }
 
   // ---- epilogue: x activation scale, (+ bias), 4 consecutive features of one token per fragment: 8-byte stores ----
@@ -434,7 +402,7 @@ inline Plan make_plan(int64_t M, int64_t N, int G, int bits) {
       const int nk = G / S;
       if (fs > 0 ? (S != fs) : (S > 1 && nk < 4)) continue;
       if (lds_bytes(nk, bm, bits) > 160 * 1024) continue;
-      if (S > 1 && (size_t)tiles * 4 > QUANTO_HIP_WS_COUNTER_BYTES) continue;
+      if (S > 1 && !ws_counters_fit(tiles)) continue;
       const float us = model_us(tiles, nk, bm, S);
       if (best.bm == 0 || us < best.us * 0.97f) best = Plan{bm, S, us};
     }
@@ -496,14 +464,14 @@ int qbits_mm_a8(const void* act, const void* act_scale, const uint8_t* packed, c
   if (!qbits_a8_supported(M, g, a_dtype, dtype)) return QUANTO_HIP_ENOTSUP;
   if ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
   a8::Plan p = a8::make_plan(M, g.N, (int)g.G, g.bits);
-  if (p.S > 1 && (!workspace || workspace_bytes < qbits_a8_workspace(M, g) || reinterpret_cast<uintptr_t>(workspace) % 16)) {
+  if (p.S > 1 && !ws_holds(workspace, workspace_bytes, qbits_a8_workspace(M, g))) {
     p.S = 1;  // no scratch: unsplit, with whichever token tile lets the whole scale table fit
     if (a8::lds_bytes((int)g.G, p.bm, g.bits) > 160 * 1024) p.bm = 64;
     if (a8::lds_bytes((int)g.G, p.bm, g.bits) > 160 * 1024) return QUANTO_HIP_EINVAL;
   }
   const a8::Args a{reinterpret_cast<const uint8_t*>(act), act_scale, packed, scale, shift, bias, y, (int)M, (int)g.N, (int)g.K, (int)g.G, p.S,
                    reinterpret_cast<int*>(workspace),
-                   p.S > 1 ? reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + QUANTO_HIP_WS_COUNTER_BYTES) : nullptr,
+                   p.S > 1 ? ws_partials(workspace) : nullptr,
                    env_int("QUANTO_HIP_A8_ABLATE", 0)};
   return dtype == QUANTO_HIP_BF16 ? a8::launch_bits<QUANTO_HIP_BF16>(a, g.bits, a_dtype, p.bm, int_shift, stream)
                                   : a8::launch_bits<QUANTO_HIP_F16>(a, g.bits, a_dtype, p.bm, int_shift, stream);

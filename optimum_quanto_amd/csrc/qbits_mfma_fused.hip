@@ -24,7 +24,7 @@
 // chunk ^ (row & 7)).  Scales / shifts of the workgroup's 128 features for its groups are parked in LDS once (16-byte loads, issued
 // in front of the first tiles' DMA).  Split-K where the scale table does not fit (K = 14336 with 128-token tiles) and, with 64-token
 // tiles, to fill the chip: fp32 partial tiles through the workspace, write-through stores, arrival counter, the last workgroup adds
-// them in split order - the protocol of qbits_skinny.hip.
+// them in split order - the split-K tail of qh_mfma.h.
 #include <type_traits>
 
 #include "qh_mfma.h"
@@ -359,50 +359,13 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the re-requested tiles past the end: nothing may land in LDS after the kernel moved on
 
-  // ---- split-K: fp32 partial tiles through the workspace, the last workgroup of a tile adds them in split order (qbits_skinny.hip) ----
+  // ---- split-K: fp32 partial tiles through the workspace, the last workgroup of a tile adds them in split order (qh_mfma.h) ----
   if (S > 1) {
     const int tile_id = blockIdx.y * gridDim.x + blockIdx.x;
-    // fragment-major: lane-major (64 B per lane) made every store instruction write a quarter of each line it touched, and partial
-    // lines are what the write-through path is slow at
-    float* mine = a.partials + ((size_t)(tile_id * S + sp) * MI * (WAVES * 64) + tid) * 4;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)  // s_nop: gfx9 hazard "VMEM store of > 64 bits, then VALU write of its data VGPRs"
-      asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(mine + i * (WAVES * 64 * 4)), "v"(acc[i]) : "memory");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
     int* flag = reinterpret_cast<int*>(smem);
-    if (tid == 0) *flag = __hip_atomic_fetch_add(a.counters + tile_id, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __syncthreads();
+    QH_SPLITK_ARRIVE(MI, WAVES * 64, a.partials, tile_id * S + sp, acc, a.counters + tile_id, flag, tid, (void)0, (void)0);
     if (*flag != S - 1) return;
-    if (tid == 0) __hip_atomic_store(a.counters + tile_id, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // leave the workspace as found
-#pragma unroll
-    for (int i = 0; i < MI; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // fixed order: the result does not depend on which workgroup arrived last.  The loads of up to four splits are in flight
-    // together: a system-coherent load is a ~2 us round trip, and r2's loop paid one per split ((128,4096,4096) with 4 splits:
-    // ~12 of its 21.7 us were this tail)
-    constexpr int QB = BM == 64 ? 4 : 2;  // splits per batch: QB * MI float4 registers
-    for (int q0 = 0; q0 < S; q0 += QB) {
-      f32x4 v[QB][MI];
-#pragma unroll
-      for (int j = 0; j < QB; ++j) {
-        const int q = q0 + j < S ? q0 + j : S - 1;
-        const float* theirs = a.partials + ((size_t)(tile_id * S + q) * MI * (WAVES * 64) + tid) * 4;
-#pragma unroll
-        for (int e = 0; e < MI; ++e) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(v[j][e]) : "v"(theirs + e * (WAVES * 64 * 4)) : "memory");
-      }
-#pragma unroll
-      for (int j = 0; j < QB; ++j)
-#pragma unroll
-        for (int e = 0; e < MI; ++e) asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[j][e])::"memory");  // ties the uses below to the wait
-#pragma unroll
-      for (int j = 0; j < QB; ++j)
-        if (q0 + j < S) {
-#pragma unroll
-          for (int e = 0; e < MI; ++e)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[e][r] += v[j][e][r];
-        }
-    }
+    QH_SPLITK_SUM(MI, WAVES * 64, (BM == 64 ? 4 : 2), MI, a.partials, tile_id, S, acc, a.counters + tile_id, tid, (void)0);  // QB * MI float4 registers
   }
 
   // ---- epilogue: 4 consecutive features of one token per fragment: 8-byte stores -------------------------------------------------------
@@ -471,7 +434,7 @@ inline Plan make_plan(int64_t M, int64_t N, int G) {
       const int nk = G / S;
       if (fs > 0 ? (S != fs) : (S > 1 && nk < 4)) continue;
       if (lds_bytes(nk, bm) > 160 * 1024) continue;
-      if (S > 1 && (size_t)tiles * 4 > QUANTO_HIP_WS_COUNTER_BYTES) continue;
+      if (S > 1 && !ws_counters_fit(tiles)) continue;
       const float us = model_us(tiles, nk, bm, S);
       if (best.bm == 0 || us < best.us * 0.97f) best = Plan{bm, S, us};  // ties: the smaller tile, fewer splits
     }
@@ -526,7 +489,7 @@ int qbits_mm_mfma_fused(const void* x, const uint8_t* packed, const void* scale,
   if (!qbits_mfma_fused_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
   fused4::Plan p = fused4::make_plan(M, g.N, (int)g.G);
-  if (p.S > 1 && (!workspace || workspace_bytes < qbits_mfma_fused_workspace(M, g) || reinterpret_cast<uintptr_t>(workspace) % 16)) {
+  if (p.S > 1 && !ws_holds(workspace, workspace_bytes, qbits_mfma_fused_workspace(M, g))) {
     // no scratch: unsplit, with whichever token tile lets the whole scale table fit
     p.S = 1;
     if (fused4::lds_bytes((int)g.G, p.bm) > 160 * 1024) p.bm = 64;
@@ -534,7 +497,7 @@ int qbits_mm_mfma_fused(const void* x, const uint8_t* packed, const void* scale,
   }
   const int bm = p.bm, S = p.S;
   fused4::Args a{x, packed, scale, shift, bias, y, (int)M, (int)g.N, (int)g.K, (int)g.G, S, reinterpret_cast<int*>(workspace),
-                 S > 1 ? reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + QUANTO_HIP_WS_COUNTER_BYTES) : nullptr,
+                 S > 1 ? ws_partials(workspace) : nullptr,
                  env_int("QUANTO_HIP_FUSED4_ABLATE", 0)};
   if (dtype == QUANTO_HIP_BF16)
     return int_shift ? fused4::launch<QUANTO_HIP_BF16, true>(a, bm, stream) : fused4::launch<QUANTO_HIP_BF16, false>(a, bm, stream);

@@ -391,11 +391,7 @@ __global__ void __launch_bounds__(WAVES * SETS * 64) qbits_skinny_kernel(Args a,
     cur = nxt + 1 == STAGES ? 0 : nxt + 1;
   }
 
-  // ---- split-K: park the partial sums, elect the last block of this feature block, which reduces in split order -------------
-  // The blocks of one feature block may run on different XCDs, whose L2s are not coherent with each other.  An agent-scope
-  // fence would be correct but writes back / invalidates a whole L2 (measured: 23 -> 57 us); instead the few KiB of partials
-  // travel with system-coherent (sc0 sc1) 16-byte stores and loads and the only
-  // ordering needed is "my stores are acknowledged (vmcnt(0)) before my workgroup's arrival is counted".
+  // ---- split-K: park the partial sums, elect the last block of this feature block, which reduces in split order (qh_mfma.h) ----
   if constexpr (SETS == 2) {  // set 0 + set 1 through LDS (the ring is free: every DMA was consumed)
     __syncthreads();
     f32x4* red = reinterpret_cast<f32x4*>(smem);
@@ -417,45 +413,10 @@ __global__ void __launch_bounds__(WAVES * SETS * 64) qbits_skinny_kernel(Args a,
   if (S > 1 && (a.ablate & 1)) {
     if (sp != 0) return;
   } else if (S > 1) {
-    float* mine = a.partials + ((size_t)blockIdx.x * TF * (WAVES * 64) + tid) * 4;
-#pragma unroll
-    for (int tf = 0; tf < TF; ++tf)  // s_nop: gfx9 hazard "VMEM store of > 64 bits, then VALU write of its data VGPRs" - hipcc cannot see into the asm
-      asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(mine + tf * (WAVES * 64 * 4)), "v"(acc[tf]) : "memory");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    probe(21);
-    __syncthreads();
     int* flag = reinterpret_cast<int*>(smem);
-    if (tid == 0) *flag = __hip_atomic_fetch_add(a.counters + fbg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __syncthreads();
-    probe(22);
+    QH_SPLITK_ARRIVE(TF, WAVES * 64, a.partials, blockIdx.x, acc, a.counters + fbg, flag, tid, probe(21), probe(22));
     if (*flag != S - 1) return;
-    if (tid == 0) __hip_atomic_store(a.counters + fbg, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // leave the workspace as found
-#pragma unroll
-    for (int tf = 0; tf < TF; ++tf) acc[tf] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // fixed order: the result does not depend on which block arrived last.  The loads of up to four splits are in flight
-    // together (one fabric round trip per four splits instead of one per split)
-    for (int q0 = 0; q0 < S; q0 += 4) {
-      f32x4 v[4][TF];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int q = q0 + j < S ? q0 + j : S - 1;
-        const float* theirs = a.partials + ((size_t)(fbg * S + q) * TF * (WAVES * 64) + tid) * 4;
-#pragma unroll
-        for (int tf = 0; tf < TF; ++tf) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(v[j][tf]) : "v"(theirs + tf * (WAVES * 64 * 4)) : "memory");
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int tf = 0; tf < TF; ++tf) asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[j][tf])::"memory");  // ties the uses below to the wait
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (q0 + j < S) {
-#pragma unroll
-          for (int tf = 0; tf < TF; ++tf)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[tf][r] += v[j][tf][r];
-        }
-    }
+    QH_SPLITK_SUM(TF, WAVES * 64, 4, TF, a.partials, fbg, S, acc, a.counters + fbg, tid, (void)0);  // four splits' loads in flight together
     probe(23);
   }
 
@@ -621,13 +582,9 @@ static int skinny_split(const PackedGeom& g, int64_t M) {
         break;
       }
   if (forced > 0 && tiles % forced == 0) s = forced;
-  if ((size_t)blocks * 4 > QUANTO_HIP_WS_COUNTER_BYTES) s = 1;  // one counter per feature block
+  if (!ws_counters_fit(blocks)) s = 1;  // one counter per feature block
   return s;
 }
-// The arrival counters of every split-K kernel of the library live in the same fixed-size region at the start of the
-// workspace and the partial sums always start behind it: a buffer that served one problem can serve any other without a
-// later call reading an earlier call's partial sums as counters (the partials are never reset, the counters always are).
-static size_t skinny_counter_bytes(const PackedGeom&) { return QUANTO_HIP_WS_COUNTER_BYTES; }
 
 bool qbits_skinny_supported(int64_t M, const PackedGeom& g, int dtype) {
   const int64_t Mp = M > 64 ? 64 : M;  // rows per pass
@@ -655,7 +612,7 @@ size_t qbits_skinny_workspace(int64_t M, const PackedGeom& g) {
   const int S = skinny_split(g, M);
   if (S == 1) return 0;
   const int tf = M <= 16 ? 1 : (M <= 32 ? 2 : 4);  // M > 64 runs in passes of 64 rows, which reuse the workspace
-  return skinny_counter_bytes(g) + (size_t)(g.N / 16) * S * 64 * tf * 16;
+  return QUANTO_HIP_WS_COUNTER_BYTES + (size_t)(g.N / 16) * S * 64 * tf * 16;
 }
 
 int qbits_mm_skinny(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
@@ -664,7 +621,7 @@ int qbits_mm_skinny(const void* x, const uint8_t* packed, const void* scale, con
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
   // split-K only with a workspace (whose counter words the caller guarantees to be zero); without one: one block per feature block
   int S = skinny_split(g, M > 64 ? 64 : M);
-  if (S > 1 && (!workspace || workspace_bytes < qbits_skinny_workspace(M, g) || reinterpret_cast<uintptr_t>(workspace) % 16)) S = 1;
+  if (S > 1 && !ws_holds(workspace, workspace_bytes, qbits_skinny_workspace(M, g))) S = 1;
   const bool per_channel = g.C == g.K && g.C != 128;
   const size_t esize = 2;  // bf16 / fp16
   for (int64_t m0 = 0; m0 < M; m0 += 64) {  // passes of up to 64 rows (stream-ordered: each pass leaves the counters zero)
@@ -672,7 +629,7 @@ int qbits_mm_skinny(const void* x, const uint8_t* packed, const void* scale, con
     skinny::Args a{reinterpret_cast<const uint8_t*>(x) + (size_t)m0 * g.K * esize, packed, scale, shift, bias,
                    reinterpret_cast<uint8_t*>(y) + (size_t)m0 * g.N * esize, (int)rows, (int)g.N, (int)g.K, (int)g.G, S,
                    reinterpret_cast<int*>(workspace),
-                   S > 1 ? reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + skinny_counter_bytes(g)) : nullptr,
+                   S > 1 ? ws_partials(workspace) : nullptr,
                    per_channel ? 1 : (int)(128 / g.C), per_channel ? 1 : 0, g.bits == 2 ? 4 : 2, (g.C == 96 && !per_channel) ? 96 : 128,
                    // later passes of a multi-pass call re-read the weights from the Infinity Cache: keep them cacheable there
                    env_int("QUANTO_HIP_SKINNY_NT", M <= 64 ? 1 : 0), env_int("QUANTO_HIP_SKINNY_ABLATE", 0),
@@ -730,10 +687,10 @@ int qbits_mm_skinny_multi(const void* x, int nseg, const uint8_t* const* packed,
   }
   if (align % 16) return QUANTO_HIP_EALIGN;
   int S = skinny_split(g, M);
-  if (S > 1 && (!workspace || workspace_bytes < qbits_skinny_workspace(M, g) || reinterpret_cast<uintptr_t>(workspace) % 16)) S = 1;
+  if (S > 1 && !ws_holds(workspace, workspace_bytes, qbits_skinny_workspace(M, g))) S = 1;
   skinny::Args a{x, packed[0], scale[0], shift[0], bias ? bias[0] : nullptr, y[0], (int)M, (int)N[0], (int)K, (int)g.G, S,
                  reinterpret_cast<int*>(workspace),
-                 S > 1 ? reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + skinny_counter_bytes(g)) : nullptr, 1, 0, 2, 128,
+                 S > 1 ? ws_partials(workspace) : nullptr, 1, 0, 2, 128,
                  env_int("QUANTO_HIP_SKINNY_NT", 1), 0, nullptr};
   if (dtype == QUANTO_HIP_BF16)
     return int_shift ? skinny::launch_tf<QUANTO_HIP_BF16, true>(a, stream, &segs, fb) : skinny::launch_tf<QUANTO_HIP_BF16, false>(a, stream, &segs, fb);

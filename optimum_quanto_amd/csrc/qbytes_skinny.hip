@@ -11,7 +11,7 @@
 //     the token's 256-byte row) - an MFMA is invariant under a k permutation applied to both operands;
 //   * the per-channel scale (and bias) is applied once, to the fp32 accumulator, in the epilogue - no per-group work;
 //   * K is split across workgroups when N alone cannot occupy the chip, and M > 64 runs in passes of 64 rows: same scheme,
-//     same workspace contract (zeroed arrival counters, system-coherent partial sums) as qbits_skinny.hip.
+//     same split-K tail and workspace contract (zeroed arrival counters, system-coherent partial sums: qh_mfma.h).
 #include <cstdlib>
 
 #include "qh_mfma.h"
@@ -206,33 +206,12 @@ __global__ void __launch_bounds__(256) qbytes_skinny_kernel(Args a, const Segs s
     cur = nxt + 1 == STAGES ? 0 : nxt + 1;
   }
 
-  // ---- split-K reduction (see qbits_skinny.hip for the coherence argument) -----------------------------------------------------
+  // ---- split-K: the last block of a feature block to arrive adds the partial sums in split order, one split per wait (qh_mfma.h) ----
   if (S > 1) {
-    float* mine = a.partials + ((size_t)blockIdx.x * TF * 256 + tid) * 4;  // fragment-major: whole lines per store instruction
-#pragma unroll
-    for (int tf = 0; tf < TF; ++tf)
-      asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(mine + tf * (256 * 4)), "v"(acc[tf]) : "memory");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
     int* flag = reinterpret_cast<int*>(smem);
-    if (tid == 0) *flag = __hip_atomic_fetch_add(a.counters + fbg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __syncthreads();
+    QH_SPLITK_ARRIVE(TF, 256, a.partials, blockIdx.x, acc, a.counters + fbg, flag, tid, (void)0, (void)0);
     if (*flag != S - 1) return;
-    if (tid == 0) __hip_atomic_store(a.counters + fbg, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#pragma unroll
-    for (int tf = 0; tf < TF; ++tf) acc[tf] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int q = 0; q < S; ++q) {
-      const float* theirs = a.partials + ((size_t)(fbg * S + q) * TF * 256 + tid) * 4;
-      f32x4 v[TF];
-#pragma unroll
-      for (int tf = 0; tf < TF; ++tf) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(v[tf]) : "v"(theirs + tf * (256 * 4)) : "memory");
-#pragma unroll
-      for (int tf = 0; tf < TF; ++tf) asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[tf])::"memory");
-#pragma unroll
-      for (int tf = 0; tf < TF; ++tf)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[tf][r] += v[tf][r];
-    }
+    QH_SPLITK_SUM(TF, 256, 1, TF, a.partials, fbg, S, acc, a.counters + fbg, tid, (void)0);
   }
 
   // ---- epilogue: per-channel scale on the accumulator, optional bias; a lane holds 4 consecutive features of one token ----------
@@ -310,11 +289,9 @@ static int skinny8_split(int64_t N, int64_t K) {
   int s = 1;  // same rule as qbits_skinny.hip: 250-500 blocks, at least 8 tiles per block
   while (s < 8 && blocks * s * 2 <= 512 && G % (s * 2) == 0 && G / (s * 2) >= 8) s *= 2;
   if (forced > 0 && G % forced == 0) s = forced;
-  if ((size_t)((N + 63) / 64) * 4 > QUANTO_HIP_WS_COUNTER_BYTES) s = 1;  // one counter per feature block of 64
+  if (!ws_counters_fit((N + 63) / 64)) s = 1;  // one counter per feature block of 64
   return s;
 }
-// fixed-size counter region shared by all split-K kernels of the library (see qbits_skinny.hip)
-static size_t skinny8_counter_bytes(int64_t) { return QUANTO_HIP_WS_COUNTER_BYTES; }
 
 bool qbytes_skinny_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
   const bool bd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2 || b_dtype == QUANTO_HIP_F8_E4M3FNUZ;
@@ -327,7 +304,7 @@ size_t qbytes_skinny_workspace(int64_t M, int64_t N, int64_t K) {
   const int S = skinny8_split(N, K);
   if (S == 1) return 0;
   const int tf = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-  return skinny8_counter_bytes(N) + (size_t)((N + 63) / 64) * S * 256 * tf * 16;
+  return QUANTO_HIP_WS_COUNTER_BYTES + (size_t)((N + 63) / 64) * S * 256 * tf * 16;
 }
 
 int qbytes_mm_skinny(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
@@ -335,12 +312,12 @@ int qbytes_mm_skinny(const void* x, const void* w, const void* s, const void* bi
   if (!qbytes_skinny_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) % 16) return QUANTO_HIP_EALIGN;
   int S = skinny8_split(N, K);
-  if (S > 1 && (!workspace || workspace_bytes < qbytes_skinny_workspace(M, N, K) || reinterpret_cast<uintptr_t>(workspace) % 16)) S = 1;
+  if (S > 1 && !ws_holds(workspace, workspace_bytes, qbytes_skinny_workspace(M, N, K))) S = 1;
   for (int64_t m0 = 0; m0 < M; m0 += 64) {
     const int64_t rows = M - m0 < 64 ? M - m0 : 64;
     skinny8::Args a{reinterpret_cast<const uint8_t*>(x) + (size_t)m0 * K * 2, reinterpret_cast<const uint8_t*>(w), s, bias,
                     reinterpret_cast<uint8_t*>(y) + (size_t)m0 * N * 2, (int)rows, (int)N, (int)K, S, reinterpret_cast<int*>(workspace),
-                    S > 1 ? reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + skinny8_counter_bytes(N)) : nullptr,
+                    S > 1 ? ws_partials(workspace) : nullptr,
                     env_int("QUANTO_HIP_SKINNY_NT", M <= 64 ? 1 : 0)};
     int r;
 #define QH_FMT(DT)                                                                              \
@@ -398,9 +375,9 @@ int qbytes_mm_skinny_multi(const void* x, int nseg, const void* const* w, const 
   }
   if (align % 16) return QUANTO_HIP_EALIGN;
   int S = skinny8_split(total, K);
-  if (S > 1 && (!workspace || workspace_bytes < qbytes_skinny_workspace(M, total, K) || reinterpret_cast<uintptr_t>(workspace) % 16)) S = 1;
+  if (S > 1 && !ws_holds(workspace, workspace_bytes, qbytes_skinny_workspace(M, total, K))) S = 1;
   skinny8::Args a{x, segs.w[0], s[0], segs.bias[0], y[0], (int)M, (int)N[0], (int)K, S, reinterpret_cast<int*>(workspace),
-                  S > 1 ? reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + skinny8_counter_bytes(total)) : nullptr,
+                  S > 1 ? ws_partials(workspace) : nullptr,
                   env_int("QUANTO_HIP_SKINNY_NT", 1)};
   int r;
 #define QH_FMT(DT)                                                                                        \

@@ -28,6 +28,7 @@
 // splits in split order (deterministic; int32: bit-identical to the unsplit result) and runs the epilogue.
 #include <type_traits>
 
+#include "qh_conv.h"
 #include "qh_mfma.h"
 
 namespace qh {
@@ -344,41 +345,9 @@ __global__ void __launch_bounds__(64) qconv2d_a8_reduce_kernel(const Args a) {
   using AV = typename std::conditional<INT, i32x4, f32x4>::type;
   const int lane = threadIdx.x, wave = blockIdx.z, S = a.S;
   AV acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = AV{0, 0, 0, 0};
-  const AV* base = reinterpret_cast<const AV*>(a.partials) + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (8 * 8 * 64) + (wave * 8) * 64 + lane;
-  const size_t split_stride = (size_t)gridDim.y * gridDim.x * (8 * 8 * 64);
-  for (int sp0 = 0; sp0 < S; sp0 += 4) {
-    AV v[4][8];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int sp = sp0 + u < S ? sp0 + u : S - 1;
-#pragma unroll
-      for (int f = 0; f < 8; ++f) v[u][f] = base[sp * split_stride + f * 64];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (sp0 + u < S) {
-#pragma unroll
-        for (int f = 0; f < 8; ++f) acc[f >> 1][f & 1] += v[u][f];
-      }
-  }
+  QH_CONV_SPLIT_SUM(AV, a.partials, S, lane, wave, acc);
   store_tile(a, acc, blockIdx.y * BM, blockIdx.x, wave >> 2, wave & 3, lane);
 }
-
-// K split: qconv_mfma.hip's rule on this kernel's 128-deep K-tiles - split until the grid reaches ~2 workgroups per CU, at least 4 K-tiles per split
-static int pick_split(int64_t M, int64_t N, int64_t K) {
-  const int forced = env_int("QUANTO_HIP_CONV_SPLIT", 0);  // experiments
-  const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN), nk = (K + BK - 1) / BK;
-  if (forced > 0) return (int)(forced <= nk ? forced : nk);
-  if (tiles > 128) return tiles <= 256 && nk >= 32 ? 2 : 1;
-  int s = 1;
-  while (tiles * (s + 1) <= 512 && nk / (s + 1) >= 4 && s < 64) ++s;
-  return s;
-}
-static size_t split_workspace(int64_t M, int64_t N, int S) { return S <= 1 ? 0 : (size_t)S * ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * (BM * BN * 4); }
 
 // conv::geometry_ok of qconv_mfma.hip (one validity bit per tap, 31-bit offsets, grid.y), with one-byte activations
 static bool geometry_ok(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW) {
@@ -417,7 +386,7 @@ bool qbytes_conv2d_a8_geometry_ok(int64_t B, int64_t cin, int64_t H, int64_t W, 
   return conv8::geometry_ok(B, cin, H, W, OC, KH, KW, OH, OW);
 }
 
-size_t conv2d_a8_workspace(int64_t M, int64_t N, int64_t K) { return conv8::split_workspace(M, N, conv8::pick_split(M, N, K)); }
+size_t conv2d_a8_workspace(int64_t M, int64_t N, int64_t K) { return conv_split_workspace<conv8::BM, conv8::BN>(M, N, conv_pick_split<conv8::BK, conv8::BM, conv8::BN>(M, N, K)); }
 
 // *kind: the conv8::Kind that ran.  The caller has validated the arguments and the format (qbytes_conv2d_a8_kind >= 0, geometry_ok).
 int qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, int64_t B, int64_t cin, int64_t H,
@@ -429,8 +398,8 @@ int qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const vo
   Args a{reinterpret_cast<const uint8_t*>(x), a_scale, reinterpret_cast<const uint8_t*>(w), w_scale, bias, y, (int)(B * OH * OW), (int)OC,
          (int)(cin * KH * KW), (int)cin, (int)H, (int)W, (int)KH, (int)KW, (int)OH, (int)OW, sh, sw, ph, pw, dh, dw, out_dtype, 1, nullptr,
          div_magic((int)(KH * KW)), div_magic((int)KW)};
-  int S = pick_split(a.M, a.N, a.K);
-  if (S > 1 && (!workspace || workspace_bytes < split_workspace(a.M, a.N, S) || reinterpret_cast<uintptr_t>(workspace) % 16)) S = 1;
+  int S = conv_pick_split<BK, BM, BN>(a.M, a.N, a.K);
+  if (S > 1 && !ws_holds(workspace, workspace_bytes, conv_split_workspace<BM, BN>(a.M, a.N, S))) S = 1;
   a.S = S;
   a.partials = workspace;
   const int ntiles = (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;

@@ -29,6 +29,7 @@
 // gather, pixel pairs, magic-number table, 8-byte epilogue stores (r5): ~1.2 us per K-tile; DESIGN.md 4.8.
 #include <type_traits>
 
+#include "qh_conv.h"
 #include "qh_mfma.h"
 
 #ifndef QH_CONV_ABLATE
@@ -937,48 +938,9 @@ template <int DT, int PL>
 __global__ void __launch_bounds__(64) qconv2d_reduce_kernel(const Args a) {
   const int lane = threadIdx.x, wave = blockIdx.z, S = a.S;
   f32x4 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const f32x4* base = reinterpret_cast<const f32x4*>(a.partials) + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (8 * 8 * 64) + (wave * 8) * 64 + lane;
-  const size_t split_stride = (size_t)gridDim.y * gridDim.x * (8 * 8 * 64);
-  for (int sp0 = 0; sp0 < S; sp0 += 4) {
-    f32x4 v[4][8];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int sp = sp0 + u < S ? sp0 + u : S - 1;
-#pragma unroll
-      for (int f = 0; f < 8; ++f) v[u][f] = base[sp * split_stride + f * 64];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (sp0 + u < S) {
-#pragma unroll
-        for (int f = 0; f < 8; ++f)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[f >> 1][f & 1][r] += v[u][f][r];
-      }
-  }
+  QH_CONV_SPLIT_SUM(f32x4, a.partials, S, lane, wave, acc);
   store_tile<DT, PL>(a, acc, blockIdx.y * BM, blockIdx.x, wave >> 2, wave & 3, lane);
 }
-
-// K split: the tile kernel is bound by its gather per K-tile (~1.9 us per workgroup and K-tile whatever M is), so what matters is how many
-// workgroups run at once: split until the grid reaches ~2 workgroups per CU, keeping at least 4 K-tiles per split (r5, after the gather and the
-// epilogue got cheaper: profiles/r05_qconv2d_split_sweep.jsonl - 3 per split over-split 26-49-tile grids by 10-14 %).  1 = no split (and no workspace).
-static int pick_split(int64_t M, int64_t N, int64_t K) {
-  const int forced = env_int("QUANTO_HIP_CONV_SPLIT", 0);  // experiments
-  const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN), nk = (K + BK - 1) / BK;
-  if (forced > 0) return (int)(forced <= nk ? forced : nk);
-  // measured (profiles/r04_qconv2d_forced_split.jsonl): at 196 tiles a split of 2 costs more in partial sums than the second workgroup per CU
-  // brings while K is short (9 K-tiles 23.9 -> 31.9 us, 18 K-tiles 43.0 -> 44.7) and pays from ~32 K-tiles on (192 tiles x 45: 81.6 -> 72.9,
-  // 256 tiles x 49: 86.8 -> 84.3)
-  if (tiles > 128) return tiles <= 256 && nk >= 32 ? 2 : 1;
-  int s = 1;
-  while (tiles * (s + 1) <= 512 && nk / (s + 1) >= 4 && s < 64) ++s;
-  return s;
-}
-static size_t split_workspace(int64_t M, int64_t N, int S) { return S <= 1 ? 0 : (size_t)S * ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * (BM * BN * 4); }
 
 // row form: three taps wide, stride 1 / dilation 1 along the width, even OW (QUANTO_HIP_CONV_ROWS=0: the tap gather, 2: global loads - experiments)
 // (pixel pairs need stride 1 and an even OW; anything else three taps wide takes one pixel per thread; QUANTO_HIP_CONV_ROWS=3: one pixel per thread everywhere)
@@ -1021,8 +983,8 @@ template <int DT, int FMT, bool INT_SHIFT, bool WIDE>
 static int launch_w(Args a, void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows) {
   constexpr int PL = planes_of(FMT);
   const int ntiles = PL > 1 ? (a.N / PL + BN / PL - 1) / (BN / PL) : (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;
-  int S = pick_split(a.M, a.N, a.K);
-  if (S > 1 && (!workspace || workspace_bytes < split_workspace(a.M, a.N, S) || reinterpret_cast<uintptr_t>(workspace) % 16)) S = 1;
+  int S = conv_pick_split<BK, BM, BN>(a.M, a.N, a.K);
+  if (S > 1 && !ws_holds(workspace, workspace_bytes, conv_split_workspace<BM, BN>(a.M, a.N, S))) S = 1;
   a.S = S;
   a.partials = reinterpret_cast<float*>(workspace);
   if constexpr (PL == 1 && !WIDE) {
@@ -1063,7 +1025,7 @@ bool qbytes_conv2d_supported(int64_t B, int64_t cin, int64_t H, int64_t W, int64
 }
 
 // scratch bytes the K split of a convolution wants (0: not split); the same for every weight format (128 x 128 tiles either way)
-size_t conv2d_workspace(int64_t M, int64_t N, int64_t K) { return conv::split_workspace(M, N, conv::pick_split(M, N, K)); }
+size_t conv2d_workspace(int64_t M, int64_t N, int64_t K) { return conv_split_workspace<conv::BM, conv::BN>(M, N, conv_pick_split<conv::BK, conv::BM, conv::BN>(M, N, K)); }
 
 // int4 / int2 weights in the row form (r5): the weight is tiny next to the activations and every pixel tile would dequantize all of it again
 // (196 times for (8,128,56,56) -> 128: the sub-byte tap kernel spends a third of its time there) - so it is dequantized ONCE into the caller's
@@ -1082,8 +1044,8 @@ int qdense_conv2d_rows(const void* x, const void* wdense, const void* bias, void
   conv::Args a{x, reinterpret_cast<const uint8_t*>(wdense), nullptr, nullptr, bias, y, (int)(B * OH * OW), (int)OC, (int)(cin * KH * KW), 0, 0,
                (int)cin, (int)H, (int)W, (int)KH, (int)KW, (int)OH, (int)OW, sh, sw, ph, pw, dh, dw, 1, nullptr, conv::div_magic((int)(KH * KW)), conv::div_magic((int)KW), conv::div_magic((int)KH)};
   using namespace conv;
-  int S = pick_split(a.M, a.N, a.K);
-  if (S > 1 && (!workspace || workspace_bytes < split_workspace(a.M, a.N, S) || reinterpret_cast<uintptr_t>(workspace) % 16)) S = 1;
+  int S = conv_pick_split<BK, BM, BN>(a.M, a.N, a.K);
+  if (S > 1 && !ws_holds(workspace, workspace_bytes, conv_split_workspace<BM, BN>(a.M, a.N, S))) S = 1;
   a.S = S;
   a.partials = reinterpret_cast<float*>(workspace);
   const int ntiles = (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;

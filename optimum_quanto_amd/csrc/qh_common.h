@@ -162,6 +162,16 @@ inline void* env_ptr(const char* name) {
   return e ? reinterpret_cast<void*>(strtoull(e, nullptr, 0)) : nullptr;
 }
 
+// ---- split-K workspace: [QUANTO_HIP_WS_COUNTER_BYTES of arrival counters | partial sums] (include/quanto_hip.h) ----------------
+// one counter per tile (feature block) that a workgroup split counts its arrivals on: more tiles than the region holds run unsplit
+inline bool ws_counters_fit(int64_t tiles) { return (size_t)tiles * 4 <= QUANTO_HIP_WS_COUNTER_BYTES; }
+// the partial sums start behind the counter region whatever the problem, so no call reads an earlier call's partials as counters
+inline float* ws_partials(void* workspace) { return reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + QUANTO_HIP_WS_COUNTER_BYTES); }
+// whether the caller's workspace can hold a split that needs `need` bytes (16-byte stores); a kernel without one runs unsplit
+inline bool ws_holds(const void* workspace, size_t workspace_bytes, size_t need) {
+  return workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 16 == 0;
+}
+
 int launch_status();  // hipGetLastError() -> quanto_hip_status (defined in c_api.hip)
 void set_last_kernel(const char* name);
 

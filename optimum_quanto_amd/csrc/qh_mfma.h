@@ -1,5 +1,5 @@
-// Building blocks shared by the MFMA kernels: the 16x16x32 bf16 / fp16 MFMA trait, LDS-DMA issue, the vmcnt ladder and the 8-bit
-// pair converter.
+// Building blocks shared by the MFMA kernels: the 16x16x32 bf16 / fp16 MFMA trait, LDS-DMA issue, the vmcnt ladder, the split-K
+// tail and the 8-bit pair converter.
 #pragma once
 #include "qh_common.h"
 
@@ -90,6 +90,76 @@ __device__ __forceinline__ void wait_vmcnt(int younger_tiles) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
 }
+
+// ---- split-K tail: the last workgroup of a tile to arrive adds the partial sums of all S splits ------------------------------
+// Used by qbits_skinny.hip, qbytes_skinny.hip, qbits_mfma_fused.hip, qbits_a8_fused.hip and qmm_mfma_large.hip:
+//   QH_SPLITK_ARRIVE(...);                   park the partial, count the arrival in the LDS word *flag
+//   if (*flag != S - 1) return;              every workgroup but the tile's last arriver is done
+//   QH_SPLITK_SUM(...);                      reset the counter, acc = the S partials added in split order
+// Workspace (include/quanto_hip.h): one arrival counter per tile, zero on entry and reset by the last arriver; the partial of split sp of
+// tile t is slot t * S + sp: NF fragments x NT threads of float4, fragment-major (every store / load instruction covers whole lines:
+// partial lines are what the write-through path is slow at).
+// Coherence: the workgroups of one tile may run on different XCDs, whose L2s are not coherent with each other.  An agent-scope fence
+// would be correct but writes back / invalidates a whole L2 (measured: 23 -> 57 us); instead the few KiB of partials travel with
+// system-coherent (sc0 sc1) 16-byte stores and loads, and the only ordering needed is "my stores are acknowledged (vmcnt(0)) before
+// my workgroup's arrival is counted".
+// Macros, not functions: hipcc optimizes a called function on its own before it inlines it, and the tail as two __forceinline__
+// templates changed the loops and the registers of every kernel that used it (qbits_skinny 134 -> 132 VGPRs, the convolution reduce
+// 132 -> 110); pasted in place, each kernel compiles to the same instructions as with its own copy.
+//
+// PARTIALS: float* behind the counters; SLOT: this workgroup's slot; ACC: the accumulator as f32x4*; COUNTER: int* of the tile's counter;
+// FLAG: int* into LDS; ACKED / COUNTED: statements run once the stores are acknowledged / the arrival is counted (qbits_skinny.hip's
+// timeline probes).  s_nop: gfx9 hazard "VMEM store of > 64 bits, then VALU write of its data VGPRs" - hipcc cannot see into the asm.
+#define QH_SPLITK_ARRIVE(NF, NT, PARTIALS, SLOT, ACC, COUNTER, FLAG, TID, ACKED, COUNTED)                                           \
+  {                                                                                                                           \
+    float* const qh_mine = (PARTIALS) + ((size_t)(SLOT) * (NF) * (NT) + (TID)) * 4;                                              \
+    _Pragma("unroll") for (int qh_f = 0; qh_f < (NF); ++qh_f) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1"   \
+                                                                           ::"v"(qh_mine + qh_f * ((NT) * 4)), "v"((ACC)[qh_f])   \
+                                                                           : "memory");                                          \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                             \
+    ACKED;                                                                                                                       \
+    __syncthreads();                                                                                                             \
+    if ((TID) == 0) *(FLAG) = __hip_atomic_fetch_add((COUNTER), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);                 \
+    __syncthreads();                                                                                                             \
+    COUNTED;                                                                                                                     \
+  }
+// In the last arriver, after RESET (a statement run once the counter is reset: qmm_mfma_large.hip's barrier before it reuses the flag
+// word): QB splits x FB fragments of loads in flight per wait (a system-coherent load is a ~2 us round trip: one per split
+// made the tail ~12 of the 21.7 us of a (128,4096,4096) fused int4 call with four splits); a batch past the last split re-loads it and
+// drops it.  Adding in split order makes the result independent of which workgroup arrived last.
+#define QH_SPLITK_SUM(NF, NT, QB, FB, PARTIALS, TILE, S, ACC, COUNTER, TID, RESET)                                                  \
+  {                                                                                                                              \
+    if ((TID) == 0) __hip_atomic_store((COUNTER), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); /* leave the workspace as found */ \
+    RESET;                                                                                                                       \
+    _Pragma("unroll") for (int qh_f = 0; qh_f < (NF); ++qh_f)(ACC)[qh_f] = f32x4{0.f, 0.f, 0.f, 0.f};                           \
+    for (int qh_q0 = 0; qh_q0 < (S); qh_q0 += (QB)) {                                                                            \
+      if constexpr ((FB) == (NF)) {                                                                                              \
+        QH_SPLITK_BATCH_(NF, NT, QB, FB, 0, PARTIALS, TILE, S, ACC, TID);                                                        \
+      } else {                                                                                                                   \
+        _Pragma("unroll") for (int qh_f0 = 0; qh_f0 < (NF); qh_f0 += (FB)) QH_SPLITK_BATCH_(NF, NT, QB, FB, qh_f0, PARTIALS, TILE, S, ACC, TID); \
+      }                                                                                                                          \
+    }                                                                                                                            \
+  }
+// fragments F0 .. F0 + FB - 1 of splits qh_q0 .. qh_q0 + QB - 1
+#define QH_SPLITK_BATCH_(NF, NT, QB, FB, F0, PARTIALS, TILE, S, ACC, TID)                                                            \
+  {                                                                                                                              \
+    f32x4 qh_v[QB][FB];                                                                                                          \
+    _Pragma("unroll") for (int qh_j = 0; qh_j < (QB); ++qh_j) {                                                                  \
+      const int qh_q = qh_q0 + qh_j < (S) ? qh_q0 + qh_j : (S) - 1;                                                              \
+      const float* const qh_theirs = (PARTIALS) + ((size_t)((TILE) * (S) + qh_q) * (NF) * (NT) + (TID)) * 4;                     \
+      _Pragma("unroll") for (int qh_e = 0; qh_e < (FB); ++qh_e) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1"           \
+                                                                              : "=v"(qh_v[qh_j][qh_e])                           \
+                                                                              : "v"(qh_theirs + ((F0) + qh_e) * ((NT) * 4))      \
+                                                                              : "memory");                                       \
+    }                                                                                                                            \
+    /* the waits tie the uses below to the loads */                                                                              \
+    _Pragma("unroll") for (int qh_j = 0; qh_j < (QB); ++qh_j) _Pragma("unroll") for (int qh_e = 0; qh_e < (FB); ++qh_e)          \
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(qh_v[qh_j][qh_e])::"memory");                                                     \
+    _Pragma("unroll") for (int qh_j = 0; qh_j < (QB); ++qh_j) if (qh_q0 + qh_j < (S)) {                                          \
+      _Pragma("unroll") for (int qh_e = 0; qh_e < (FB); ++qh_e) _Pragma("unroll") for (int qh_r = 0; qh_r < 4; ++qh_r)           \
+        (ACC)[(F0) + qh_e][qh_r] += qh_v[qh_j][qh_e][qh_r];                                                                      \
+    }                                                                                                                            \
+  }
 
 // ---- 8-bit weight codes -> 16-bit MFMA operands (qbytes_skinny.hip, qmm_mfma_large.hip) ------------------------------------
 // The format is a template argument of the kernels: these numbers are part of their names.

@@ -27,7 +27,7 @@ struct Args {
   int M, N, K;
   int group_m;  // tile raster: groups of group_m tile rows, column-major inside a group (see tile_coords)
   // split-K (S > 1): workgroup b computes K-range b % S of tile b / S; fp32 partial sums go to `partials` and the last
-  // workgroup of a tile to arrive adds them in split order (same protocol and workspace contract as qbits_skinny.hip)
+  // workgroup of a tile to arrive adds them in split order (the split-K tail of qh_mfma.h)
   int S;
   int* counters;    // [tiles], zero on entry, zero on exit
   float* partials;  // [tiles * S][NJ * MI][threads] float4

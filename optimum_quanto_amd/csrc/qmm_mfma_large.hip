@@ -430,43 +430,13 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qbytes_mfma_large_kernel(cons
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   if (S > 1) {
-    // split-K reduction: system-coherent 16-byte stores / loads of the partial sums (no L2-wide fence), one arrival counter
-    // per tile, the last workgroup to arrive sums in split order - see qbits_skinny.hip for the coherence argument
-    // fragment-major layout: every store / load instruction of a wave covers 1 KiB of whole lines (lane-major - NJ*MI*16 bytes per lane -
-    // wrote 16 bytes into every second line per instruction, and partial lines are what the write-through path is slow at)
-    float* mine = a.partials + ((size_t)blockIdx.x * (NJ * MI) * (NWAVES * 64) + tid) * 4;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(mine + (j * MI + i) * (NWAVES * 64 * 4)), "v"(acc[j][i]) : "memory");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    // split-K: the tail of qh_mfma.h with acc[NJ][MI] as NJ * MI fragments, one split and MI fragments per wait
+    f32x4* const accf = reinterpret_cast<f32x4*>(acc);
     int* flag = reinterpret_cast<int*>(smem);
-    if (tid == 0) *flag = __hip_atomic_fetch_add(a.counters + tile_id, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __syncthreads();
+    QH_SPLITK_ARRIVE(NJ * MI, NWAVES * 64, a.partials, blockIdx.x, accf, a.counters + tile_id, flag, tid, (void)0, (void)0);
     if (*flag != S - 1) return;
-    if (tid == 0) __hip_atomic_store(a.counters + tile_id, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __syncthreads();  // the flag word is part of the parking area used below
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int i = 0; i < MI; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int q = 0; q < S; ++q) {
-      const float* theirs = a.partials + ((size_t)(tile_id * S + q) * (NJ * MI) * (NWAVES * 64) + tid) * 4;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        f32x4 v[MI];
-#pragma unroll
-        for (int i = 0; i < MI; ++i) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(v[i]) : "v"(theirs + (j * MI + i) * (NWAVES * 64 * 4)) : "memory");
-#pragma unroll
-        for (int i = 0; i < MI; ++i) asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[i])::"memory");
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[j][i][r] += v[i][r];
-      }
-    }
+    QH_SPLITK_SUM(NJ * MI, NWAVES * 64, 1, MI, a.partials, tile_id, S, accf, a.counters + tile_id, tid,
+                  __syncthreads() /* the flag word is part of the parking area used below */);
   }
   constexpr int JP = NJ < 4 ? NJ : 4;  // feature fragments per pass: parked rows of JP*32 bytes
   constexpr int ROWB = JP * 32, LPR = ROWB / 16;  // lanes per parked row on the read side
@@ -624,15 +594,13 @@ static int large_split(int64_t M, int64_t N, int64_t K) {
   if (tiles128 <= 32 && (K / lt::BK) % 16 == 0 && K / lt::BK >= 32) s = 4;
   if (forced > 0 && tiles128 <= 512 && (K / lt::BK) % forced == 0 && K / lt::BK / forced >= 2) s = forced;
   (void)tiles256;
-  if ((size_t)tiles128 * 4 > QUANTO_HIP_WS_COUNTER_BYTES) s = 1;  // one counter per 128-tile
+  if (!ws_counters_fit(tiles128)) s = 1;  // one counter per 128-tile
   return s;
 }
-// fixed-size counter region shared by all split-K kernels of the library (see qbits_skinny.hip)
-static size_t large_counter_bytes(int64_t, int64_t) { return QUANTO_HIP_WS_COUNTER_BYTES; }
 size_t qbytes_mfma_large_workspace(int64_t M, int64_t N, int64_t K) {
   const int S = large_split(M, N, K);
   if (S == 1) return 0;
-  return large_counter_bytes(M, N) + (size_t)(((M + 127) / 128) * ((N + 127) / 128)) * S * (128 * 128 * 4);
+  return QUANTO_HIP_WS_COUNTER_BYTES + (size_t)(((M + 127) / 128) * ((N + 127) / 128)) * S * (128 * 128 * 4);
 }
 
 // Dense 16-bit GEMM y = x @ w^T (+ bias) on the weights-direct 128-tile loop, for grids that leave every workgroup a CU of its
@@ -657,7 +625,7 @@ int qbytes_mm_mfma_large(const void* x, const void* w, const void* s, const void
                       int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!qbytes_mfma_large_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
   int split = large_split(M, N, K);
-  if (split > 1 && (!workspace || workspace_bytes < qbytes_mfma_large_workspace(M, N, K) || reinterpret_cast<uintptr_t>(workspace) % 16)) split = 1;
+  if (split > 1 && !ws_holds(workspace, workspace_bytes, qbytes_mfma_large_workspace(M, N, K))) split = 1;
   // 128-tiles as long as all of them are resident at once (two workgroups per CU: 512), 256-tiles beyond.  Measured,
   // bf16 x int8, K = 4096, us with 256-tiles -> 128-tiles: (512,14336) 87 -> 67, (1024,8192) 85 -> 70, (2048,4096) 79 -> 66;
   // but (1280,8192) 82 -> 99, (2048,8192) 107 -> 125
@@ -670,7 +638,7 @@ int qbytes_mm_mfma_large(const void* x, const void* w, const void* s, const void
   if (cfg != lt::CFG_128_4W) split = 1;  // the workspace is sized for 128-tiles
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) % 16) return QUANTO_HIP_EALIGN;
   lt::Args a{x, reinterpret_cast<const uint8_t*>(w), s, bias, y, (int)M, (int)N, (int)K, 1, split, reinterpret_cast<int*>(workspace),
-             split > 1 ? reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + large_counter_bytes(M, N)) : nullptr};
+             split > 1 ? ws_partials(workspace) : nullptr};
 #define QH_CASE(DT, FMT) return lt::launch<DT, FMT>(a, cfg, stream)
   if (out_dtype == QUANTO_HIP_BF16) {
     if (b_dtype == QUANTO_HIP_I8) QH_CASE(QUANTO_HIP_BF16, lt::W_I8);

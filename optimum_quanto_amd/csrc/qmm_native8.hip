@@ -58,7 +58,7 @@ struct Args {
   int gm;             // tile raster: consecutive workgroup ids walk down gm tile rows before moving to the next tile column (1 = row-major)
   // split-K (r6, 128-byte-row kernel): S workgroups per tile, workgroup (tile, sp) multiplies the K range sp of S; the accumulators (int32 / fp32) travel
   // fragment-major through `partials`, an arrival counter per tile elects the last workgroup, which adds in split order and runs the epilogue
-  // (protocol and workspace contract of qmm_mfma_large.hip / qbits_skinny.hip: counters zero on entry and on exit)
+  // (workspace contract of the split-K tail in qh_mfma.h: counters zero on entry and on exit)
   int S;
   int* counters;      // [tiles]
   void* partials;     // [tiles * S][NJ * 8][threads] 16-byte accumulator quads
@@ -969,7 +969,7 @@ static int launch(Args a, void* workspace, size_t workspace_bytes, hipStream_t s
   if (p.S > 1 && workspace_bytes < plan_workspace<KIND>(p, a.M, a.N)) p = make_plan<KIND>(a, false);
   a.S = p.S;
   a.counters = p.S > 1 ? reinterpret_cast<int*>(workspace) : nullptr;
-  a.partials = p.S > 1 ? reinterpret_cast<uint8_t*>(workspace) + QUANTO_HIP_WS_COUNTER_BYTES : nullptr;
+  a.partials = p.S > 1 ? ws_partials(workspace) : nullptr;
   a.poll_ticks = env_int("QUANTO_HIP_NATIVE8_POLL_TICKS", 20000);  // tests: 0 = nobody waits, the last arriver reduces every slice it finds abandoned
   const bool small = p.small;
   // 128-byte rows (full-line vector-L1 fills, one barrier per 128 bytes of K) whenever K allows

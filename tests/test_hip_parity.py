@@ -252,6 +252,35 @@ def test_qbits_mfma_fused4_split_k(dt, split, M, N, K, zp, bm, monkeypatch):
     np.testing.assert_array_equal(_run_qbits(p, "mfma_fused4", bias), O.round_to((y0 + bias).astype(np.float32), dt))
 
 
+# Forced K splits of the streaming and large-tile kernels (their automatic rules pick powers of two): 3, 5 and 6 are not multiples of the splits
+# the split-K tail loads per wait (qbits_skinny: four), so its last batch re-loads the last split and drops it.  The workspace size shows that the
+# knob took effect; a second call on the same workspace gives the same bits (the arrival counters were left zero); bias bit for bit against the
+# kernel's own bias-free output (rounded product + bias, rounded again).
+DT_CODE = {"fp16": 1, "bf16": 2}  # quanto_hip_dtype
+
+
+def _token_fragments(M):  # per pass of at most 64 rows
+    M = min(M, 64)
+    return 1 if M <= 16 else (2 if M <= 32 else 4)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+@pytest.mark.parametrize("split", [3, 5, 6])
+@pytest.mark.parametrize("M,N,zp", [(8, 512, False), (24, 512, True), (40, 160, False), (100, 48, True)])
+def test_qbits_skinny_split_k(dt, split, M, N, zp, monkeypatch):
+    """1 / 2 / 4 token fragments (two wave sets from two on), 4-, 2- and 1-wave blocks (N = 512 / 160 / 48), two passes of 64 rows (M = 100)."""
+    K = 3840  # 30 groups
+    monkeypatch.setenv("QUANTO_HIP_SKINNY_SPLIT", str(split))
+    ws = quanto_hip.cdll.quanto_hip_qbits_mm_workspace_size(M, N, K, 4, 128, DT_CODE[dt], 5)  # QUANTO_HIP_KERNEL_SKINNY
+    assert ws == 4096 + N // 16 * split * 64 * _token_fragments(M) * 16
+    p = make_qbits_problem(M, N, K, dt, zeropoint=zp, seed=M + N + split)
+    y0 = _run_qbits(p, "skinny")
+    assert_close_to_exact(y0, _exact_qbits(p), dt, f"skinny split {split} {M}x{K}x{N}")
+    np.testing.assert_array_equal(_run_qbits(p, "skinny"), y0)
+    bias = O.round_to(np.random.default_rng(6).standard_normal(N).astype(np.float32), dt)
+    np.testing.assert_array_equal(_run_qbits(p, "skinny", bias), O.round_to((y0 + bias).astype(np.float32), dt))
+
+
 @pytest.mark.parametrize("dt", ["bf16", "fp16"])
 def test_qbits_mfma_zeropoint_and_bias(dt):
     p = make_qbits_problem(40, 256, 512, dt, zeropoint=True, seed=12)
@@ -481,6 +510,44 @@ def test_qbytes_mfma_large_tile_split_k(dt, kind, M, N, K):
     assert_close_to_exact(_run_qbytes(p, "mfma_large"), want, dt, "qbytes mfma_large split-K")
     bias = O.round_to(np.random.default_rng(7).standard_normal(N).astype(np.float32), dt)
     assert_close_with_bias(_run_qbytes(p, "mfma_large", bias), want, bias, dt, "qbytes mfma_large split-K + bias")
+
+
+def _qbytes_split_k(p, kernel, what):
+    """the checks of test_qbits_skinny_split_k for a qbytes kernel"""
+    dt, N = p["dt"], p["data"].shape[0]
+    y0 = _run_qbytes(p, kernel)
+    assert_close_to_exact(y0, O.qbytes_mm_exact(p["x"], p["data"], p["scale"], p["kind"]), dt, what)
+    np.testing.assert_array_equal(_run_qbytes(p, kernel), y0)
+    bias = O.round_to(np.random.default_rng(8).standard_normal(N).astype(np.float32), dt)
+    np.testing.assert_array_equal(_run_qbytes(p, kernel, bias), O.round_to((y0 + bias).astype(np.float32), dt))
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+@pytest.mark.parametrize("kind", [None, "e4m3fn"])
+@pytest.mark.parametrize("split", [3, 5, 6])
+@pytest.mark.parametrize("M,N", [(8, 512), (40, 130), (100, 256)])
+def test_qbytes_skinny_split_k(dt, kind, split, M, N, monkeypatch):
+    """Forced splits of the 8-bit streaming kernel: 1 and 4 token fragments, ragged N, two passes of 64 rows (M = 100)."""
+    K = 3840  # 30 tiles of 128
+    monkeypatch.setenv("QUANTO_HIP_SKINNY_SPLIT", str(split))
+    b_code = 3 if kind is None else 5  # QUANTO_HIP_I8 / QUANTO_HIP_F8_E4M3FN
+    ws = quanto_hip.cdll.quanto_hip_qbytes_mm_workspace_size(M, N, K, DT_CODE[dt], b_code, DT_CODE[dt], 5)  # QUANTO_HIP_KERNEL_SKINNY
+    assert ws == 4096 + (N + 63) // 64 * split * 256 * _token_fragments(M) * 16
+    _qbytes_split_k(make_qbytes_problem(M, N, K, dt, kind, seed=M + N + split), "skinny", f"qbytes skinny split {split} {M}x{K}x{N}")
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+@pytest.mark.parametrize("kind", [None, "e4m3fn"])
+@pytest.mark.parametrize("split", [3, 5, 6])
+@pytest.mark.parametrize("M,N", [(300, 700), (128, 256)])
+def test_qbytes_mfma_large_tile_split_k_forced(dt, kind, split, M, N, monkeypatch):
+    """Forced splits of the 128-tile kernel, ragged edges: 20 / 12 K-tiles per split take the weights-direct loop, 10 the LDS-weight loop."""
+    K = 7680  # 60 K-tiles
+    monkeypatch.setenv("QUANTO_HIP_LARGE_SPLIT", str(split))
+    b_code = 3 if kind is None else 5
+    ws = quanto_hip.cdll.quanto_hip_qbytes_mm_workspace_size(M, N, K, DT_CODE[dt], b_code, DT_CODE[dt], 4)  # QUANTO_HIP_KERNEL_MFMA_LARGE
+    assert ws == 4096 + ((M + 127) // 128) * ((N + 127) // 128) * split * 128 * 128 * 4
+    _qbytes_split_k(make_qbytes_problem(M, N, K, dt, kind, seed=M + K + split), "mfma_large", f"qbytes mfma_large split {split} {M}x{K}x{N}")
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16", "fp16"])

@@ -184,7 +184,7 @@ def test_conv2d_entries_reject_bad_arguments_without_a_gpu():
 
 
 def test_conv2d_k_split_plan_without_a_gpu():
-    """quanto_hip_conv2d_workspace_size is the host-side statement of the convolution kernel's K split (csrc/qconv_mfma.hip: pick_split): up to
+    """quanto_hip_conv2d_workspace_size is the host-side statement of the convolution kernel's K split (csrc/qh_common.h: conv_pick_split): up to
     ~2 workgroups per CU, at least 4 K-tiles per split (r5; 3 until the gather got cheaper), no split beyond 128 output tiles; one 128 x 128 fp32 tile per (split, tile)."""
     f = quanto_hip.cdll.quanto_hip_conv2d_workspace_size
     f.restype, f.argtypes = ctypes.c_int64, [ctypes.c_int64] * 5
