@@ -189,7 +189,8 @@ int64_t quanto_hip_qbits_mm_workspace_size(int64_t M, int64_t N, int64_t K, int 
 /* The quanto_hip_kernel that QUANTO_HIP_KERNEL_AUTO resolves to for this problem when a sufficient workspace is given. */
 int quanto_hip_qbits_mm_pick(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype);
 /* Both answers in one call (a binding on the decode path makes one FFI round trip instead of two): resolves `kernel`
- * (AUTO -> the kernel quanto_hip_qbits_mm_pick returns) into *kernel_out and its scratch bytes into *workspace_bytes_out. */
+ * (AUTO -> the kernel quanto_hip_qbits_mm_pick returns) into *kernel_out and its scratch bytes into *workspace_bytes_out.  A forced kernel whose
+ * support rule does not admit the problem (operand products, grid limits, formats): QUANTO_HIP_ENOTSUP here and from _workspace_size. */
 int quanto_hip_qbits_mm_plan(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype, int kernel, int* kernel_out,
                              int64_t* workspace_bytes_out);
 
@@ -231,6 +232,7 @@ int quanto_hip_qbytes_mm_multi_plan(int count, const int64_t* N, int64_t M, int6
 int quanto_hip_qbytes_mm_ws(const void* a, const void* b, const void* scales, const void* bias, void* y,
                             int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* Like their qbits_mm counterparts: a forced kernel outside its support rule gives QUANTO_HIP_ENOTSUP, not a size. */
 int64_t quanto_hip_qbytes_mm_workspace_size(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel);
 int quanto_hip_qbytes_mm_pick(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype);
 int quanto_hip_qbytes_mm_plan(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel, int* kernel_out,

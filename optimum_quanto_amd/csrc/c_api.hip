@@ -222,6 +222,26 @@ static int64_t qbits_kernel_workspace(int kernel, int64_t M, const PackedGeom& g
   return 0;
 }
 
+// Whether a FORCED kernel serves this qbits_mm problem, by the rule its launcher checks: the size and plan entries answer QUANTO_HIP_ENOTSUP
+// for a shape beyond that rule instead of a workspace size (QUANTO_HIP_EINVAL for an id that is no kernel).
+static int qbits_kernel_serves(int kernel, int64_t M, const PackedGeom& g, int dtype) {
+  const bool f32 = dtype == QUANTO_HIP_F32;
+  bool ok = false;
+  switch (kernel) {
+    case QUANTO_HIP_KERNEL_AUTO:
+    case QUANTO_HIP_KERNEL_NAIVE: ok = true; break;
+    case QUANTO_HIP_KERNEL_GEMV: ok = f32 ? qbits_gemv_f32_supported(M, g, dtype) : qbits_gemv_supported(M, g, dtype); break;
+    case QUANTO_HIP_KERNEL_MFMA: ok = f32 ? qbits_mm_f32_supported(M, g, dtype) : qbits_mfma_supported(M, g, dtype); break;
+    case QUANTO_HIP_KERNEL_DEQUANT_MFMA: ok = dequant_mfma_supported(M, g, dtype); break;
+    case QUANTO_HIP_KERNEL_SKINNY: ok = qbits_skinny_supported(M, g, dtype); break;
+    case QUANTO_HIP_KERNEL_MMV: ok = qbits_mmv_supported(M, g, dtype); break;
+    case QUANTO_HIP_KERNEL_MFMA_FUSED4: ok = qbits_mfma_fused_supported(M, g, dtype); break;
+    case QUANTO_HIP_KERNEL_MFMA_LARGE4: ok = qbits_mfma_large_supported(M, g, dtype); break;
+    default: return QUANTO_HIP_EINVAL;
+  }
+  return ok || M == 0 ? QUANTO_HIP_OK : QUANTO_HIP_ENOTSUP;
+}
+
 // The kernel a qbits_mm call runs and the workspace it needs.  AUTO picks for a caller with (have_workspace) or without a workspace, then
 // steps down from the kernels that need more than workspace_bytes: the queries plan with (true, SIZE_MAX), the launch with what it was given.
 static Plan plan_qbits(int64_t M, const PackedGeom& g, int dtype, int kernel, bool have_workspace, size_t workspace_bytes) {
@@ -299,7 +319,10 @@ int64_t quanto_hip_qbits_mm_workspace_size(int64_t M, int64_t N, int64_t K, int 
   bool int_shift = false;
   const int st = check_qbits(M, N, K, bits, group_size, dtype, dtype, &int_shift);
   if (st != QUANTO_HIP_OK) return st;
-  return plan_qbits(M, make_geom(N, K, bits, group_size), dtype, kernel, true, SIZE_MAX).workspace;
+  const PackedGeom g = make_geom(N, K, bits, group_size);
+  const int serves = qbits_kernel_serves(kernel, M, g, dtype);
+  if (serves != QUANTO_HIP_OK) return serves;
+  return plan_qbits(M, g, dtype, kernel, true, SIZE_MAX).workspace;
 }
 
 int quanto_hip_qbits_mm_pick(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype) {
@@ -315,7 +338,10 @@ int quanto_hip_qbits_mm_plan(int64_t M, int64_t N, int64_t K, int bits, int grou
   bool int_shift = false;
   const int st = check_qbits(M, N, K, bits, group_size, dtype, dtype, &int_shift);
   if (st != QUANTO_HIP_OK) return st;
-  const Plan p = plan_qbits(M, make_geom(N, K, bits, group_size), dtype, kernel, true, SIZE_MAX);
+  const PackedGeom g = make_geom(N, K, bits, group_size);
+  const int serves = qbits_kernel_serves(kernel, M, g, dtype);
+  if (serves != QUANTO_HIP_OK) return serves;
+  const Plan p = plan_qbits(M, g, dtype, kernel, true, SIZE_MAX);
   *kernel_out = p.kernel;
   *workspace_bytes_out = p.workspace;
   return QUANTO_HIP_OK;
@@ -516,6 +542,27 @@ static int pick_qbytes_kernel(int64_t M, int64_t N, int64_t K, int a_dtype, int 
   return QUANTO_HIP_KERNEL_NAIVE;
 }
 
+// qbits_kernel_serves for qbytes_mm
+static int qbytes_kernel_serves(int kernel, int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
+  const bool f32 = a_dtype == QUANTO_HIP_F32 && out_dtype == QUANTO_HIP_F32;
+  bool ok = false;
+  switch (kernel) {
+    case QUANTO_HIP_KERNEL_AUTO:
+    case QUANTO_HIP_KERNEL_NAIVE: ok = true; break;
+    case QUANTO_HIP_KERNEL_GEMV:
+      ok = f32 ? qbytes_gemv_f32_supported(M, N, K, a_dtype, b_dtype, out_dtype) : qbytes_gemv_supported(M, N, K, a_dtype, b_dtype, out_dtype);
+      break;
+    case QUANTO_HIP_KERNEL_MFMA:
+      ok = f32 ? qbytes_mm_f32_supported(M, N, K, a_dtype, b_dtype, out_dtype) : qbytes_mfma_supported(M, N, K, a_dtype, b_dtype, out_dtype);
+      break;
+    case QUANTO_HIP_KERNEL_SKINNY: ok = qbytes_skinny_supported(M, N, K, a_dtype, b_dtype, out_dtype); break;
+    case QUANTO_HIP_KERNEL_MFMA_LARGE: ok = qbytes_mfma_large_supported(M, N, K, a_dtype, b_dtype, out_dtype); break;
+    case QUANTO_HIP_KERNEL_NATIVE8: ok = qbytes_native8_supported(M, N, K, a_dtype, b_dtype, out_dtype); break;
+    default: return QUANTO_HIP_EINVAL;
+  }
+  return ok || M == 0 ? QUANTO_HIP_OK : QUANTO_HIP_ENOTSUP;
+}
+
 // The kernel a qbytes_mm call runs and the workspace it needs (the kernels that split K run unsplit without one)
 static Plan plan_qbytes(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel) {
   if (kernel == QUANTO_HIP_KERNEL_AUTO) kernel = pick_qbytes_kernel(M, N, K, a_dtype, b_dtype, out_dtype);
@@ -540,14 +587,16 @@ int quanto_hip_qbytes_mm_pick(int64_t M, int64_t N, int64_t K, int a_dtype, int 
 }
 
 int64_t quanto_hip_qbytes_mm_workspace_size(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel) {
-  const int st = check_qbytes(M, N, K, out_dtype);
+  int st = check_qbytes(M, N, K, out_dtype);
+  if (st == QUANTO_HIP_OK) st = qbytes_kernel_serves(kernel, M, N, K, a_dtype, b_dtype, out_dtype);
   return st != QUANTO_HIP_OK ? st : plan_qbytes(M, N, K, a_dtype, b_dtype, out_dtype, kernel).workspace;
 }
 
 int quanto_hip_qbytes_mm_plan(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel, int* kernel_out,
                               int64_t* workspace_bytes_out) {
   if (!kernel_out || !workspace_bytes_out) return QUANTO_HIP_EINVAL;
-  const int st = check_qbytes(M, N, K, out_dtype);
+  int st = check_qbytes(M, N, K, out_dtype);
+  if (st == QUANTO_HIP_OK) st = qbytes_kernel_serves(kernel, M, N, K, a_dtype, b_dtype, out_dtype);
   if (st != QUANTO_HIP_OK) return st;
   const Plan p = plan_qbytes(M, N, K, a_dtype, b_dtype, out_dtype, kernel);
   *kernel_out = p.kernel;

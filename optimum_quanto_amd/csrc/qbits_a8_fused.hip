@@ -448,7 +448,7 @@ bool qbits_a8_supported(int64_t M, const PackedGeom& g, int a_dtype, int dtype) 
   if (!((g.bits == 4 || g.bits == 2) && g.C == 128 && (g.N % (4 * g.vpi) == 0) && (g.K % 128 == 0) && M >= 1 &&
         (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) &&
         (a_dtype == QUANTO_HIP_I8 || a_dtype == QUANTO_HIP_F8_E4M3FN || a_dtype == QUANTO_HIP_F8_E5M2) && g.N < (1 << 30) && g.K < (1 << 30) &&
-        M * g.K < (1ll << 32) && g.N * g.K < (1ll << 33)))
+        M * g.K < (1ll << 32) && g.N * g.K < (1ll << 33) && grid_yz_fits(M, 64)))  // grid.y = token tiles of the smaller tile the plan may take
     return false;
   return a8::make_plan(M, g.N, (int)g.G, g.bits).bm != 0;
 }

@@ -460,7 +460,7 @@ static int launch(const Args& a, int bm, hipStream_t stream) {
 
 bool qbits_mfma_fused_supported(int64_t M, const PackedGeom& g, int dtype) {
   if (!(g.bits == 4 && g.C == 128 && (g.N % 8 == 0) && (g.K % 128 == 0) && M >= 1 && (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) &&
-        g.N < (1 << 30) && g.K < (1 << 30) && M * g.K < (1ll << 31) && g.N * g.K < (1ll << 33)))
+        g.N < (1 << 30) && g.K < (1 << 30) && M * g.K < (1ll << 31) && g.N * g.K < (1ll << 33) && grid_yz_fits(M, 64)))  // grid.y: 64-token tiles
     return false;
   return fused4::make_plan(M, g.N, (int)g.G).bm != 0;
 }

@@ -172,6 +172,12 @@ inline bool ws_holds(const void* workspace, size_t workspace_bytes, size_t need)
   return workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 16 == 0;
 }
 
+// ---- launch grids: a kernel that puts a tile count in grid.y / grid.z takes at most this many (hipDeviceProp_t::maxGridSize[1] and [2]
+// are 65536 on gfx950; the convolutions' rules always used 65535).  A support rule bounds its tile count with it, so that AUTO steps down
+// to another kernel instead of reaching a launch that cannot succeed (tests/test_size_limits_cpu.py).
+constexpr int64_t kMaxGridYZ = 65535;
+inline bool grid_yz_fits(int64_t items, int64_t tile) { return (items + tile - 1) / tile <= kMaxGridYZ; }
+
 int launch_status();  // hipGetLastError() -> quanto_hip_status (defined in c_api.hip)
 void set_last_kernel(const char* name);
 

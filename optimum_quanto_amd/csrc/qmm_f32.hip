@@ -395,7 +395,7 @@ bool qbits_gemv_f32_supported(int64_t M, const PackedGeom& g, int dtype) {
   return f32_qbits_common(M, g, dtype) && g.K % 16 == 0 && M <= QUANTO_HIP_GEMV_F32_MAX_M;
 }
 bool qbits_mm_f32_supported(int64_t M, const PackedGeom& g, int dtype) {
-  return f32_qbits_common(M, g, dtype) && g.K % f32k::BK == 0;
+  return f32_qbits_common(M, g, dtype) && g.K % f32k::BK == 0 && grid_yz_fits(M, f32k::BM);  // grid.y = M tiles
 }
 
 int qbits_mm_gemv_f32(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
@@ -427,7 +427,7 @@ bool qbytes_gemv_f32_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int
   return f32_qbytes_common(M, N, K, a_dtype, b_dtype, out_dtype) && K % 16 == 0 && M <= QUANTO_HIP_GEMV_F32_MAX_M;
 }
 bool qbytes_mm_f32_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  return f32_qbytes_common(M, N, K, a_dtype, b_dtype, out_dtype) && K % f32k::BK == 0;
+  return f32_qbytes_common(M, N, K, a_dtype, b_dtype, out_dtype) && K % f32k::BK == 0 && grid_yz_fits(M, f32k::BM);  // grid.y = M tiles
 }
 
 template <bool GEMV>

@@ -322,7 +322,7 @@ static int mma_launch(const MmaArgs& a, hipStream_t stream) {
 bool qbytes_mfma_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
   const bool bd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2;
   return bd && a_dtype == out_dtype && (out_dtype == QUANTO_HIP_BF16 || out_dtype == QUANTO_HIP_F16) && M >= 1 && K % BK == 0 &&
-         K >= BK && M < (1 << 30) && N < (1 << 30) && K < (1 << 30);
+         K >= BK && M < (1 << 30) && N < (1 << 30) && K < (1 << 30) && grid_yz_fits(M, BM);  // grid.y = M tiles
 }
 
 int qbytes_mm_mfma(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
@@ -344,7 +344,7 @@ int qbytes_mm_mfma(const void* x, const void* w, const void* s, const void* bias
 
 bool qbits_mfma_supported(int64_t M, const PackedGeom& g, int dtype) {
   return g.bits == 4 && (g.C == 64 || g.C == 128) && (g.N % 2 == 0) && (g.K % g.C == 0) && M >= 1 &&
-         (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && M < (1 << 30) && g.N < (1 << 30) && g.K < (1 << 30);
+         (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && M < (1 << 30) && g.N < (1 << 30) && g.K < (1 << 30) && grid_yz_fits(M, BM);
 }
 
 size_t qbits_mfma_workspace(int64_t M, const PackedGeom& g) {
