@@ -1,5 +1,5 @@
 // extern "C" surface of libquanto_hip.so: argument validation + kernel selection.  No torch, no allocation.
-#include "qh_common.h"
+#include "qh_conv.h"
 
 namespace qh {
 
@@ -31,25 +31,21 @@ int dequantize_symmetric(const void*, const void*, void*, int64_t, int, int, hip
 int quantize_affine(const void*, const void*, const void*, void*, int64_t, int64_t, int, int, bool, hipStream_t);
 int quantize_affine_packed(const void*, const void*, const void*, void*, int64_t, int64_t, int, int, bool, hipStream_t);
 int pack_weights(const uint8_t*, uint8_t*, int64_t, int64_t, int, hipStream_t);
-bool qbits_conv2d_supported(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const PackedGeom&, int);
-int qbits_conv2d_mfma(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                      int64_t, int64_t, int, int, int, int, int, int, const PackedGeom&, int, bool, void*, size_t, hipStream_t);
+// convolutions: a call's geometry travels as one ConvGeom (qh_conv.h)
+bool qbits_conv2d_supported(const ConvGeom&, const PackedGeom&, int);
+int qbits_conv2d_mfma(const void*, const uint8_t*, const void*, const void*, const void*, void*, const ConvGeom&, const PackedGeom&, int, bool, void*, size_t,
+                      hipStream_t);
 size_t conv2d_workspace(int64_t, int64_t, int64_t);
 // depthwise convolution with an 8-bit weight (r6, qconv_depthwise.hip)
-int qbytes_conv2d_depthwise(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                            int64_t, int, int, int, int, int, int, int, int, int, hipStream_t, bool* strip);
+int qbytes_conv2d_depthwise(const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, hipStream_t, bool* strip);
 size_t conv2d_dense_weight_bytes(int64_t, int64_t);
-bool conv2d_rows_eligible(int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int64_t);
-int qdense_conv2d_rows(const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int,
-                       int, int, int, int, int, void*, size_t, hipStream_t);
+bool conv2d_rows_eligible(const ConvGeom&);
+int qdense_conv2d_rows(const void*, const void*, const void*, void*, const ConvGeom&, int, void*, size_t, hipStream_t);
 // convolution with quantized activations on the 8-bit matrix instructions (qconv_a8.hip)
 int qbytes_conv2d_a8_kind(int, int, int);
-bool qbytes_conv2d_a8_geometry_ok(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t);
 size_t conv2d_a8_workspace(int64_t, int64_t, int64_t);
-int qbytes_conv2d_a8(const void*, const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                     int64_t, int64_t, int, int, int, int, int, int, int, int, int, void*, size_t, hipStream_t, int*);
-int qbytes_conv2d_mfma(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                       int64_t, int, int, int, int, int, int, int, int, int, void*, size_t, hipStream_t, bool* rows);
+int qbytes_conv2d_a8(const void*, const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t, hipStream_t, int*);
+int qbytes_conv2d_mfma(const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t, hipStream_t, bool* rows);
 int qbytes_mm_gemv_multi(const void*, int, const void* const*, const void* const*, const void* const*, void* const*, const int64_t*, int64_t,
                          int64_t, int, int, hipStream_t);
 bool qbytes_skinny_multi_supported(int, const int64_t*, int64_t, int64_t, int, int, int);
@@ -770,11 +766,11 @@ int64_t quanto_hip_qbits_conv2d_workspace_size(int64_t B, int64_t OH, int64_t OW
   return split + (int64_t)conv2d_dense_weight_bytes(OC, K);
 }
 
-static bool qbits_conv2d_takes_rows(int64_t B, int64_t cin, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_w, int dil_w) {
+static bool qbits_conv2d_takes_rows(const ConvGeom& g) {
   // (the tap kernel dequantizes the whole weight once per 128-pixel tile; one dequantize launch pays from ~8 pixel tiles on: (8,512,7,7) -> 512, 4 of
   // them, 28.8 us on the tap kernel against 30.2 this way, (32,512,7,7), 13 tiles, 44.3 against 40.3 - profiles/r05_qconv2d_rows_one_pixel_ab.jsonl)
-  const int64_t pixel_tiles = (B * OH * OW + 127) / 128;
-  return conv2d_rows_eligible(cin, KH, KW, W, OW, stride_w, dil_w, OC) && pixel_tiles >= env_int("QUANTO_HIP_CONV_DENSE_MIN_TILES", 8);
+  const int64_t pixel_tiles = (g.M() + 127) / 128;
+  return conv2d_rows_eligible(g) && pixel_tiles >= env_int("QUANTO_HIP_CONV_DENSE_MIN_TILES", 8);
 }
 
 int64_t quanto_hip_qbits_conv2d_workspace_size_geom(int64_t B, int64_t cin, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW,
@@ -784,14 +780,17 @@ int64_t quanto_hip_qbits_conv2d_workspace_size_geom(int64_t B, int64_t cin, int6
   const int64_t split = quanto_hip_conv2d_workspace_size(B, OH, OW, OC, K);
   if (split < 0) return split;
   if (B == 0 || OH == 0 || OW == 0) return 0;
-  return split + (qbits_conv2d_takes_rows(B, cin, W, OC, KH, KW, OH, OW, stride_w, dil_w) ? (int64_t)conv2d_dense_weight_bytes(OC, K) : 0);
+  const ConvGeom g{B, cin, 0, W, OC, KH, KW, OH, OW, 1, stride_w, 0, 0, 1, dil_w};  // (the row rule reads the window and the width only)
+  return split + (qbits_conv2d_takes_rows(g) ? (int64_t)conv2d_dense_weight_bytes(OC, K) : 0);
 }
 
+// the one place where the ABI's positional geometry becomes a ConvGeom (*g, valid when QUANTO_HIP_OK comes back)
 static int check_conv2d_args(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h,
-                             int stride_w, int pad_h, int pad_w, int dil_h, int dil_w) {
+                             int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, ConvGeom* g) {
   if (B < 0 || cin <= 0 || H <= 0 || W <= 0 || OC <= 0 || KH <= 0 || KW <= 0 || OH < 0 || OW < 0) return QUANTO_HIP_EINVAL;
   if (stride_h <= 0 || stride_w <= 0 || pad_h < 0 || pad_w < 0 || dil_h <= 0 || dil_w <= 0) return QUANTO_HIP_EINVAL;
   if (OH != (H + 2 * pad_h - dil_h * (KH - 1) - 1) / stride_h + 1 || OW != (W + 2 * pad_w - dil_w * (KW - 1) - 1) / stride_w + 1) return QUANTO_HIP_EINVAL;
+  *g = ConvGeom{B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w};
   return QUANTO_HIP_OK;
 }
 
@@ -799,14 +798,14 @@ int quanto_hip_qbytes_conv2d(const void* x, const void* w, const void* scales, c
                              int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
                              int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes,
                              void* stream) {
-  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+  ConvGeom g;
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, &g);
   if (geo != QUANTO_HIP_OK) return geo;
   if (!is_float_dtype(out_dtype)) return QUANTO_HIP_ENOTSUP;
   if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
   if (!x || !w || !scales || !y) return QUANTO_HIP_EINVAL;
   bool rows = false;
-  const int r = qbytes_conv2d_mfma(x, w, scales, bias, y, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, a_dtype,
-                                   b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), &rows);
+  const int r = qbytes_conv2d_mfma(x, w, scales, bias, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), &rows);
   if (r == QUANTO_HIP_OK) set_last_kernel(rows ? "conv2d_mfma_rows" : "conv2d_mfma");
   return r;
 }
@@ -814,26 +813,27 @@ int quanto_hip_qbytes_conv2d(const void* x, const void* w, const void* scales, c
 int64_t quanto_hip_qbytes_conv2d_a8_workspace_size(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW,
                                                    int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype,
                                                    int out_dtype) {
-  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+  ConvGeom g;
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, &g);
   if (geo != QUANTO_HIP_OK) return geo;
   if (qbytes_conv2d_a8_kind(a_dtype, b_dtype, out_dtype) < 0) return QUANTO_HIP_ENOTSUP;
   if (B == 0 || OH == 0 || OW == 0) return 0;
-  if (!qbytes_conv2d_a8_geometry_ok(B, cin, H, W, OC, KH, KW, OH, OW)) return QUANTO_HIP_ENOTSUP;
-  return (int64_t)conv2d_a8_workspace(B * OH * OW, OC, cin * KH * KW);
+  if (!conv_geometry_ok(g)) return QUANTO_HIP_ENOTSUP;
+  return (int64_t)conv2d_a8_workspace(g.M(), OC, g.K());
 }
 
 int quanto_hip_qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, int64_t B, int64_t cin,
                                 int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
                                 int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes,
                                 void* stream) {
-  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+  ConvGeom g;
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, &g);
   if (geo != QUANTO_HIP_OK) return geo;
   if (qbytes_conv2d_a8_kind(a_dtype, b_dtype, out_dtype) < 0) return QUANTO_HIP_ENOTSUP;
   if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
   if (!x || !a_scale || !w || !w_scale || !y) return QUANTO_HIP_EINVAL;
   int kind = -1;
-  const int r = qbytes_conv2d_a8(x, a_scale, w, w_scale, bias, y, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, a_dtype,
-                                 b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), &kind);
+  const int r = qbytes_conv2d_a8(x, a_scale, w, w_scale, bias, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), &kind);
   static const char* const names[3] = {"conv2d_a8_int8", "conv2d_a8_fp8", "conv2d_a8_fp8_w8"};
   if (r == QUANTO_HIP_OK) set_last_kernel(names[kind]);
   return r;
@@ -842,15 +842,15 @@ int quanto_hip_qbytes_conv2d_a8(const void* x, const void* a_scale, const void* 
 int quanto_hip_qbytes_conv2d_depthwise(const void* x, const void* w, const void* scales, const void* bias, void* y, int64_t B, int64_t cin, int64_t H,
                                        int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
                                        int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype, void* stream) {
-  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+  ConvGeom g;
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, &g);
   if (geo != QUANTO_HIP_OK) return geo;
   if (OC % cin != 0) return QUANTO_HIP_EINVAL;
   if (!is_float_dtype(out_dtype)) return QUANTO_HIP_ENOTSUP;
   if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
   if (!x || !w || !scales || !y) return QUANTO_HIP_EINVAL;
   bool strip = false;  // 16-byte row chunks; otherwise quads
-  const int r = qbytes_conv2d_depthwise(x, w, scales, bias, y, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, a_dtype,
-                                        b_dtype, out_dtype, reinterpret_cast<hipStream_t>(stream), &strip);
+  const int r = qbytes_conv2d_depthwise(x, w, scales, bias, y, g, a_dtype, b_dtype, out_dtype, reinterpret_cast<hipStream_t>(stream), &strip);
   if (r == QUANTO_HIP_OK) set_last_kernel(strip ? "conv2d_depthwise_strip" : "conv2d_depthwise");
   return r;
 }
@@ -859,32 +859,31 @@ int quanto_hip_qbits_conv2d(const void* x, const uint8_t* packed, const void* sc
                             int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
                             int pad_w, int dil_h, int dil_w, int bits, int group_size, int dtype, int shift_dtype, void* workspace,
                             size_t workspace_bytes, void* stream) {
-  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+  ConvGeom cg;
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, &cg);
   if (geo != QUANTO_HIP_OK) return geo;
   bool int_shift = false;
-  const int64_t K = cin * KH * KW;
-  const int st = check_qbits(B * OH * OW, OC, K, bits, group_size, dtype, shift_dtype, &int_shift);
+  const int64_t K = cg.K();
+  const int st = check_qbits(cg.M(), OC, K, bits, group_size, dtype, shift_dtype, &int_shift);
   if (st != QUANTO_HIP_OK) return st;
   if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
   if (!x || !packed || !scale || !shift || !y) return QUANTO_HIP_EINVAL;
   const PackedGeom g = make_geom(OC, K, bits, group_size);
   hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
   const size_t dense = conv2d_dense_weight_bytes(OC, K);
-  if (qbits_conv2d_takes_rows(B, cin, W, OC, KH, KW, OH, OW, stride_w, dil_w) && workspace &&
+  if (qbits_conv2d_takes_rows(cg) && workspace &&
       workspace_bytes >= dense && reinterpret_cast<uintptr_t>(workspace) % 16 == 0 && is_float_dtype(dtype) && dtype != QUANTO_HIP_F32) {
     // three-tap-wide windows at stride 1: dequantize once (the reference's own dense weight), then the row form of the convolution on it
     int r = dequantize_qbits_dispatch(packed, scale, shift, workspace, g, dtype, int_shift, hs);
     if (r == QUANTO_HIP_OK)
-      r = qdense_conv2d_rows(x, workspace, bias, y, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, dtype,
-                             reinterpret_cast<uint8_t*>(workspace) + dense, workspace_bytes - dense, hs);
+      r = qdense_conv2d_rows(x, workspace, bias, y, cg, dtype, reinterpret_cast<uint8_t*>(workspace) + dense, workspace_bytes - dense, hs);
     if (r == QUANTO_HIP_OK) {
       set_last_kernel(bits == 4 ? "conv2d_rows_dequant_int4" : "conv2d_rows_dequant_int2");
       return r;
     }
     if (r != QUANTO_HIP_ENOTSUP) return r;
   }
-  const int r = qbits_conv2d_mfma(x, packed, scale, shift, bias, y, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, g, dtype,
-                                  int_shift, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  const int r = qbits_conv2d_mfma(x, packed, scale, shift, bias, y, cg, g, dtype, int_shift, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
   if (r == QUANTO_HIP_OK) set_last_kernel(bits == 4 ? "conv2d_mfma_int4" : "conv2d_mfma_int2");
   return r;
 }

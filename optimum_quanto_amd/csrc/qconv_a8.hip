@@ -9,9 +9,10 @@
 // codes.  acc is exact int32 for int8 x int8 (the result is a pure function of the integers, split or not) and the fp32 matrix-pipe sum of exact
 // products for fp8.
 //
-// GEMM view, tiles and gather = qconv_mfma.hip's tap kernel: M = B*OH*OW pixels, N = OC, K = cin*KH*KW in the weight's (c, i, j)
-// order; one workgroup = 128 pixels x 128 channels, eight waves (2 x 4, 64 pixels x 32 channels each), two LDS buffers.  A K-tile is 128 ONE-byte
-// elements - again a 128-byte LDS row, so lds_off's swizzle and the conflict-free fragment reads carry over unchanged:
+// GEMM view, tiles and gather: the tap gather of DESIGN.md 4.8, whose shared pieces (LDS layout, tap table, validity test, partial-tile store, split
+// plan and reduce, geometry rule) live in qh_conv.h: M = B*OH*OW pixels, N = OC, K = cin*KH*KW in the weight's (c, i, j) order; one workgroup =
+// 128 pixels x 128 channels, eight waves (2 x 4, 64 pixels x 32 channels each), two LDS buffers.  A K-tile is 128 ONE-byte elements - one 128-byte
+// LDS row of conv_lds_off:
 //   * a thread stages one pixel (tile row tid & 127) and two 16-byte chunks of it per K-tile, kc = (tid >> 7) + 4 j: k is uniform across a wave;
 //   * the k-only part of an address (byte offset of tap (c, i, j) relative to the window's top-left tap, and the tap's number) comes from a
 //     128-entry LDS table per K-tile; the pixel-only part (base offset, one validity bit per tap) lives in registers; an element is one
@@ -24,7 +25,7 @@
 // LDS fragment by v_perm over 16-entry code tables (qbits_a8_fused.hip's nibble scheme).  Two MX-format MFMAs per fragment into the SAME fp32
 // accumulator: lo with weight block scale 2^0, hi with 2^4 - the fold 16 hi + lo happens exactly inside the matrix pipe (an e4m3 / e5m2 value times
 // an integer of magnitude <= 128 is exact in fp32), no extra accumulator set, no fp32 math between the MFMAs.
-// K split (grids that cannot fill the chip): qconv_mfma.hip's scheme - split z parks its int32 / fp32 tile in `partials`, a separate kernel adds the
+// K split (grids that cannot fill the chip): split z parks its int32 / fp32 tile in `partials`, a separate kernel adds the
 // splits in split order (deterministic; int32: bit-identical to the unsplit result) and runs the epilogue.
 #include <type_traits>
 
@@ -44,9 +45,7 @@ enum { F_E4M3 = 0, F_E5M2 = 1 };              // cbsz / blgp codes of the MX-for
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-struct __attribute__((packed, aligned(1))) U4u { uint32_t x, y, z, w; };  // byte-aligned 16-byte load (K need not be a multiple of anything)
-
-__device__ __forceinline__ int lds_off(int row, int kc) { return row * BK + ((kc ^ (row & 7)) << 4); }
+static_assert(BK == kConvRowBytes, "a K-tile of one-byte elements is one LDS row of conv_lds_off");
 
 struct Args {
   const uint8_t* x;       // [B, cin, H, W] int8 / fp8 codes
@@ -60,67 +59,17 @@ struct Args {
   int out_dtype;          // QUANTO_HIP_{F32, F16, BF16}
   int S;                  // K split over blockIdx.z
   void* partials;         // [S][tiles][8 waves][8 fragments][64 lanes] 16 bytes (int32 / fp32)
-  uint32_t khw_magic, kw_magic;  // ceil(2^32 / (KH KW)), ceil(2^32 / KW); 0 when the divisor is 1
+  uint32_t khw_magic, kw_magic;  // ceil(2^32 / (KH KW)), ceil(2^32 / KW); 0 when the divisor is 1 (conv_fill_ktab)
 };
-static uint32_t div_magic(int d) { return d <= 1 ? 0u : (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d); }
 
-// ---- epilogue: the lane's 4 x 2 fragments (D row = pixel (lane >> 4) * 4 + r of fragment i, column = channel lane & 15 of fragment j) -> NCHW;
-// the lane's four rows are four neighbouring pixels of one channel plane: one 8- / 16-byte store when they lie in one image and are aligned
+// ---- epilogue (conv_store_tile): the channel's factor is the scale product rounded to the output dtype, as torch multiplies the two scale tensors
 template <int DT, typename AV>
 __device__ __forceinline__ void store_tile_dt(const Args& a, const AV (&acc)[4][2], int m0, int nt, int wm, int wn, int lane) {
   using E = Elem<DT>;
   using T = typename E::T;
-  T* yg = reinterpret_cast<T*>(a.y);
-  const int M = a.M, N = a.N, L = a.OH * a.OW;
-  const bool vec = (L & 3) == 0 && (reinterpret_cast<uintptr_t>(a.y) & (4 * sizeof(T) - 1)) == 0;
   const float as = E::to_f32(*reinterpret_cast<const T*>(a.a_scale));
-  int bq[4], lq[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
-    const int b = m / L;
-    bq[i] = b;
-    lq[i] = m - b * L;
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = nt * BN + wn * 32 + j * 16 + (lane & 15);
-    if (n >= N) continue;
-    const float sc = E::to_f32(E::from_f32(as * E::to_f32(reinterpret_cast<const T*>(a.w_scale)[n])));  // the scale product in the dtype
-    const bool has_bias = a.bias != nullptr;
-    const float bv = has_bias ? E::to_f32(reinterpret_cast<const T*>(a.bias)[n]) : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
-      if (m >= M) continue;
-      T out[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = (float)acc[i][j][r] * sc;
-        asm volatile("" : "+v"(v));  // product rounded to fp32 first (no single-rounding v_fma_mixlo_f16)
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv;
-        out[r] = E::from_f32(v);
-      }
-      T* dst = yg + ((size_t)bq[i] * N + n) * L + lq[i];
-      if (vec && m + 3 < M) {
-        if constexpr (sizeof(T) == 2)
-          *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(out);
-        else
-          *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(out);
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (m + r < M) {
-            int bb = bq[i], ll = lq[i] + r;
-            while (ll >= L) {  // an image ends inside the lane's four pixels
-              ll -= L;
-              ++bb;
-            }
-            yg[((size_t)bb * N + n) * L + ll] = out[r];
-          }
-      }
-    }
-  }
+  conv_store_tile<DT, 1, CONV_EPI_8BIT>(a, acc, m0, nt, wm, wn, lane,
+                                        [&](int n) { return E::to_f32(E::from_f32(as * E::to_f32(reinterpret_cast<const T*>(a.w_scale)[n]))); });
 }
 template <typename AV>
 __device__ __forceinline__ void store_tile(const Args& a, const AV (&acc)[4][2], int m0, int nt, int wm, int wn, int lane) {
@@ -158,6 +107,8 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.x), 0, (int)(((long)M / (a.OH * a.OW)) * a.cin * a.H * a.W), 0x00020000);
 
   // ---- the thread's pixel: byte offset of element (b, 0, oh sh, ow sw) and one validity bit per tap (set: inside the image) ----
+  // (The one-pixel case of qconv_mfma.hip's prologue; a change to the border handling belongs in both.  Kept here in its own wording: in that
+  // file's wording, as a function or as a macro, hipcc gives every kernel of this file another instruction stream - DESIGN.md 4.8.)
   uint32_t px_off;
   uint64_t ok0 = 0, ok1 = 0;
   {
@@ -180,27 +131,7 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
         }
       }
   }
-  auto tap_ok = [&](int tp) -> int {  // -1: tap tp lies inside the image
-    if constexpr (WIDE)
-      return -(int)((((tp & 64) ? ok1 : ok0) >> (tp & 63)) & 1ull);
-    else
-      return __builtin_amdgcn_sbfe((uint32_t)ok0, tp, 1);
-  };
   int2* ktab = reinterpret_cast<int2*>(smem + 2 * 2 * TILE_BYTES);  // [2][128] {byte offset relative to px_off, tap number}
-  auto div_small = [](int n, int d, uint32_t magic, int& rem) {  // exact for n < 2^24, d <= 127 (qconv_mfma.hip)
-    const int q = magic ? (int)__umulhi((uint32_t)n, magic) : n;
-    rem = n - q * d;
-    return q;
-  };
-  auto fill_ktab = [&](int t) {
-    if (tid < BK) {
-      const int k = (kt_lo + t) * BK + tid;
-      int rem, kj;
-      const int ci = div_small(k, a.KH * a.KW, a.khw_magic, rem);
-      const int ki = div_small(rem, a.KW, a.kw_magic, kj);
-      ktab[(t & 1) * BK + tid] = k < K ? make_int2((ci * a.H + ki * a.dh) * a.W + kj * a.dw - (a.ph * a.W + a.pw), rem) : make_int2(0, NO_TAP);
-    }
-  };
 
   // ---- staging registers: 2 x 16 gathered bytes, 32 weight bytes (channel tid >> 2, bytes 32 (tid & 3) ..) ----
   uint8_t g[2][16];
@@ -217,7 +148,7 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
         const int off[4] = {t0.x, t0.z, t1.x, t1.z}, tap[4] = {t0.y, t0.w, t1.y, t1.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          g[j][4 * h + q] = __builtin_amdgcn_raw_buffer_load_b8(xrsrc, (px_off + (uint32_t)off[q]) | ~(uint32_t)tap_ok(tap[q]), 0, 0);
+          g[j][4 * h + q] = __builtin_amdgcn_raw_buffer_load_b8(xrsrc, (px_off + (uint32_t)off[q]) | ~(uint32_t)conv_tap_ok<WIDE>(ok0, ok1, tap[q]), 0, 0);
       }
     }
     int n = nt * BN + (tid >> 2);
@@ -244,12 +175,12 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
     uint8_t* sb = sa + TILE_BYTES;
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-      *reinterpret_cast<uint4*>(sa + lds_off(tid & 127, (tid >> 7) + 4 * j)) =
+      *reinterpret_cast<uint4*>(sa + conv_lds_off(tid & 127, (tid >> 7) + 4 * j)) =
           make_uint4(pack4(g[j][0], g[j][1], g[j][2], g[j][3]), pack4(g[j][4], g[j][5], g[j][6], g[j][7]),
                      pack4(g[j][8], g[j][9], g[j][10], g[j][11]), pack4(g[j][12], g[j][13], g[j][14], g[j][15]));
     const int row = tid >> 2, part = tid & 3;
-    *reinterpret_cast<uint4*>(sb + lds_off(row, 2 * part)) = rw[0];
-    *reinterpret_cast<uint4*>(sb + lds_off(row, 2 * part + 1)) = rw[1];
+    *reinterpret_cast<uint4*>(sb + conv_lds_off(row, 2 * part)) = rw[0];
+    *reinterpret_cast<uint4*>(sb + conv_lds_off(row, 2 * part + 1)) = rw[1];
   };
 
   AV acc[4][2];
@@ -265,9 +196,9 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
     for (int h = 0; h < 2; ++h) {
       const int kc = h * 4 + (lane >> 4);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) fa[h][i] = *reinterpret_cast<const uint4*>(sa + lds_off(wm * 64 + i * 16 + (lane & 15), kc));
+      for (int i = 0; i < 4; ++i) fa[h][i] = *reinterpret_cast<const uint4*>(sa + conv_lds_off(wm * 64 + i * 16 + (lane & 15), kc));
 #pragma unroll
-      for (int j = 0; j < 2; ++j) fb[h][j] = *reinterpret_cast<const uint4*>(sb + lds_off(wn * 32 + j * 16 + (lane & 15), kc));
+      for (int j = 0; j < 2; ++j) fb[h][j] = *reinterpret_cast<const uint4*>(sb + conv_lds_off(wn * 32 + j * 16 + (lane & 15), kc));
     }
     auto cat = [](const uint4& lo, const uint4& hi) { return i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w}; };
     if constexpr (KIND == K_I8) {
@@ -311,8 +242,8 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
     }
   };
 
-  fill_ktab(0);
-  if (nk > 1) fill_ktab(1);
+  conv_fill_ktab<1, BK, NO_TAP>(a, ktab, kt_lo, 0, tid);
+  if (nk > 1) conv_fill_ktab<1, BK, NO_TAP>(a, ktab, kt_lo, 1, tid);
   __syncthreads();
   issue_loads(0);
   write_lds(0);
@@ -320,7 +251,7 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
   int cur = 0;
   for (int kt = 0; kt < nk; ++kt) {
     if (kt + 1 < nk) issue_loads(kt + 1);
-    if (kt + 2 < nk) fill_ktab(kt + 2);  // into the table buffer tile kt's gather last read; visible after this iteration's barrier
+    if (kt + 2 < nk) conv_fill_ktab<1, BK, NO_TAP>(a, ktab, kt_lo, kt + 2, tid);  // into the table buffer tile kt's gather last read; visible after this iteration's barrier
     const uint8_t* sa = smem + cur * 2 * TILE_BYTES;
     mma_phase(sa, sa + TILE_BYTES);
     if (kt + 1 < nk) write_lds(cur ^ 1);
@@ -328,14 +259,7 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
     cur ^= 1;
   }
 
-  if (S > 1) {  // park the partial sums: one 1 KiB store per wave and fragment
-    AV* mine = reinterpret_cast<AV*>(a.partials) + ((size_t)(sp * gridDim.y + blockIdx.y) * gridDim.x + nt) * (8 * 8 * 64) + (wave * 8) * 64 + lane;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) mine[(i * 2 + j) * 64] = acc[i][j];
-    return;
-  }
+  if (S > 1) return conv_park_tile(a.partials, sp, nt, wave, lane, acc);
   store_tile(a, acc, m0, nt, wm, wn, lane);
 }
 
@@ -347,13 +271,6 @@ __global__ void __launch_bounds__(64) qconv2d_a8_reduce_kernel(const Args a) {
   AV acc[4][2];
   QH_CONV_SPLIT_SUM(AV, a.partials, S, lane, wave, acc);
   store_tile(a, acc, blockIdx.y * BM, blockIdx.x, wave >> 2, wave & 3, lane);
-}
-
-// conv::geometry_ok of qconv_mfma.hip (one validity bit per tap, 31-bit offsets, grid.y), with one-byte activations
-static bool geometry_ok(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW) {
-  const int64_t K = cin * KH * KW;
-  return B >= 1 && OH >= 1 && OW >= 1 && K >= 1 && K < (1ll << 24) && KH * KW <= 127 && B * cin * H * W < (1ll << 30) && B * OC * OH * OW < (1ll << 31) &&
-         OC * K < (1ll << 31) && (B * OH * OW + BM - 1) / BM <= 65535;
 }
 
 template <int KIND, int AF, int BF, bool WIDE>
@@ -382,25 +299,19 @@ int qbytes_conv2d_a8_kind(int a_dtype, int b_dtype, int out_dtype) {
   return -1;
 }
 
-bool qbytes_conv2d_a8_geometry_ok(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW) {
-  return conv8::geometry_ok(B, cin, H, W, OC, KH, KW, OH, OW);
-}
-
 size_t conv2d_a8_workspace(int64_t M, int64_t N, int64_t K) { return conv_split_workspace<conv8::BM, conv8::BN>(M, N, conv_pick_split<conv8::BK, conv8::BM, conv8::BN>(M, N, K)); }
 
-// *kind: the conv8::Kind that ran.  The caller has validated the arguments and the format (qbytes_conv2d_a8_kind >= 0, geometry_ok).
-int qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, int64_t B, int64_t cin, int64_t H,
-                     int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int sh, int sw, int ph, int pw, int dh, int dw, int a_dtype,
+// *kind: the conv8::Kind that ran.  The caller has validated the arguments and the format (qbytes_conv2d_a8_kind >= 0, conv_geometry_ok).
+int qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, const ConvGeom& g, int a_dtype,
                      int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
   using namespace conv8;
   const int k = qbytes_conv2d_a8_kind(a_dtype, b_dtype, out_dtype);
-  if (k < 0 || !geometry_ok(B, cin, H, W, OC, KH, KW, OH, OW)) return QUANTO_HIP_ENOTSUP;
-  Args a{reinterpret_cast<const uint8_t*>(x), a_scale, reinterpret_cast<const uint8_t*>(w), w_scale, bias, y, (int)(B * OH * OW), (int)OC,
-         (int)(cin * KH * KW), (int)cin, (int)H, (int)W, (int)KH, (int)KW, (int)OH, (int)OW, sh, sw, ph, pw, dh, dw, out_dtype, 1, nullptr,
-         div_magic((int)(KH * KW)), div_magic((int)KW)};
-  int S = conv_pick_split<BK, BM, BN>(a.M, a.N, a.K);
-  if (S > 1 && !ws_holds(workspace, workspace_bytes, conv_split_workspace<BM, BN>(a.M, a.N, S))) S = 1;
-  a.S = S;
+  if (k < 0 || !conv_geometry_ok(g)) return QUANTO_HIP_ENOTSUP;
+  Args a{};
+  a.x = reinterpret_cast<const uint8_t*>(x), a.a_scale = a_scale, a.w = reinterpret_cast<const uint8_t*>(w), a.w_scale = w_scale, a.bias = bias, a.y = y;
+  a.out_dtype = out_dtype;
+  conv_set_geometry(a, g);
+  const int S = a.S = conv_plan_split<BK, BM, BN>(a.M, a.N, a.K, workspace, workspace_bytes);
   a.partials = workspace;
   const int ntiles = (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;
   const bool ae5 = a_dtype == QUANTO_HIP_F8_E5M2, be5 = b_dtype == QUANTO_HIP_F8_E5M2;

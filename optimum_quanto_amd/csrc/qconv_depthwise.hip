@@ -13,7 +13,7 @@
 //     arithmetic contract of the dense convolution kernel (qconv_mfma.hip).
 #include <type_traits>
 
-#include "qh_common.h"
+#include "qh_conv.h"
 
 namespace qh {
 namespace dw {
@@ -264,22 +264,23 @@ static int launch(const Args& a, hipStream_t stream) {
 
 }  // namespace dw
 
-bool qbytes_conv2d_depthwise_supported(int64_t B, int64_t C, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int sh, int sw,
-                                       int ph, int pw, int dh, int dw, int a_dtype, int b_dtype, int out_dtype) {
+bool qbytes_conv2d_depthwise_supported(const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype) {
   const bool wd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2;
   const bool ad = (a_dtype == QUANTO_HIP_BF16 || a_dtype == QUANTO_HIP_F16) && out_dtype == a_dtype;
-  if (!wd || !ad || B < 1 || C < 1 || OC < C || OC % C != 0 || KH < 1 || KW < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0) return false;
-  if (OH != (H + 2 * ph - dh * (KH - 1) - 1) / sh + 1 || OW != (W + 2 * pw - dw * (KW - 1) - 1) / sw + 1 || OH < 1 || OW < 1) return false;
-  return B * C * H * W < (1ll << 31) && B * OC * OH * OW < (1ll << 31) && KH * KW <= 4096 && H < (1 << 20) && W < (1 << 20);
+  if (!wd || !ad || g.B < 1 || g.cin < 1 || g.OC < g.cin || g.OC % g.cin != 0 || g.KH < 1 || g.KW < 1 || g.sh < 1 || g.sw < 1 || g.dh < 1 || g.dw < 1 ||
+      g.ph < 0 || g.pw < 0)
+    return false;
+  if (g.OH != (g.H + 2 * g.ph - g.dh * (g.KH - 1) - 1) / g.sh + 1 || g.OW != (g.W + 2 * g.pw - g.dw * (g.KW - 1) - 1) / g.sw + 1 || g.OH < 1 || g.OW < 1) return false;
+  return g.B * g.cin * g.H * g.W < (1ll << 31) && g.B * g.OC * g.OH * g.OW < (1ll << 31) && g.KH * g.KW <= 4096 && g.H < (1 << 20) && g.W < (1 << 20);
 }
 
-int qbytes_conv2d_depthwise(const void* x, const void* w, const void* scales, const void* bias, void* y, int64_t B, int64_t C, int64_t H, int64_t W,
-                            int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int sh, int sw, int ph, int pw, int dh, int dw, int a_dtype,
-                            int b_dtype, int out_dtype, hipStream_t stream, bool* strip) {
+// g.cin: the channels C of x (one group each)
+int qbytes_conv2d_depthwise(const void* x, const void* w, const void* scales, const void* bias, void* y, const ConvGeom& g, int a_dtype, int b_dtype,
+                            int out_dtype, hipStream_t stream, bool* strip) {
   *strip = false;
-  if (!qbytes_conv2d_depthwise_supported(B, C, H, W, OC, KH, KW, OH, OW, sh, sw, ph, pw, dh, dw, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  const dw::Args a{x, reinterpret_cast<const uint8_t*>(w), scales, bias, y, (int)B, (int)C, (int)H, (int)W, (int)OC, (int)(OC / C), (int)KH, (int)KW, (int)OH,
-                   (int)OW, sh, sw, ph, pw, dh, dw, (int)((OW + dw::PX - 1) / dw::PX)};
+  if (!qbytes_conv2d_depthwise_supported(g, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
+  const dw::Args a{x, reinterpret_cast<const uint8_t*>(w), scales, bias, y, (int)g.B, (int)g.cin, (int)g.H, (int)g.W, (int)g.OC, (int)(g.OC / g.cin), (int)g.KH,
+                   (int)g.KW, (int)g.OH, (int)g.OW, g.sh, g.sw, g.ph, g.pw, g.dh, g.dw, (int)((g.OW + dw::PX - 1) / dw::PX)};
 #define QH_DW(DT)                                                                                       \
   if (b_dtype == QUANTO_HIP_I8) return dw::launch<DT, QUANTO_HIP_I8>(a, stream);                         \
   if (b_dtype == QUANTO_HIP_F8_E4M3FN) return dw::launch<DT, QUANTO_HIP_F8_E4M3FN>(a, stream);           \

@@ -27,6 +27,8 @@
 // History (profiles/r04_qconv2d_*.jsonl, r05_qconv2d_*.jsonl): first form - four pixels per thread, a counted (c, i, j) walk and four compares per
 // element, four waves (inside qmm_mfma.hip) - 3.7 us per K-tile whatever M was; the table on four waves 2.0; eight waves 1.85 (r4); buffer-load
 // gather, pixel pairs, magic-number table, 8-byte epilogue stores (r5): ~1.2 us per K-tile; DESIGN.md 4.8.
+// What the tap gather shares with qconv_a8.hip (the same gather over one-byte elements) lives in qh_conv.h: LDS layout, tap table, validity test,
+// partial-tile store, split plan and reduce, the geometry (ConvGeom) and its rule.
 #include <type_traits>
 
 #include "qh_conv.h"
@@ -47,15 +49,7 @@ constexpr int LDS_BYTES = 2 * 2 * TILE_BYTES + 2 * BK * 8;
 enum WFmt { W_I8 = 0, W_F8E4M3 = 1, W_F8E5M2 = 2, W_I4R = 3, W_I2R = 4, W_DENSE16 = 5 };  // W_DENSE16 (row form only): a weight already in the activation dtype
 constexpr int planes_of(int fmt) { return fmt == W_I4R ? 2 : (fmt == W_I2R ? 4 : 1); }  // values per packed byte
 
-// byte-aligned 8- and 16-byte loads (K = cin KH KW need not be a multiple of anything: an RGB stem has K = 27 or 147): hipcc lowers them to
-// global_load_dwordx2 / x4, which the gfx950 memory pipeline serves at any alignment (unaligned access mode, the HSA default)
-struct __attribute__((packed, aligned(1))) U4u { uint32_t x, y, z, w; };
-struct __attribute__((packed, aligned(1))) U2u { uint32_t x, y; };
-struct __attribute__((packed, aligned(1))) U1u { uint32_t x; };
-
-// 128-byte rows of eight 16-byte chunks; chunk kc of row r sits at position kc ^ (r & 7): the fragment reads (16 rows x 4 chunks) and the staging
-// writes are conflict-free
-__device__ __forceinline__ int lds_off(int row, int kc) { return row * (BK * 2) + ((kc ^ (row & 7)) << 4); }
+static_assert(BK * 2 == kConvRowBytes, "a K-tile of two-byte elements is one LDS row of conv_lds_off");
 
 template <int DT>
 __device__ __forceinline__ uint32_t pack_rne(float a, float b) {
@@ -161,84 +155,18 @@ struct Args {
   // ([S][tiles][8 waves][8 fragments][64 lanes] float4: whole lines per store); qconv2d_reduce_kernel adds them in split order and runs the epilogue
   int S;
   float* partials;
-  uint32_t khw_magic, kw_magic;  // ceil(2^32 / (KH KW)), ceil(2^32 / KW); 0 when the divisor is 1 (fill_ktab)
+  uint32_t khw_magic, kw_magic;  // ceil(2^32 / (KH KW)), ceil(2^32 / KW); 0 when the divisor is 1 (conv_fill_ktab)
   uint32_t kh_magic;             // ceil(2^32 / KH) (row form)
 };
-static uint32_t div_magic(int d) { return d <= 1 ? 0u : (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d); }
 
-// the lane's 4 x 2 accumulator fragments -> output: D row = pixel (lane >> 4) * 4 + r of fragment i, D column = channel lane & 15 of fragment j; NCHW:
-// the lane's four rows are four neighbouring pixels of one channel plane - ONE 8-byte store when they lie in one image and the plane size is a
-// multiple of 4 (r5; before: four 2-byte stores, each with its own integer division by the plane size - the epilogue and the prologue were a
-// third of a (8,128,56,56) -> 128 call, profiles/r05_qconv2d_ablations.jsonl).  m < 2^24 (geometry_ok): m / L through the fp32 reciprocal, corrected.
+// epilogue (conv_store_tile): the channel's factor is the 8-bit weight's scale[n]; 1 for sub-byte weights (dequantized at staging) and dense ones
 template <int DT, int PL>
 __device__ __forceinline__ void store_tile(const Args& a, const f32x4 (&acc)[4][2], int m0, int nt, int wm, int wn, int lane) {
   using E = Elem<DT>;
   using T = typename E::T;
-  T* yg = reinterpret_cast<T*>(a.y);
-  const int M = a.M, N = a.N, P = N / (PL > 1 ? PL : 2), L = a.OH * a.OW;
-  const float r_l = 1.0f / (float)L;
-  const bool vec = (L & 3) == 0 && (reinterpret_cast<uintptr_t>(a.y) & 7) == 0;
-  int bq[4], lq[4];  // image and offset inside the plane of the first of the lane's four pixels of fragment i
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
-    int b = (int)((float)m * r_l), l = m - b * L;
-    if (l < 0) {
-      --b;
-      l += L;
-    } else if (l >= L) {
-      ++b;
-      l -= L;
-    }
-    bq[i] = b;
-    lq[i] = l;
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int tc = wn * 32 + j * 16 + (lane & 15);
-    int n;
-    if constexpr (PL > 1) {  // the tile's 128 columns are (128 / PL) packed rows x PL planes; plane pl holds channels pl * P + p
-      constexpr int RPT = BN / PL;
-      const int p = nt * RPT + (tc % RPT);
-      n = p < P ? p + (tc / RPT) * P : -1;
-    } else {
-      n = nt * BN + tc;
-      n = n < N ? n : -1;
-    }
-    if (n < 0) continue;
-    float sc = 1.f;
-    if (PL == 1 && a.scale != nullptr) sc = E::to_f32(reinterpret_cast<const T*>(a.scale)[n]);  // (no scale: a dense weight)
-    const bool has_bias = a.bias != nullptr;
-    const float bv = has_bias ? E::to_f32(reinterpret_cast<const T*>(a.bias)[n]) : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
-      if (m >= M) continue;
-      T out[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[i][j][r] * sc;
-        asm volatile("" : "+v"(v));  // product rounded to fp32 first, with and without bias (no single-rounding v_fma_mixlo_f16)
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv;  // the reference's order: rounded convolution output + bias, rounded again
-        out[r] = E::from_f32(v);
-      }
-      T* dst = yg + ((size_t)bq[i] * N + n) * L + lq[i];
-      if (vec && m + 3 < M) {  // (L % 4 == 0 and m % 4 == 0: the four pixels are in one image, 8-byte aligned)
-        *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(out);
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (m + r < M) {
-            int bb = bq[i], ll = lq[i] + r;
-            while (ll >= L) {  // an image ends inside the lane's four pixels (planes of fewer than 4 pixels: more than once)
-              ll -= L;
-              ++bb;
-            }
-            yg[((size_t)bb * N + n) * L + ll] = out[r];
-          }
-      }
-    }
-  }
+  conv_store_tile<DT, PL, CONV_EPI_16BIT>(a, acc, m0, nt, wm, wn, lane, [&](int n) {
+    return PL == 1 && a.scale != nullptr ? E::to_f32(reinterpret_cast<const T*>(a.scale)[n]) : 1.f;
+  });
 }
 
 // The same epilogue through LDS (r5): store_tile's lanes hold four pixels of ONE channel each - a wave's store touches 16 channel planes with 32
@@ -340,13 +268,15 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_mfma_kernel(const Args a) {
   const int kt_lo = (int)((long)sp * nk_all / S), nk = (int)((long)(sp + 1) * nk_all / S) - kt_lo;  // this split's K-tiles: kt_lo + t, t = 0 .. nk - 1
   const int P = N / (PL > 1 ? PL : 2);  // packed rows (int4 / int2)
   const uint8_t* xb = reinterpret_cast<const uint8_t*>(a.x);
-  // x as a raw buffer whose range is its true size (geometry_ok: < 2^31 bytes): an offset of 0xFFFFFFFF reads as 0
+  // x as a raw buffer whose range is its true size (conv_geometry_ok: < 2^31 bytes): an offset of 0xFFFFFFFF reads as 0
   const __amdgpu_buffer_rsrc_t xrsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, (int)(((long)M / (a.OH * a.OW)) * a.cin * a.H * a.W * 2), 0x00020000);
 
   // ---- the thread's pixel (PAIR: its two pixels m, m + 1) ------------------------------------------------------------------------------------
   // px_off: byte offset of input element (b, 0, oh sh, ow sw) - the window's top-left tap shifted right / down by the padding.
   // Bit i KW + j of a validity word (64 taps per word; narrow: 32 bits) is SET when tap (i, j) of the pixel's window lies inside the image.
+  // (qconv_a8.hip has the one-pixel case in its own wording; a change to the border handling belongs in both - neither wording compiles to the
+  // other file's listing)
   uint32_t px_off;
   uint64_t ok_a0 = 0, ok_a1 = 0, ok_b0 = 0, ok_b1 = 0;  // first / second pixel of the pair, taps 0..63 / 64..127 (scalars: a dynamically indexed array would live in scratch)
   {
@@ -373,32 +303,9 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_mfma_kernel(const Args a) {
         }
       }
   }
-  // -1 when tap `tp` of pixel `px` of the pair lies inside the image, else 0
-  auto tap_ok = [&](int px, int tp) -> int {
-    const uint64_t w0 = px ? ok_b0 : ok_a0, w1 = px ? ok_b1 : ok_a1;  // (px is a literal at every call)
-    if constexpr (WIDE)
-      return -(int)((((tp & 64) ? w1 : w0) >> (tp & 63)) & 1ull);
-    else
-      return __builtin_amdgcn_sbfe((uint32_t)w0, tp, 1);
-  };
+  // -1 when tap `tp` of pixel `px` of the pair (a literal at every call) lies inside the image, else 0
+  auto tap_ok = [&](int px, int tp) -> int { return conv_tap_ok<WIDE>(px ? ok_b0 : ok_a0, px ? ok_b1 : ok_a1, tp); };
   int2* ktab = reinterpret_cast<int2*>(smem + 2 * 2 * TILE_BYTES);  // [2][64] {byte offset relative to px_off (signed), tap number}
-  // k -> (channel, tap row, tap column): two divisions by small run-time constants per table entry, done by ONE wave per K-tile while the other
-  // seven wait for it at the barrier.  As integer divisions they were ~60 of that wave's instructions per tile; here q = mulhi(n, ceil(2^32 / d)),
-  // exact for n < 2^24 and d <= 127 (n (M d - 2^32) < 2^24 * 127 < 2^32); the magic numbers come from the host (0: d = 1)
-  auto div_small = [](int n, int d, uint32_t magic, int& rem) {
-    const int q = magic ? (int)__umulhi((uint32_t)n, magic) : n;
-    rem = n - q * d;
-    return q;
-  };
-  auto fill_ktab = [&](int t) {
-    if (tid < BK && !((QH_CONV_ABLATE & 32) && t > 1)) {
-      const int k = (kt_lo + t) * BK + tid;
-      int rem, kj;
-      const int ci = div_small(k, a.KH * a.KW, a.khw_magic, rem);
-      const int ki = div_small(rem, a.KW, a.kw_magic, kj);
-      ktab[(t & 1) * BK + tid] = k < K ? make_int2(2 * ((ci * a.H + ki * a.dh) * a.W + kj * a.dw - (a.ph * a.W + a.pw)), rem) : make_int2(0, NO_TAP);
-    }
-  };
 
   // ---- staging registers --------------------------------------------------------------------------------------------------------------------
   // gathered elements of the K-tile in flight (taps over the padding read 0).  16-bit variables on purpose: as uint32_t the zero-extension (a v_and
@@ -497,38 +404,38 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_mfma_kernel(const Args a) {
       for (int q = 0; q < 8; ++q) d[q] = __builtin_amdgcn_perm(g_pair[q], 0u, g_sel[q]);  // [first pixel | second pixel] of tap q, realigned, padding zeroed
       const int row = 2 * (tid & 63);
       // first pixel: the low halves of the eight dwords; second pixel: the high halves
-      *reinterpret_cast<uint4*>(sa + lds_off(row, wave)) =
+      *reinterpret_cast<uint4*>(sa + conv_lds_off(row, wave)) =
           make_uint4(__builtin_amdgcn_perm(d[1], d[0], 0x05040100u), __builtin_amdgcn_perm(d[3], d[2], 0x05040100u),
                      __builtin_amdgcn_perm(d[5], d[4], 0x05040100u), __builtin_amdgcn_perm(d[7], d[6], 0x05040100u));
-      *reinterpret_cast<uint4*>(sa + lds_off(row + 1, wave)) =
+      *reinterpret_cast<uint4*>(sa + conv_lds_off(row + 1, wave)) =
           make_uint4(__builtin_amdgcn_perm(d[1], d[0], 0x07060302u), __builtin_amdgcn_perm(d[3], d[2], 0x07060302u),
                      __builtin_amdgcn_perm(d[5], d[4], 0x07060302u), __builtin_amdgcn_perm(d[7], d[6], 0x07060302u));
     } else {
 #pragma unroll
       for (int j = 0; j < 2; ++j)
-        *reinterpret_cast<uint4*>(sa + lds_off(tid & 127, (tid >> 7) + 4 * j)) =
+        *reinterpret_cast<uint4*>(sa + conv_lds_off(tid & 127, (tid >> 7) + 4 * j)) =
             make_uint4(pack16(g_raw[j][0], g_raw[j][1]), pack16(g_raw[j][2], g_raw[j][3]), pack16(g_raw[j][4], g_raw[j][5]), pack16(g_raw[j][6], g_raw[j][7]));
     }
     if constexpr (PL == 2) {
       uint4 lo, hi;
       convert8_i4r<DT, INT_SHIFT>(make_uint2(rw.x, rw.y), rs[0], rz[0], rs[1], rz[1], lo, hi);
       const int row = tid >> 3, part = tid & 7;
-      *reinterpret_cast<uint4*>(sb + lds_off(row, part)) = lo;
-      *reinterpret_cast<uint4*>(sb + lds_off(64 + row, part)) = hi;
+      *reinterpret_cast<uint4*>(sb + conv_lds_off(row, part)) = lo;
+      *reinterpret_cast<uint4*>(sb + conv_lds_off(64 + row, part)) = hi;
     } else if constexpr (PL == 4) {
       if (tid < RPT * 8) {
         uint4 o[4];
         convert8_i2r<DT, INT_SHIFT>(make_uint2(rw.x, rw.y), rs, rz, o);
         const int row = tid >> 3, part = tid & 7;
 #pragma unroll
-        for (int pl = 0; pl < 4; ++pl) *reinterpret_cast<uint4*>(sb + lds_off(pl * RPT + row, part)) = o[pl];
+        for (int pl = 0; pl < 4; ++pl) *reinterpret_cast<uint4*>(sb + conv_lds_off(pl * RPT + row, part)) = o[pl];
       }
     } else {
       uint4 c0, c1;
       convert16<DT, FMT>(rw, c0, c1);
       const int row = tid >> 2, part = tid & 3;
-      *reinterpret_cast<uint4*>(sb + lds_off(row, 2 * part)) = c0;
-      *reinterpret_cast<uint4*>(sb + lds_off(row, 2 * part + 1)) = c1;
+      *reinterpret_cast<uint4*>(sb + conv_lds_off(row, 2 * part)) = c0;
+      *reinterpret_cast<uint4*>(sb + conv_lds_off(row, 2 * part + 1)) = c1;
     }
   };
 
@@ -538,8 +445,8 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_mfma_kernel(const Args a) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  fill_ktab(0);
-  if (nk > 1) fill_ktab(1);
+  conv_fill_ktab<2, BK, NO_TAP>(a, ktab, kt_lo, 0, tid);
+  if (nk > 1) conv_fill_ktab<2, BK, NO_TAP>(a, ktab, kt_lo, 1, tid);
   __syncthreads();
   issue_loads(0);
   write_lds(0);
@@ -548,7 +455,7 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_mfma_kernel(const Args a) {
   for (int kt = 0; kt < nk; ++kt) {
     if (kt + 1 < nk) issue_loads(kt + 1);
     // table of tile kt + 2 into the buffer whose last reader was tile kt's gather (an iteration ago); visible after this iteration's barrier
-    if (kt + 2 < nk) fill_ktab(kt + 2);
+    if (kt + 2 < nk && !(QH_CONV_ABLATE & 32)) conv_fill_ktab<2, BK, NO_TAP>(a, ktab, kt_lo, kt + 2, tid);
     const uint8_t* sa = smem + cur * 2 * TILE_BYTES;
     const uint8_t* sb = sa + TILE_BYTES;
 #pragma unroll
@@ -556,9 +463,9 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_mfma_kernel(const Args a) {
       V8 fa[4], fb[2];
       const int kc = kk * 4 + (lane >> 4);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const V8*>(sa + lds_off(wm * 64 + i * 16 + (lane & 15), kc));
+      for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const V8*>(sa + conv_lds_off(wm * 64 + i * 16 + (lane & 15), kc));
 #pragma unroll
-      for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const V8*>(sb + lds_off(wn * 32 + j * 16 + (lane & 15), kc));
+      for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const V8*>(sb + conv_lds_off(wn * 32 + j * 16 + (lane & 15), kc));
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -569,14 +476,7 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_mfma_kernel(const Args a) {
     cur ^= 1;
   }
 
-  if (S > 1) {  // park the partial sums: one 1 KiB store per wave and fragment
-    f32x4* mine = reinterpret_cast<f32x4*>(a.partials) + ((size_t)(sp * gridDim.y + blockIdx.y) * gridDim.x + nt) * (8 * 8 * 64) + (wave * 8) * 64 + lane;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) mine[(i * 2 + j) * 64] = acc[i][j];
-    return;
-  }
+  if (S > 1) return conv_park_tile(a.partials, sp, nt, wave, lane, acc);
   if (epilogue_through_lds(a))
     store_tile_lds<DT, PL>(a, acc, m0, nt, wm, wn, lane, tid, smem);
   else
@@ -909,14 +809,7 @@ __global__ void __launch_bounds__(NT, DB ? 1 : 2) qconv2d_rows_kernel(const Args
   mma_phase(B0{});
   }
 
-  if (S > 1) {
-    f32x4* mine = reinterpret_cast<f32x4*>(a.partials) + ((size_t)(sp * gridDim.y + blockIdx.y) * gridDim.x + nt) * (8 * 8 * 64) + (wave * 8) * 64 + lane;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) mine[(i * 2 + j) * 64] = acc[i][j];
-    return;
-  }
+  if (S > 1) return conv_park_tile(a.partials, sp, nt, wave, lane, acc);
   if (QH_CONV_ABLATE & 128) {  // no epilogue (the accumulators stay alive)
     float t = 0.f;
 #pragma unroll
@@ -944,8 +837,8 @@ __global__ void __launch_bounds__(64) qconv2d_reduce_kernel(const Args a) {
 
 // row form: three taps wide, stride 1 / dilation 1 along the width, even OW (QUANTO_HIP_CONV_ROWS=0: the tap gather, 2: global loads - experiments)
 // (pixel pairs need stride 1 and an even OW; anything else three taps wide takes one pixel per thread; QUANTO_HIP_CONV_ROWS=3: one pixel per thread everywhere)
-static bool rows_eligible(int64_t cin, int64_t KH, int64_t KW, int64_t W, int64_t OW, int sw, int dw) {
-  return env_int("QUANTO_HIP_CONV_ROWS", 1) != 0 && KW == 3 && dw == 1 && W >= 4 && KH <= 31 && (cin * KH) % 8 == 0;
+static bool rows_eligible(const ConvGeom& g) {
+  return env_int("QUANTO_HIP_CONV_ROWS", 1) != 0 && g.KW == 3 && g.dw == 1 && g.W >= 4 && g.KH <= 31 && (g.cin * g.KH) % 8 == 0;
 }
 static bool rows_pairs(int64_t OW, int sw) { return sw == 1 && OW % 2 == 0 && env_int("QUANTO_HIP_CONV_ROWS", 1) != 3; }
 template <int DT, int FMT>
@@ -980,16 +873,13 @@ static void launch_k(const Args& a, int ntiles, int mtiles, hipStream_t stream) 
 }
 // *rows (when asked): whether the row form ran
 template <int DT, int FMT, bool INT_SHIFT, bool WIDE>
-static int launch_w(Args a, void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows) {
+static int launch_w(Args a, const ConvGeom& g, void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows) {
   constexpr int PL = planes_of(FMT);
   const int ntiles = PL > 1 ? (a.N / PL + BN / PL - 1) / (BN / PL) : (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;
-  int S = conv_pick_split<BK, BM, BN>(a.M, a.N, a.K);
-  if (S > 1 && !ws_holds(workspace, workspace_bytes, conv_split_workspace<BM, BN>(a.M, a.N, S))) S = 1;
-  a.S = S;
+  a.S = conv_plan_split<BK, BM, BN>(a.M, a.N, a.K, workspace, workspace_bytes);
   a.partials = reinterpret_cast<float*>(workspace);
   if constexpr (PL == 1 && !WIDE) {
-    if (rows_eligible(a.cin, a.KH, a.KW, a.W, a.OW, a.sw, a.dw)) {
-      a.S = S;
+    if (rows_eligible(g)) {
       if (rows) *rows = true;
       return launch_rows<DT, FMT>(a, ntiles, mtiles, stream);
     }
@@ -1000,28 +890,31 @@ static int launch_w(Args a, void* workspace, size_t workspace_bytes, hipStream_t
     launch_k<DT, FMT, INT_SHIFT, WIDE, true>(a, ntiles, mtiles, stream);
   else
     launch_k<DT, FMT, INT_SHIFT, WIDE, false>(a, ntiles, mtiles, stream);
-  if (S > 1) hipLaunchKernelGGL((qconv2d_reduce_kernel<DT, PL>), dim3(ntiles, mtiles, 8), dim3(64), 0, stream, a);
+  if (a.S > 1) hipLaunchKernelGGL((qconv2d_reduce_kernel<DT, PL>), dim3(ntiles, mtiles, 8), dim3(64), 0, stream, a);
   return launch_status();
 }
 template <int DT, int FMT, bool INT_SHIFT>
-static int launch(Args a, void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows = nullptr) {
-  return a.KH * a.KW > 31 ? launch_w<DT, FMT, INT_SHIFT, true>(a, workspace, workspace_bytes, stream, rows)
-                          : launch_w<DT, FMT, INT_SHIFT, false>(a, workspace, workspace_bytes, stream, rows);
+static int launch(const Args& a, const ConvGeom& g, void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows = nullptr) {
+  return a.KH * a.KW > 31 ? launch_w<DT, FMT, INT_SHIFT, true>(a, g, workspace, workspace_bytes, stream, rows)
+                          : launch_w<DT, FMT, INT_SHIFT, false>(a, g, workspace, workspace_bytes, stream, rows);
 }
 
-static bool geometry_ok(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW) {
-  const int64_t K = cin * KH * KW;
-  // one validity bit per tap (two mask words, one bit kept free); byte offsets into x and element offsets into y / w in 31 bits; grid.y
-  return B >= 1 && OH >= 1 && OW >= 1 && K >= 1 && K < (1ll << 24) && KH * KW <= 127 && B * cin * H * W < (1ll << 30) && B * OC * OH * OW < (1ll << 31) &&
-         OC * K < (1ll << 31) && (B * OH * OW + BM - 1) / BM <= 65535;  // (the K split is at most 64: grid.z)
+// the kernel arguments of a call, unsplit: the operands, the int4 / int2 grouping (C, G; 0 otherwise) and the geometry with its magic numbers
+static Args make_args(const void* x, const void* w, const void* scale, const void* shift, const void* bias, void* y, int64_t C, int64_t G, const ConvGeom& g) {
+  Args a{};
+  a.x = x, a.w = reinterpret_cast<const uint8_t*>(w), a.scale = scale, a.shift = shift, a.bias = bias, a.y = y;
+  a.C = (int)C, a.G = (int)G;
+  conv_set_geometry(a, g);
+  a.kh_magic = div_magic((int)g.KH);
+  a.S = 1;
+  return a;
 }
 
 }  // namespace conv
 
-bool qbytes_conv2d_supported(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int a_dtype,
-                             int b_dtype, int out_dtype) {
+bool qbytes_conv2d_supported(const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype) {
   const bool bd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2;
-  return bd && a_dtype == out_dtype && (out_dtype == QUANTO_HIP_BF16 || out_dtype == QUANTO_HIP_F16) && conv::geometry_ok(B, cin, H, W, OC, KH, KW, OH, OW);
+  return bd && a_dtype == out_dtype && (out_dtype == QUANTO_HIP_BF16 || out_dtype == QUANTO_HIP_F16) && conv_geometry_ok(g);
 }
 
 // scratch bytes the K split of a convolution wants (0: not split); the same for every weight format (128 x 128 tiles either way)
@@ -1032,35 +925,25 @@ size_t conv2d_workspace(int64_t M, int64_t N, int64_t K) { return conv_split_wor
 // workspace by the fused dequantize_qbits kernel (bit-identical to the reference's dequantize()) and the row form multiplies by that dense weight:
 // what the reference does, as two launches, without im2col.  Workspace: [dense weight, 256-byte multiple | K-split partials].
 size_t conv2d_dense_weight_bytes(int64_t N, int64_t K) { return ((size_t)N * K * 2 + 255) / 256 * 256; }
-bool conv2d_rows_eligible(int64_t cin, int64_t KH, int64_t KW, int64_t W, int64_t OW, int sw, int dw, int64_t OC) {
-  return conv::rows_eligible(cin, KH, KW, W, OW, sw, dw) && KH * KW <= 31 && OC * cin * KH * KW < (1ll << 30);
-}
-int qdense_conv2d_rows(const void* x, const void* wdense, const void* bias, void* y, int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH,
-                       int64_t KW, int64_t OH, int64_t OW, int sh, int sw, int ph, int pw, int dh, int dw, int dtype, void* workspace, size_t workspace_bytes,
+bool conv2d_rows_eligible(const ConvGeom& g) { return conv::rows_eligible(g) && g.KH * g.KW <= 31 && g.OC * g.K() < (1ll << 30); }
+int qdense_conv2d_rows(const void* x, const void* wdense, const void* bias, void* y, const ConvGeom& g, int dtype, void* workspace, size_t workspace_bytes,
                        hipStream_t stream) {
-  if (!conv2d_rows_eligible(cin, KH, KW, W, OW, sw, dw, OC) || !conv::geometry_ok(B, cin, H, W, OC, KH, KW, OH, OW) ||
-      (dtype != QUANTO_HIP_BF16 && dtype != QUANTO_HIP_F16))
-    return QUANTO_HIP_ENOTSUP;
-  conv::Args a{x, reinterpret_cast<const uint8_t*>(wdense), nullptr, nullptr, bias, y, (int)(B * OH * OW), (int)OC, (int)(cin * KH * KW), 0, 0,
-               (int)cin, (int)H, (int)W, (int)KH, (int)KW, (int)OH, (int)OW, sh, sw, ph, pw, dh, dw, 1, nullptr, conv::div_magic((int)(KH * KW)), conv::div_magic((int)KW), conv::div_magic((int)KH)};
+  if (!conv2d_rows_eligible(g) || !conv_geometry_ok(g) || (dtype != QUANTO_HIP_BF16 && dtype != QUANTO_HIP_F16)) return QUANTO_HIP_ENOTSUP;
   using namespace conv;
-  int S = conv_pick_split<BK, BM, BN>(a.M, a.N, a.K);
-  if (S > 1 && !ws_holds(workspace, workspace_bytes, conv_split_workspace<BM, BN>(a.M, a.N, S))) S = 1;
-  a.S = S;
+  Args a = make_args(x, wdense, nullptr, nullptr, bias, y, 0, 0, g);
+  a.S = conv_plan_split<BK, BM, BN>(a.M, a.N, a.K, workspace, workspace_bytes);
   a.partials = reinterpret_cast<float*>(workspace);
   const int ntiles = (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;
   return dtype == QUANTO_HIP_BF16 ? launch_rows<QUANTO_HIP_BF16, W_DENSE16>(a, ntiles, mtiles, stream) : launch_rows<QUANTO_HIP_F16, W_DENSE16>(a, ntiles, mtiles, stream);
 }
 
-int qbytes_conv2d_mfma(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC,
-                       int64_t KH, int64_t KW, int64_t OH, int64_t OW, int sh, int sw, int ph, int pw, int dh, int dw, int a_dtype, int b_dtype,
-                       int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows) {
+int qbytes_conv2d_mfma(const void* x, const void* w, const void* s, const void* bias, void* y, const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype,
+                       void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows) {
   *rows = false;
-  if (!qbytes_conv2d_supported(B, cin, H, W, OC, KH, KW, OH, OW, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  const conv::Args a{x, reinterpret_cast<const uint8_t*>(w), s, nullptr, bias, y, (int)(B * OH * OW), (int)OC, (int)(cin * KH * KW), 0, 0,
-                     (int)cin, (int)H, (int)W, (int)KH, (int)KW, (int)OH, (int)OW, sh, sw, ph, pw, dh, dw, 1, nullptr, conv::div_magic((int)(KH * KW)), conv::div_magic((int)KW), conv::div_magic((int)KH)};
+  if (!qbytes_conv2d_supported(g, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
   using namespace conv;
-#define QH_CASE(DT, FMT) return launch<DT, FMT, false>(a, workspace, workspace_bytes, stream, rows)
+  const Args a = make_args(x, w, s, nullptr, bias, y, 0, 0, g);
+#define QH_CASE(DT, FMT) return launch<DT, FMT, false>(a, g, workspace, workspace_bytes, stream, rows)
   if (out_dtype == QUANTO_HIP_BF16) {
     if (b_dtype == QUANTO_HIP_I8) QH_CASE(QUANTO_HIP_BF16, W_I8);
     if (b_dtype == QUANTO_HIP_F8_E4M3FN) QH_CASE(QUANTO_HIP_BF16, W_F8E4M3);
@@ -1074,21 +957,17 @@ int qbytes_conv2d_mfma(const void* x, const void* w, const void* s, const void* 
 
 // int4 / int2: group sizes that are multiples of 8 (a staging chunk of 8 k must not straddle groups) or per-channel scales; OC a multiple of the
 // values per byte (the planes of the generic packed layout)
-bool qbits_conv2d_supported(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, const PackedGeom& g,
-                            int dtype) {
-  return (g.bits == 4 || g.bits == 2) && g.N == OC && g.K == cin * KH * KW && OC % g.vpi == 0 && (g.C % 8 == 0 || g.G == 1) &&
-         (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) &&
-         OC * g.G < (1ll << 31) && conv::geometry_ok(B, cin, H, W, OC, KH, KW, OH, OW);
+bool qbits_conv2d_supported(const ConvGeom& cg, const PackedGeom& g, int dtype) {
+  return (g.bits == 4 || g.bits == 2) && g.N == cg.OC && g.K == cg.K() && cg.OC % g.vpi == 0 && (g.C % 8 == 0 || g.G == 1) &&
+         (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && cg.OC * g.G < (1ll << 31) && conv_geometry_ok(cg);
 }
 
-int qbits_conv2d_mfma(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t B, int64_t cin,
-                      int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int sh, int sw, int ph, int pw, int dh, int dw,
+int qbits_conv2d_mfma(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, const ConvGeom& cg,
                       const PackedGeom& g, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!qbits_conv2d_supported(B, cin, H, W, OC, KH, KW, OH, OW, g, dtype)) return QUANTO_HIP_ENOTSUP;
-  const conv::Args a{x, packed, scale, shift, bias, y, (int)(B * OH * OW), (int)OC, (int)(cin * KH * KW), (int)g.C, (int)g.G,
-                     (int)cin, (int)H, (int)W, (int)KH, (int)KW, (int)OH, (int)OW, sh, sw, ph, pw, dh, dw, 1, nullptr, conv::div_magic((int)(KH * KW)), conv::div_magic((int)KW), conv::div_magic((int)KH)};
+  if (!qbits_conv2d_supported(cg, g, dtype)) return QUANTO_HIP_ENOTSUP;
   using namespace conv;
-#define QH_CASE(DT, FMT) return int_shift ? launch<DT, FMT, true>(a, workspace, workspace_bytes, stream) : launch<DT, FMT, false>(a, workspace, workspace_bytes, stream)
+  const Args a = make_args(x, packed, scale, shift, bias, y, g.C, g.G, cg);
+#define QH_CASE(DT, FMT) return int_shift ? launch<DT, FMT, true>(a, cg, workspace, workspace_bytes, stream) : launch<DT, FMT, false>(a, cg, workspace, workspace_bytes, stream)
   if (g.bits == 4) {
     if (dtype == QUANTO_HIP_BF16) QH_CASE(QUANTO_HIP_BF16, W_I4R);
     QH_CASE(QUANTO_HIP_F16, W_I4R);

@@ -343,7 +343,7 @@ class _Bindings:
 
     @classmethod
     def conv2d_geometry_ok(cls, x_shape, w_shape, stride, padding, dilation) -> bool:
-        """Python mirror of ``conv::geometry_ok`` (csrc/qconv_mfma.hip): what the implicit-GEMM kernels index with 31-bit offsets and one grid
+        """Python mirror of ``conv_geometry_ok`` (csrc/qh_conv.h): what the implicit-GEMM kernels index with 31-bit offsets and one grid
         dimension.  Beyond these limits the C entry returns ENOTSUP; the callers ask here first and keep the im2col / reference path instead."""
         B, C, H, W = x_shape
         OC, _, KH, KW = w_shape

@@ -21,7 +21,9 @@ int main() {
     hipMemcpy(x, hx.data(), hx.size() * 2, hipMemcpyHostToDevice); hipMemcpy(w, hw.data(), hw.size(), hipMemcpyHostToDevice);
     hipMemcpy(sc, hs.data(), s.OC * 2, hipMemcpyHostToDevice);
     auto run = [&]() {
-      return qh::qbytes_conv2d_mfma(x, w, sc, nullptr, y, s.B, s.C, s.H, s.H, s.OC, 3, 3, OH, OW, 1, 1, 1, 1, 1, 1, QUANTO_HIP_BF16, QUANTO_HIP_I8, QUANTO_HIP_BF16, ws, ws_bytes, 0);
+      const qh::ConvGeom g{s.B, s.C, s.H, s.H, s.OC, 3, 3, OH, OW, 1, 1, 1, 1, 1, 1};
+      bool rows;
+      return qh::qbytes_conv2d_mfma(x, w, sc, nullptr, y, g, QUANTO_HIP_BF16, QUANTO_HIP_I8, QUANTO_HIP_BF16, ws, ws_bytes, 0, &rows);
     };
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     int st = 0;

@@ -31,7 +31,8 @@ def test_no_packed_fp32_with_op_sel_next_to_mfmas(unit):
     assert not packed, f"{unit}: hipcc re-packed scalar fp32 math ({len(packed)} v_pk_*_f32): is -fno-slp-vectorize still applied?"
 
 
-MFMA_UNITS = ["qmm_mfma_large", "qbits_skinny", "qbytes_skinny", "qmm_native8", "qbits_mmv", "qbits_mfma_fused", "qbits_mfma_large", "qconv_mfma", "qmm_mfma"]
+MFMA_UNITS = ["qmm_mfma_large", "qbits_skinny", "qbytes_skinny", "qmm_native8", "qbits_mmv", "qbits_mfma_fused", "qbits_a8_fused", "qbits_mfma_large", "qconv_mfma", "qconv_a8",
+              "qmm_mfma"]
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="needs hipcc")
