@@ -50,7 +50,7 @@ constexpr int BP = 128;           // packed rows per workgroup (256 features)
 constexpr int NW = 8;             // waves
 constexpr int MI = BM / 16;       // token fragments per wave (all of them)
 constexpr int STEPS = 2 * MI;     // (k-half, token fragment)
-constexpr int STAGES = 3;
+using lt::STAGES;  // 3: the K loop is QH_RING3_FOR_EACH_TILE
 constexpr int A_BYTES = BM * BK * 2;          // 32 KiB of activations per stage
 constexpr int W_BYTES = BP * BK;              // + 8 KiB of packed weights
 constexpr int STAGE_BYTES = A_BYTES + W_BYTES;
@@ -365,21 +365,7 @@ __global__ void __launch_bounds__(NW * 64, 1) qbits_mfma_large_kernel(const Args
       zc[j] = zn[j];
     }
   };
-  using yes = std::integral_constant<bool, true>;
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
-  using S2 = std::integral_constant<int, 2>;
-  int kt = 0;
-  for (; kt + 4 < nk; kt += 3) {  // three tiles that all still have a tile kt + 2 to fetch
-    tile(S0{}, kt, yes{}, yes{});
-    tile(S1{}, kt + 1, yes{}, yes{});
-    tile(S2{}, kt + 2, yes{}, yes{});
-  }
-  const int rem = nk - kt;  // 2..4 tiles left, kt % 3 == 0
-  tile(S0{}, kt, rem > 2, true);
-  tile(S1{}, kt + 1, rem > 3, rem > 2);
-  if (rem > 2) tile(S2{}, kt + 2, false, rem > 3);
-  if (rem > 3) tile(S0{}, kt + 3, false, false);
+  QH_RING3_FOR_EACH_TILE(nk, tile);
 
   // ---- epilogue: park the tile in LDS ([token][plane][128 packed rows] of T), store whole 256-byte rows per column block --------------
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -435,15 +421,7 @@ template <int DT, bool INT_SHIFT, bool FULLM, bool HG>
 static int launch_m(const Args& a, hipStream_t stream) {
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N / 2 + BP - 1) / BP, tiles = tiles_m * tiles_n;
   Args b = a;
-  {
-    // per-XCD band of B tiles as a (g x B/g) rectangle: fetched bytes per k ~ g * BM * 2 (activations) + (B / g) * BP (packed weights)
-    const int band = (tiles + 7) / 8;
-    int g = 1;
-    while ((g + 1) * (g + 1) * 2 * BM <= band * BP) ++g;
-    const int forced = env_int("QUANTO_HIP_GROUP_M", 0);  // experiments
-    if (forced > 0) g = forced;
-    b.group_m = g < tiles_m ? g : tiles_m;
-  }
+  b.group_m = lt::raster_group_m(tiles, tiles_m, BM, BP);  // BP bytes of packed weights per k and tile column
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbits_mfma_large_kernel<DT, INT_SHIFT, FULLM, HG>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   hipLaunchKernelGGL((qbits_mfma_large_kernel<DT, INT_SHIFT, FULLM, HG>), dim3(tiles), dim3(NW * 64), LDS_BYTES, stream, b);

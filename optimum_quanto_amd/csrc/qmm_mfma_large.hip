@@ -143,27 +143,11 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qbytes_mfma_large_kernel(cons
 #pragma unroll
     for (int i = 0; i < MI; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // r6: per-feature scale / bias of the tile wait in LDS behind the ring.  The epilogue used to fetch them from global memory AFTER the
-  // K loop: a full round trip in front of the first output byte, on the critical path of every tile (all tiles end together).  One 2-byte
-  // load per thread, issued in front of the prologue's DMA (oldest entry of the in-order vector-memory queue: complete at the prologue's
-  // counted wait), parked behind the ring before the first barrier.  As asm: a load hipcc can see makes it wait vmcnt(0) at the store.
+  // scale / bias of the tile: fetched ahead of the prologue's DMA, parked behind the ring before the first barrier (FeatureTable)
   constexpr int RING_BYTES = (WD != 0 ? WD : STAGES) * STAGE_BYTES;
   static_assert(NWAVES * 64 >= 2 * BN, "one table entry per thread");
-  uint32_t tab_val = 0;
-  const bool tab_scale = tid < BN ? a.scale != nullptr : a.bias != nullptr;
-  if (tid < 2 * BN && tab_scale) {
-    int n = n0 + (tid < BN ? tid : tid - BN);
-    n = n < N ? n : N - 1;
-    const T* src = reinterpret_cast<const T*>(tid < BN ? a.scale : a.bias) + n;
-    asm volatile("global_load_ushort %0, %1, off" : "=v"(tab_val) : "v"(src) : "memory");
-  }
-  auto park_table = [&]() {  // after the prologue's vmcnt wait, before its barrier
-    asm volatile("" : "+v"(tab_val));
-    if (tid < 2 * BN) {
-      const uint16_t one = DT == QUANTO_HIP_BF16 ? 0x3F80 : 0x3C00;
-      reinterpret_cast<uint16_t*>(smem + RING_BYTES)[tid] = tab_scale ? (uint16_t)tab_val : (tid < BN ? one : (uint16_t)0);
-    }
-  };
+  FeatureTable<DT, BN> ftab;
+  ftab.fetch(a.scale, a.bias, N, n0, tid);
 
   uint32_t w0[NJ][4], w1[NJ][4];
   V8 xf[4];              // activation fragments, two steps ahead (ring of 4: STEPS is a multiple of 4, the ring stays aligned)
@@ -216,9 +200,8 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qbytes_mfma_large_kernel(cons
       for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int b = 0; b < WB; ++b) asm volatile("" : "+v"(rg[t][j][b]));
-    park_table();
+    ftab.park(smem + RING_BYTES, tid);
     QH_LT_STAMP(1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     QH_LT_STAMP(2);
@@ -308,9 +291,8 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qbytes_mfma_large_kernel(cons
       for (int p = 0; p < NPIECES; ++p) issue_piece(1, 1, p);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile 1 too: its weight bytes are fetched during tile 0
-    park_table();
+    ftab.park(smem + RING_BYTES, tid);
     QH_LT_STAMP(1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     QH_LT_STAMP(2);
@@ -402,27 +384,14 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qbytes_mfma_large_kernel(cons
         asm volatile("" ::: "memory");
       }
     };
-    using S0 = std::integral_constant<int, 0>;
-    using S1 = std::integral_constant<int, 1>;
-    using S2 = std::integral_constant<int, 2>;
-    static_assert(STAGES == 3, "the loop below is unrolled over three stages");
     QH_LT_STAMP(3);
-    int kt = 0;
-    for (; kt + 4 < nk; kt += 3) {  // three tiles that all still have a tile kt+2 to fetch
-      tile(S0{}, kt, yes{}, yes{});
-      tile(S1{}, kt + 1, yes{}, yes{});
-      tile(S2{}, kt + 2, yes{}, yes{});
-    }
-    // tail: 2..4 tiles (nk >= 2), kt % 3 == 0; the last two have nothing left to prefetch, the last one no barrier
-    const int rem = nk - kt;
-    tile(S0{}, kt, rem > 2, true);
-    tile(S1{}, kt + 1, rem > 3, rem > 2);
-    if (rem > 2) tile(S2{}, kt + 2, false, rem > 3);
-    if (rem > 3) tile(S0{}, kt + 3, false, false);
+    QH_RING3_FOR_EACH_TILE(nk, tile);
   }
   QH_LT_STAMP(4);
 
   // ---- epilogue: scale (+bias) on the fp32 accumulator; each wave parks MI*16 tokens x 64 features per pass -------------
+  // The same epilogue as n8::epilogue (qmm_native8.hip), which spells it as a function over 2- and 4-byte outputs: a fix to one belongs in the
+  // other.  One shared function (this wording or that one, 8-byte or element reads of the table) changed the listings of both units.
   T* yg = reinterpret_cast<T*>(a.y);
   const bool has_bias = a.bias != nullptr;
   const bool full = (m0 + BM <= M) && (n0 + BN <= N) && (N % 8 == 0);
@@ -518,15 +487,7 @@ static int launch_cfg(const Args& a, hipStream_t stream) {
   static_assert(lds0 >= BM * BN * 2, "the epilogue parks the output tile in the stage memory");
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN, tiles = tiles_m * tiles_n;
   Args b = a;
-  {
-    // per-XCD band of B tiles as a (g x B/g) rectangle: fetched bytes ~ g*BM*2 + (B/g)*BN per k -> g = sqrt(B*BN/(2*BM))
-    const int band = (tiles + 7) / 8;
-    int g = 1;
-    while ((g + 1) * (g + 1) * 2 * BM <= band * BN) ++g;
-    const int forced = env_int("QUANTO_HIP_GROUP_M", 0);  // experiments
-    if (forced > 0) g = forced;
-    b.group_m = g < tiles_m ? g : tiles_m;
-  }
+  b.group_m = raster_group_m(tiles, tiles_m, BM, BN);  // BN bytes of weights per k and tile column
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_mfma_large_kernel<DT, FMT, BM, BN, WM, WN, WD>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   hipLaunchKernelGGL((qbytes_mfma_large_kernel<DT, FMT, BM, BN, WM, WN, WD>), dim3(tiles * b.S), dim3(WM * WN * 64), lds, stream, b);

@@ -6,14 +6,18 @@
 //                rounding to the output dtype -> bit-identical to the reference's _int_mm path;
 //   fp8  x fp8 : every product of two e4m3/e5m2 values is exact in fp32; fp32 accumulation.
 //
-// Same structure as qmm_mfma_large.hip (256x256 tile, 8 waves as 2x4, LDS-DMA with counted vmcnt, swizzled 64-byte rows,
-// one software-pipelined instruction stream per wave, one barrier per K-tile, LDS-transposed full-line epilogue), with a
-// K-tile of 64 bytes per row for BOTH operands (4 stages of 32 KiB): 12 ds_read_b128, 4 DMA issues and 32 (int8) or
-// 64 (fp8) MFMAs per wave and K-tile.
+// Two kernels, same tile shapes (256x256 with 8 waves as 2x4, or 128x128 with 4 waves as 1x4), one software-pipelined instruction stream per
+// wave, LDS-DMA with counted vmcnt, an LDS-transposed full-line epilogue; raster and scale / bias table are those of qmm_large_common.h:
+//   * qbytes_native8_r128_kernel (second in this file, the product kernel): 128-byte rows - a DMA piece is 8 rows x one whole line, two LDS
+//     buffers, one barrier per 128 bytes of K, fp8 on the K = 128 MX-format MFMA (unit scales), split-K with a sliced tail.  Serves every
+//     K * element size that is a multiple of 128, i.e. all the measured shapes (w8a8 / fp8a8, the dense 16-bit GEMM behind int4 prefill);
+//   * qbytes_native8_kernel (first): the r1-r4 kernel - K-tiles of 64 bytes per row for both operands, four stages of 32 KiB, 12 ds_read_b128,
+//     4 DMA issues and 32 (int8) or 64 (fp8, 16x16x32) MFMAs per wave and K-tile.  It still serves K * element size = 64 (mod 128) and
+//     QUANTO_HIP_NATIVE8_ROW128=0; its PAIRED loop is built by probes only (-DQH_N8_EXPERIMENTS).
 #include <cstdlib>
 #include <type_traits>
 
-#include "qh_mfma.h"
+#include "qmm_large_common.h"
 
 #ifndef QH_N8_ABLATE
 #define QH_N8_ABLATE 0  // timing experiments only: 1 = no DMA inside the K loop
@@ -32,10 +36,8 @@ __device__ unsigned long long g_stamps[4096 * 8];
 constexpr int BK = 64;  // bytes per row and K-tile, both operands
 constexpr int STAGES = 4;
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-__device__ __forceinline__ int swz64(int row) { return (-(row >> 2)) & 3; }  // 64-byte rows, lanes read chunk lane>>4
+using lt::i32x4;
+using lt::lds_ptr_t;
 
 enum { K_I8 = 0, K_F8E4M3 = 1, K_F8E5M2 = 2, K_BF16 = 3, K_F16 = 4 };  // K_BF16 / K_F16: dense 16-bit operands, 32 elements per K-tile
 
@@ -48,80 +50,20 @@ struct Acc<K_I8> {
   using V = i32x4;
 };
 
-struct Args {
-  const uint8_t* a;   // [M, K] 1 byte per element (2 for the dense 16-bit kinds)
-  const uint8_t* w;   // [N, K]
-  const void* scale;  // [N] output dtype, or null (= 1)
-  const void* bias;   // [N] or null
-  void* y;            // [M, N]
-  int M, N, K;
-  int gm;             // tile raster: consecutive workgroup ids walk down gm tile rows before moving to the next tile column (1 = row-major)
-  // split-K (r6, 128-byte-row kernel): S workgroups per tile, workgroup (tile, sp) multiplies the K range sp of S; the accumulators (int32 / fp32) travel
-  // fragment-major through `partials`, an arrival counter per tile elects the last workgroup, which adds in split order and runs the epilogue
-  // (workspace contract of the split-K tail in qh_mfma.h: counters zero on entry and on exit)
-  int S;
-  int* counters;      // [tiles]
-  void* partials;     // [tiles * S][NJ * 8][threads] 16-byte accumulator quads
-  int poll_ticks;     // how long a workgroup waits for its partners (s_memrealtime ticks of 10 ns) before it leaves its slice to the last arriver
+// lt::Args (x / w: 1 byte per element, 2 for the dense 16-bit kinds; `partials` carries int32 or fp32 quads) plus the poll limit of the split-K tail below:
+// S workgroups per tile (128-byte-row kernel), workgroup (tile, sp) multiplies the K range sp of S; workspace contract of the split-K tail in qh_mfma.h
+struct Args : lt::Args {
+  int poll_ticks;  // how long a workgroup waits for its partners (s_memrealtime ticks of 10 ns) before it leaves its slice to the last arriver
 };
 
-// Tile raster.  The XCD remap in the kernels hands every XCD (its own 4 MiB L2, 32 CUs) one contiguous range of tile indices; all of an
-// XCD's workgroups walk K in step, so its L2 fetches every operand line once per distinct tile row / tile column in that range.  Row-major
-// indices make the range 2 tile rows x 16 tile columns at 4096^3 (18 row-panels of traffic per XCD, 72 % L2 hits), and ONE row x 32 columns for
-// the 128-tiles of (512,8192,8192) (33 panels); walking `gm` tile rows first turns it into a gm x (32 / gm) block: 4 x 8 or 8 x 4 = 12 panels (measured, r5: L2 misses -27 %, (512,8192,8192)
-// int8 / fp8 46.1 / 46.5 -> 42.8 / 43.4 us, int4 prefill 4096^3 104.3 -> 102.4, the square 4096^3 products unchanged).
-// The vector L1 keeps ~57 of its 64 miss slots busy in these kernels (requests x latency / cycles, profiles/r05_native8_row128.md), so the
-// fill rate is slots x 128 B / latency and the L2 hit rate sets the latency.
-__device__ __forceinline__ void tile_of(int bid, int tiles_m, int tiles_n, int gm, int& tm, int& tn) {
-  const int per_group = gm * tiles_n;
-  const int grp = bid / per_group, first = grp * gm;
-  const int rows = tiles_m - first < gm ? tiles_m - first : gm;
-  const int in = bid - grp * per_group;
-  tn = in / rows;
-  tm = first + (in - tn * rows);
-}
-
-// ---- r6: per-feature scale / bias of the tile, parked in LDS behind the operand ring by the prologue ------------------------------------
-// The epilogue used to fetch them from global memory after the K loop: a round trip in front of the first output byte of every tile, and all
-// tiles of these grids end together.  One load per thread (threads = 2 * BN), issued in FRONT of the prologue's DMA - the oldest entry of the
-// in-order vector-memory queue, so the prologue's counted wait covers it - and stored behind the ring before the prologue's barrier.  As asm:
-// a load hipcc can see makes it drain the DMA queue (vmcnt(0)) at the store.  (Same change as qmm_mfma_large.hip: cfg2 -1.4 us, cfg4 -1.1 us.)
-template <int ODT, int BN>
-struct FeatureTable {
-  using T = typename Elem<ODT>::T;
-  static constexpr int BYTES = 2 * BN * (int)sizeof(T);  // [scale x BN | bias x BN]
-  uint32_t v;
-  bool have;
-  __device__ __forceinline__ void fetch(const Args& a, int n0, int tid) {
-    v = 0;
-    have = tid < BN ? a.scale != nullptr : a.bias != nullptr;
-    if (tid < 2 * BN && have) {
-      int n = n0 + (tid < BN ? tid : tid - BN);
-      n = n < a.N ? n : a.N - 1;
-      const T* src = reinterpret_cast<const T*>(tid < BN ? a.scale : a.bias) + n;
-      if constexpr (sizeof(T) == 2)
-        asm volatile("global_load_ushort %0, %1, off" : "=v"(v) : "v"(src) : "memory");
-      else
-        asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(src) : "memory");
-    }
-  }
-  // after the prologue's vmcnt wait, before its barrier
-  __device__ __forceinline__ void park(uint8_t* tab, int tid) {
-    asm volatile("" : "+v"(v));
-    if (tid < 2 * BN) {
-      if constexpr (sizeof(T) == 2) {
-        const uint16_t one = ODT == QUANTO_HIP_BF16 ? 0x3F80 : 0x3C00;
-        reinterpret_cast<uint16_t*>(tab)[tid] = have ? (uint16_t)v : (tid < BN ? one : (uint16_t)0);
-      } else {
-        reinterpret_cast<uint32_t*>(tab)[tid] = have ? v : (tid < BN ? 0x3F800000u : 0u);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
-};
+// Tile raster: lt::xcd_band + lt::grouped_tile (qmm_large_common.h).  The vector L1 keeps ~57 of its 64 miss slots busy in these kernels (requests x
+// latency / cycles, profiles/r05_native8_row128.md), so the fill rate is slots x 128 B / latency and the L2 hit rate the raster buys sets the latency.
+using lt::FeatureTable;
 
 // ---- epilogue: (int32 | fp32) accumulator * scale[n] (+ bias), parked per wave in LDS, stored as full 128-byte lines ----
 // (shared by the 64-byte-row and the 128-byte-row kernels; every wave must be done with the operand stages: the barrier below)
+// The same epilogue as the inline one of qmm_mfma_large.hip (2-byte outputs, 8-byte reads of the table, MI * 16 rows per wave): a fix to one belongs
+// in the other.  One shared function changed the listings of both units, whichever of the two wordings it took.
 // NI / i0: the token fragments acc[.][0 .. NI-1] are fragments i0 .. i0 + NI - 1 of the wave's 128 rows (the K split hands every workgroup 8 / S of them)
 template <int ODT, int KIND, int NJ, int BM, int BN, int NI = 8>
 __device__ __forceinline__ void epilogue(const Args& a, typename Acc<KIND>::V (&acc)[NJ][NI], uint8_t* smem, const uint8_t* tabp, int m0, int n0, int wm,
@@ -364,18 +306,14 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_kernel(co
 
   const int tiles_n = (N + BN - 1) / BN, tiles_m = (M + BM - 1) / BM;
   const int nwg = tiles_n * tiles_m;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = lt::xcd_band(blockIdx.x, nwg);
   int tm, tn;
-  tile_of(bid, tiles_m, tiles_n, a.gm, tm, tn);
+  lt::grouped_tile(bid, tiles_m, tiles_n, a.group_m, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
   constexpr int RING_BYTES = STAGES * STAGE_BYTES;
   FeatureTable<ODT, BN> ftab;  // scale / bias of the tile: fetched ahead of the DMA, parked behind the ring before the prologue's barrier
   static_assert(NWAVES * 64 == 2 * BN, "one table entry per thread");
-  ftab.fetch(a, n0, tid);
+  ftab.fetch(a.scale, a.bias, N, n0, tid);
 
   // ---- DMA: 2 + 2 pieces of 1 KiB per wave and K-tile; piece j of an operand covers tile rows (j*8+wave)*16 .. +15 -------
   uint32_t asrc[2], wsrc[2];
@@ -383,7 +321,7 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_kernel(co
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int R = (j * NWAVES + wave) * 16 + (lane >> 2);
-    const int c = (lane & 3) ^ swz64(R);
+    const int c = (lane & 3) ^ lt::swz_w(R);
     int m = m0 + R, n = n0 + R;
     m = m < M ? m : M - 1;
     n = n < N ? n : N - 1;
@@ -402,14 +340,14 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_kernel(co
       mdst[t][p] = __builtin_amdgcn_readfirstlane(lds_base + t * STAGE_BYTES + (p < 2 ? adst[p] : wdst[p - 2]));
   auto issue_piece_to = [&](int kt, const uint32_t (&dst)[4], int piece) {
     if (piece < 2)
-      glds16(a.a + (size_t)kt * BK, asrc[piece], dst[piece]);
+      glds16(reinterpret_cast<const uint8_t*>(a.x) + (size_t)kt * BK, asrc[piece], dst[piece]);
     else
       glds16(a.w + (size_t)kt * BK, wsrc[piece - 2], dst[piece]);
   };
   auto issue = [&](int kt, int stage) {  // prologue only (run-time stage)
     const uint32_t st = __builtin_amdgcn_readfirstlane(lds_base + stage * STAGE_BYTES);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) glds16(a.a + (size_t)kt * BK, asrc[j], st + adst[j]);
+    for (int j = 0; j < 2; ++j) glds16(reinterpret_cast<const uint8_t*>(a.x) + (size_t)kt * BK, asrc[j], st + adst[j]);
 #pragma unroll
     for (int j = 0; j < 2; ++j) glds16(a.w + (size_t)kt * BK, wsrc[j], st + wdst[j]);
   };
@@ -417,8 +355,8 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_kernel(co
   // ---- fragment reads: ONE ds_read_b128 per 16-row fragment and K-tile (bytes k = 16g .. 16g+15, g = lane >> 4); the
   // swizzle only depends on (row & 15) >> 2, so fragment i / j adds a compile-time multiple of 1024 bytes
   const int ra = wm * 128 + (lane & 15), rw = wn * (NJ * 16) + (lane & 15);
-  const int aoff0 = ra * 64 + (((lane >> 4) ^ swz64(ra)) << 4);
-  const int boff0 = A_BYTES + rw * 64 + (((lane >> 4) ^ swz64(rw)) << 4);
+  const int aoff0 = ra * 64 + (((lane >> 4) ^ lt::swz_w(ra)) << 4);
+  const int boff0 = A_BYTES + rw * 64 + (((lane >> 4) ^ lt::swz_w(rw)) << 4);
   // The K loops are unrolled over the four stages (tile kt lives in stage kt & 3): fragment bases per stage are loop
   // constants in registers, a K-tile carries no address arithmetic (run-time stage bookkeeping was ~40 of the ~190
   // instructions per two tiles and wave)
@@ -664,23 +602,20 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_r128_kern
   const int S = a.S;
   const int np = K * ES / RB / S;  // pairs (128-byte K-tiles) of this workgroup's K range
 
+  // (tile constants and wave layout as in the kernel above; one struct holding both heads changed this file's listing)
   const int tiles_n = (N + BN - 1) / BN, tiles_m = (M + BM - 1) / BM;
   const int nwg = tiles_n * tiles_m * S;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = lt::xcd_band(blockIdx.x, nwg);
   // the S workgroups of a tile are neighbours in the remapped order: same XCD (they share the tile's operand panels' neighbours in L2)
   const int tile_lin = S > 1 ? bid / S : bid, sp = S > 1 ? bid - tile_lin * S : 0;
   const size_t kbase = (size_t)sp * np * RB;  // byte offset of this K range inside an operand row
   int tm, tn;
-  tile_of(tile_lin, tiles_m, tiles_n, a.gm, tm, tn);
+  lt::grouped_tile(tile_lin, tiles_m, tiles_n, a.group_m, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
   constexpr int RING_BYTES = 4 * OP_BYTES;
   FeatureTable<ODT, BN> ftab;  // scale / bias of the tile: fetched ahead of the DMA, parked behind the ring before the prologue's barrier
   static_assert(NWAVES * 64 == 2 * BN, "one table entry per thread");
-  ftab.fetch(a, n0, tid);
+  ftab.fetch(a.scale, a.bias, N, n0, tid);
 
   // ---- DMA: 4 + 4 pieces of 1 KiB per wave and pair; piece j of an operand covers tile rows (j * NWAVES + wave) * 8 .. + 7 ----
   uint32_t asrc[PPW], wsrc[PPW];
@@ -703,7 +638,7 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_r128_kern
       mdst[b][q] = __builtin_amdgcn_readfirstlane(lds_base + (q < PPW ? 0 : W_BASE) + b * OP_BYTES + ((q % PPW) * NWAVES + wave) * 1024);
   auto issue_piece = [&](int p, const uint32_t (&dst)[2 * PPW], int q) {  // piece q of pair p: q < 4 activations, else weights
     if (q < PPW)
-      glds16(a.a + kbase + (size_t)p * RB, asrc[q], dst[q]);
+      glds16(reinterpret_cast<const uint8_t*>(a.x) + kbase + (size_t)p * RB, asrc[q], dst[q]);
     else
       glds16(a.w + kbase + (size_t)p * RB, wsrc[q - PPW], dst[q]);
   };
@@ -893,6 +828,8 @@ static int launch_r128(const Args& a, hipStream_t stream) {
   return launch_status();
 }
 
+// A fixed group of 8 tile rows, not lt::raster_group_m's square-root rule: these kernels read both operands at the same width, and 8 is what
+// r5 measured best on the shapes above (4 x 8 or 8 x 4 blocks per XCD) - a different, measured policy.
 static int raster_group() {
   const int g = env_int("QUANTO_HIP_NATIVE8_GROUP_M", 8);  // experiments: 1 = row-major
   return g < 1 ? 1 : g;
@@ -998,7 +935,7 @@ bool dense_mm_large_supported(int64_t M, int64_t N, int64_t K, int dtype) {
 int dense_mm_large(const void* x, const void* w, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int dtype, hipStream_t stream) {
   if (!dense_mm_large_supported(M, N, K, dtype)) return QUANTO_HIP_ENOTSUP;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) % 16) return QUANTO_HIP_EALIGN;
-  n8::Args args{reinterpret_cast<const uint8_t*>(x), reinterpret_cast<const uint8_t*>(w), nullptr, bias, y, (int)M, (int)N, (int)K, n8::raster_group(), 1, nullptr, nullptr, 0};
+  n8::Args args{{x, reinterpret_cast<const uint8_t*>(w), nullptr, bias, y, (int)M, (int)N, (int)K, n8::raster_group(), 1, nullptr, nullptr}, 0};
   if (dtype == QUANTO_HIP_BF16) return n8::launch<QUANTO_HIP_BF16, n8::K_BF16>(args, nullptr, 0, stream);
   return n8::launch<QUANTO_HIP_F16, n8::K_F16>(args, nullptr, 0, stream);
 }
@@ -1017,7 +954,7 @@ static int native8_kind(int a_dtype) { return a_dtype == QUANTO_HIP_I8 ? n8::K_I
 // split-K scratch for this problem: [QUANTO_HIP_WS_COUNTER_BYTES of arrival counters, zero on entry and on exit | partial accumulator tiles]; 0 = the plan does not split
 size_t qbytes_native8_workspace(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
   if (!qbytes_native8_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return 0;
-  n8::Args args{nullptr, nullptr, nullptr, nullptr, nullptr, (int)M, (int)N, (int)K, 1, 1, nullptr, nullptr, 0};
+  n8::Args args{{nullptr, nullptr, nullptr, nullptr, nullptr, (int)M, (int)N, (int)K, 1, 1, nullptr, nullptr}, 0};
   switch (native8_kind(a_dtype)) {
     case n8::K_I8: return n8::plan_workspace<n8::K_I8>(n8::make_plan<n8::K_I8>(args, true), M, N);
     case n8::K_F8E4M3: return n8::plan_workspace<n8::K_F8E4M3>(n8::make_plan<n8::K_F8E4M3>(args, true), M, N);
@@ -1029,7 +966,7 @@ int qbytes_mm_native8(const void* a, const void* b, const void* s, const void* b
                       int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!qbytes_native8_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
   if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) % 16) return QUANTO_HIP_EALIGN;
-  n8::Args args{reinterpret_cast<const uint8_t*>(a), reinterpret_cast<const uint8_t*>(b), s, bias, y, (int)M, (int)N, (int)K, n8::raster_group(), 1, nullptr, nullptr, 0};
+  n8::Args args{{a, reinterpret_cast<const uint8_t*>(b), s, bias, y, (int)M, (int)N, (int)K, n8::raster_group(), 1, nullptr, nullptr}, 0};
 #define QH_KIND(ODT)                                                                  \
   if (a_dtype == QUANTO_HIP_I8) return n8::launch<ODT, n8::K_I8>(args, workspace, workspace_bytes, stream);       \
   if (a_dtype == QUANTO_HIP_F8_E4M3FN) return n8::launch<ODT, n8::K_F8E4M3>(args, workspace, workspace_bytes, stream); \

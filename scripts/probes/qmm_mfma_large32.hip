@@ -316,14 +316,7 @@ static int launch(const Args& a, hipStream_t stream) {
   static_assert(lds >= NWAVES * MI * 32 * 128, "the epilogue parks the output tile in the stage memory");
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN, tiles = tiles_m * tiles_n;
   Args b = a;
-  {
-    const int band = (tiles + 7) / 8;
-    int g = 1;
-    while ((g + 1) * (g + 1) * 2 * BM <= band * BN) ++g;
-    const int forced = env_int("QUANTO_HIP_GROUP_M", 0);  // experiments
-    if (forced > 0) g = forced;
-    b.group_m = g < tiles_m ? g : tiles_m;
-  }
+  b.group_m = lt::raster_group_m(tiles, tiles_m, BM, BN);
   b.S = 1;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_mfma_large32_kernel<DT, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   hipLaunchKernelGGL((qbytes_mfma_large32_kernel<DT, FMT>), dim3(tiles), dim3(NWAVES * 64), lds, stream, b);

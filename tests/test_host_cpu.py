@@ -505,3 +505,22 @@ def test_bench_inputs_are_quantizer_outputs(kind):
         assert x.dtype == torch.float8_e4m3fn
     else:
         assert x.dtype == torch.bfloat16
+
+
+def test_staleness_list_names_every_file_the_objects_depend_on():
+    """NativeLibrary's "is the built library older than its sources" check reads hip.py's ``sources`` list; the Makefile's ``build/%.o`` rule
+    and its ``SRCS`` line say what an object file depends on.  The two sets are the same files: an edit to a header the list omits would not
+    mark the library stale."""
+    csrc = os.path.join(ROOT, "optimum_quanto_amd", "csrc")
+    make = open(os.path.join(csrc, "Makefile")).read()
+    srcs = re.search(r"^SRCS\s*=\s*(.+)$", make, re.M).group(1).split()
+    rule = re.search(r"^build/%\.o:\s*(.+)$", make, re.M).group(1).split()
+    assert rule[0] == "%.hip" and len(srcs) > 10 and len(rule) > 3
+    makefile_files = {os.path.normpath(os.path.join(csrc, f)) for f in srcs + rule[1:]}
+    hip_py = open(os.path.join(ROOT, "optimum_quanto_amd", "library", "hip.py")).read()
+    listed = re.search(r"sources=\[(.*?)\]", hip_py, re.S).group(1)
+    names = [os.path.join(*re.findall(r'"([^"]+)"', item)) for item in re.split(r",(?![^()]*\))", listed) if item.strip()]
+    assert len(names) == len(set(names))
+    listed_files = {os.path.normpath(os.path.join(csrc, n)) for n in names}
+    assert listed_files == makefile_files, sorted(listed_files ^ makefile_files)
+    assert all(os.path.isfile(f) for f in listed_files)
