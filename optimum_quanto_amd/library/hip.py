@@ -376,7 +376,9 @@ class _Bindings:
             return False
         OH = self.conv2d_out_size(H, KH, stride[0], padding[0], dilation[0])
         OW = self.conv2d_out_size(W, KW, stride[1], padding[1], dilation[1])
-        return (B >= 1 and OH >= 1 and OW >= 1 and B * C * H * W < (1 << 31) and B * OC * OH * OW < (1 << 31) and KH * KW <= 4096)
+        # (H, W < 2^20: the C rule's clause, csrc/qconv_depthwise.hip - without it a column of 2^20 rows got ENOTSUP raised instead of the reference path)
+        return (B >= 1 and OH >= 1 and OW >= 1 and B * C * H * W < (1 << 31) and B * OC * OH * OW < (1 << 31) and KH * KW <= 4096 and
+                H < (1 << 20) and W < (1 << 20))
 
     def qbytes_conv2d(self, x, w, scales, bias, stride, padding, dilation):
         """Dense convolution with an 8-bit weight [OC, C, KH, KW] and per-channel scales: im2col happens inside the kernel's staging loads.  A weight

@@ -152,6 +152,14 @@ def assert_close_with_bias(y: np.ndarray, prod_exact: np.ndarray, bias: np.ndarr
     assert (y == want).mean() > 0.97, f"{what}: only {(y == want).mean():.4f} identical to the reference sequence"
 
 
+def projection_bound(abs_sum, n: int, ymax: float):
+    """Bound on |sum_j v_j y_j - exact| for a +-1 projection over ``n`` bf16 outputs whose absolute values sum to ``abs_sum`` (a tensor, one
+    entry per projected row / pixel): the parity gate's per-element error (2 bf16 ulp of the output plus 1e-2 of the largest output ``ymax``
+    for cancelled elements, DESIGN.md "Parity") summed over the projection, with the fp32 accumulation's own slack.  The one formula of the
+    Freivalds checks in test_large_operands_gpu.py and test_large_convs_gpu.py."""
+    return (2.0 ** -6) * abs_sum + n * (2.0 ** -7) * 1e-2 * ymax + 1e-6 * n * ymax
+
+
 def assert_similar(a: torch.Tensor, b: torch.Tensor, atol=None, rtol=None):
     """The reference's own similarity check (tests/helpers.py:85-99): cosine similarity ~ 1."""
     assert a.dtype == b.dtype and a.shape == b.shape

@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import assert_close_to_exact, to_numpy
+from helpers import assert_close_to_exact, projection_bound, to_numpy
 from optimum_quanto_amd.library.hip import quanto_hip
 
 pytestmark = pytest.mark.gpu
@@ -199,7 +199,7 @@ def _check_freivalds(y, x, w, what, out_scale=1.0, nvec=3, seed=0):
         yc = y[m0:m1].float().double()
         got = yc @ v
         want = (x[m0:m1].float().double() @ wv) * out_scale
-        bound = (2.0 ** -6) * yc.abs().sum(dim=1, keepdim=True) + N * (2.0 ** -7) * 1e-2 * ymax + 1e-6 * N * ymax
+        bound = projection_bound(yc.abs().sum(dim=1, keepdim=True), N, ymax)
         ratio = float(((got - want).abs() / bound).max())
         worst = max(worst, ratio)
         assert ratio <= 1.0, f"{what}: Freivalds projection off in rows {m0}..{m1 - 1} ({ratio:.2f} x the bound)"
