@@ -239,6 +239,25 @@ int quanto_hip_qbytes_mm_plan(int64_t M, int64_t N, int64_t K, int a_dtype, int 
                               int64_t* workspace_bytes_out);
 
 /*
+ * quanto::qbytes_mm_q(Tensor A, Tensor B, Tensor scales, Tensor? bias, Tensor out_scale) -> Tensor
+ *   replaces, for a layer with quantized activations, the product AND the re-quantization of its output (nn/qmodule.py:281-299 ->
+ *   library/quantize.py:26-55): yq = quantize_symmetric(qbytes_mm(a, b, scales) (+ bias), a_dtype, per-tensor, out_scale) in ONE launch, the
+ *   [M, N] tensor of mid_dtype never written.  Bit-identical to quanto_hip_qbytes_mm_ws followed by quanto_hip_quantize_symmetric.
+ * a: a_dtype[M, K], b: b_dtype[N, K], both I8, both F8_E4M3FN or both F8_E5M2; scales / bias: mid_dtype[N] (bias may be NULL);
+ * out_scale: mid_dtype[1] (device); yq: a_dtype[M, N] codes.  a, b and yq 16-byte aligned (QUANTO_HIP_EALIGN otherwise).
+ * Served: what the NATIVE8 kernel of quanto_hip_qbytes_mm serves (K a multiple of 64, M * K and N * K below 2^31) with mid_dtype BF16 or F16 and
+ * kernel AUTO or NATIVE8.  Everything else - F32 mid_dtype, mixed or other operand dtypes, other K, the size limits, another kernel - returns
+ * QUANTO_HIP_ENOTSUP and writes nothing: the caller runs the two entries above.  workspace: the split-K scratch of quanto_hip_qbytes_mm_ws, same contract;
+ * quanto_hip_qbytes_mm_q_plan gives the same kernel and bytes as quanto_hip_qbytes_mm_plan does for the NATIVE8 kernel.
+ * quanto_hip_last_kernel() reports "mfma_native8_q" after a successful launch.
+ */
+int quanto_hip_qbytes_mm_q_ws(const void* a, const void* b, const void* scales, const void* bias, const void* out_scale, void* yq,
+                              int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int mid_dtype, int kernel,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int quanto_hip_qbytes_mm_q_plan(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int mid_dtype, int kernel, int* kernel_out,
+                                int64_t* workspace_bytes_out);
+
+/*
  * quanto::quantize_symmetric(Tensor base, ScalarType dtype, int? axis, Tensor scale) -> Tensor
  *   replaces library/quantize.py:26-55 (div, round, clamp, cast = four elementwise passes) with one pass; it is the
  *   per-forward step of quantized activations (tensor/activations/qbytes.py:31-39, nn/qmodule.py:281-291).

@@ -62,6 +62,8 @@ int dense_mm_wd(const void*, const void*, const void*, void*, int64_t, int64_t, 
 bool qbytes_native8_supported(int64_t, int64_t, int64_t, int, int, int);
 size_t qbytes_native8_workspace(int64_t, int64_t, int64_t, int, int, int);
 int qbytes_mm_native8(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, void*, size_t, hipStream_t);
+int qbytes_mm_native8_q(const void*, const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, void*, size_t,
+                        hipStream_t);
 bool qbits_skinny_multi_supported(int, const int64_t*, int64_t, int64_t, int);
 size_t qbits_skinny_multi_workspace(int, const int64_t*, int64_t, int64_t);
 int qbits_mm_skinny_multi(const void*, int, const uint8_t* const*, const void* const*, const void* const*, const void* const*, void* const*,
@@ -701,6 +703,40 @@ int quanto_hip_qbytes_mm_multi_ws(const void* a, int count, const void* const* b
 int quanto_hip_qbytes_mm(const void* a, const void* b, const void* scales, const void* bias, void* y, int64_t M, int64_t N, int64_t K,
                          int a_dtype, int b_dtype, int out_dtype, int kernel, void* stream) {
   return quanto_hip_qbytes_mm_ws(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, kernel, nullptr, 0, stream);
+}
+
+// ---- qbytes_mm with the layer's output quantization in the epilogue: one route (NATIVE8), everything else is the caller's two-op sequence ----
+// sizes -> EINVAL; then every reason not to serve -> ENOTSUP, ahead of any look at the data pointers
+static int check_qbytes_q(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int mid_dtype, int kernel) {
+  if (M < 0 || N <= 0 || K <= 0) return QUANTO_HIP_EINVAL;
+  if (kernel < QUANTO_HIP_KERNEL_AUTO || kernel > QUANTO_HIP_KERNEL_MFMA_LARGE4) return QUANTO_HIP_EINVAL;
+  if (kernel != QUANTO_HIP_KERNEL_AUTO && kernel != QUANTO_HIP_KERNEL_NATIVE8) return QUANTO_HIP_ENOTSUP;  // no other kernel stores codes
+  if (mid_dtype != QUANTO_HIP_BF16 && mid_dtype != QUANTO_HIP_F16) return QUANTO_HIP_ENOTSUP;              // fp32 layers (and non-float dtypes)
+  // equal operand pairs, K a multiple of 64, operand sizes below 2^31 bytes: the rule of the unfused route
+  return qbytes_native8_supported(M > 0 ? M : 1, N, K, a_dtype, b_dtype, mid_dtype) ? QUANTO_HIP_OK : QUANTO_HIP_ENOTSUP;
+}
+
+int quanto_hip_qbytes_mm_q_plan(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int mid_dtype, int kernel, int* kernel_out,
+                                int64_t* workspace_bytes_out) {
+  if (!kernel_out || !workspace_bytes_out) return QUANTO_HIP_EINVAL;
+  const int st = check_qbytes_q(M, N, K, a_dtype, b_dtype, mid_dtype, kernel);
+  if (st != QUANTO_HIP_OK) return st;
+  const Plan p = plan_qbytes(M, N, K, a_dtype, b_dtype, mid_dtype, QUANTO_HIP_KERNEL_NATIVE8);  // the planner of the unfused entry: same split, same scratch
+  *kernel_out = p.kernel;
+  *workspace_bytes_out = p.workspace;
+  return QUANTO_HIP_OK;
+}
+
+int quanto_hip_qbytes_mm_q_ws(const void* a, const void* b, const void* scales, const void* bias, const void* out_scale, void* yq, int64_t M, int64_t N,
+                              int64_t K, int a_dtype, int b_dtype, int mid_dtype, int kernel, void* workspace, size_t workspace_bytes, void* stream_) {
+  const int st = check_qbytes_q(M, N, K, a_dtype, b_dtype, mid_dtype, kernel);
+  if (st != QUANTO_HIP_OK) return st;
+  if (M == 0) return QUANTO_HIP_OK;
+  if (!a || !b || !scales || !out_scale || !yq) return QUANTO_HIP_EINVAL;
+  const int r = qbytes_mm_native8_q(a, b, scales, bias, out_scale, yq, M, N, K, a_dtype, b_dtype, mid_dtype, workspace, workspace_bytes,
+                                    reinterpret_cast<hipStream_t>(stream_));
+  if (r == QUANTO_HIP_OK) set_last_kernel("mfma_native8_q");
+  return r;
 }
 
 int quanto_hip_quantize_symmetric(const void* base, const void* scale, void* out, int64_t numel, int64_t inner, int scale_mode,

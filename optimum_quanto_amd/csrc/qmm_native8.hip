@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "qmm_large_common.h"
+#include "qh_quantize.h"
 
 #ifndef QH_N8_ABLATE
 #define QH_N8_ABLATE 0  // timing experiments only: 1 = no DMA inside the K loop
@@ -54,6 +55,7 @@ struct Acc<K_I8> {
 // S workgroups per tile (128-byte-row kernel), workgroup (tile, sp) multiplies the K range sp of S; workspace contract of the split-K tail in qh_mfma.h
 struct Args : lt::Args {
   int poll_ticks;  // how long a workgroup waits for its partners (s_memrealtime ticks of 10 ns) before it leaves its slice to the last arriver
+  const void* out_scale;  // QOUT kernels only: one element of the output dtype, the per-tensor scale of the codes they store into `y` ([M, N] bytes)
 };
 
 // Tile raster: lt::xcd_band + lt::grouped_tile (qmm_large_common.h).  The vector L1 keeps ~57 of its 64 miss slots busy in these kernels (requests x
@@ -65,9 +67,94 @@ using lt::FeatureTable;
 // The same epilogue as the inline one of qmm_mfma_large.hip (2-byte outputs, 8-byte reads of the table, MI * 16 rows per wave): a fix to one belongs
 // in the other.  One shared function changed the listings of both units, whichever of the two wordings it took.
 // NI / i0: the token fragments acc[.][0 .. NI-1] are fragments i0 .. i0 + NI - 1 of the wave's 128 rows (the K split hands every workgroup 8 / S of them)
-template <int ODT, int KIND, int NJ, int BM, int BN, int NI = 8>
+// ---- the same epilogue storing OUTPUT CODES: what quanto::quantize_symmetric(y, activation dtype, None, out_scale) makes of the T-rounded y ----
+// (nn/qmodule.py:281-299 re-quantizes every output of a quantized-activation layer; here the [M, N] tensor of T never exists.)  Per element exactly the
+// two kernels back to back: t as in the epilogue below - scaled, rounded to T, bias added, rounded again - then the rule of qh_quantize.h on t:
+// T(fp32(t) / fp32(out_scale)) with a correctly rounded divide, clamp_target, pack4.  The code type is the operands' own (int8 / e4m3 / e5m2).
+// Parking: one byte per feature, so a wave's 16 * NJ features are ONE row of ROWB = 64 (256-tile) or 32 (128-tile) bytes and one pass; a lane parks the
+// four codes of its four consecutive features as one dword, LPR = ROWB / 16 lanes read a row back as 16-byte chunks and store them: full 16-byte stores on
+// full tiles when N % 16 == 0, guarded bytes otherwise.  The 16-byte chunk index is XORed with (row / (256 / ROWB)) so that the 64 dwords of one parking
+// instruction (16 rows x 4 dwords of chunk jj) fall into 64 different banks.  Each wave reads only what it parked itself.
+template <int ODT, int KIND, int NJ, int BM, int BN, int NI>
+__device__ __forceinline__ void epilogue_codes(const Args& a, typename Acc<KIND>::V (&acc)[NJ][NI], uint8_t* smem, const uint8_t* tabp, int m0, int n0,
+                                               int wm, int wn, int wave, int lane, int i0) {
+  using E = Elem<ODT>;
+  using T = typename E::T;
+  static_assert(sizeof(T) == 2 && (KIND == K_I8 || KIND == K_F8E4M3 || KIND == K_F8E5M2), "codes: 8-bit operands, bf16 / fp16 scales");
+  constexpr int QDT = KIND == K_I8 ? QUANTO_HIP_I8 : KIND == K_F8E4M3 ? QUANTO_HIP_F8_E4M3FN : QUANTO_HIP_F8_E5M2;
+  const int M = a.M, N = a.N;
+  uint8_t* yq = reinterpret_cast<uint8_t*>(a.y);
+  const bool has_bias = a.bias != nullptr;
+  const bool full = (m0 + BM <= M) && (n0 + BN <= N) && (N % 16 == 0);
+  const float os = E::to_f32(*reinterpret_cast<const T*>(a.out_scale));  // in flight across the barrier and the table reads
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  constexpr int ROWB = NJ * 16, LPR = ROWB / 16;  // bytes per parked row, lanes per row on the read side
+  constexpr int SWR = 256 / ROWB;                 // rows per 256 bytes of parking: the swizzle period
+  constexpr int RPI = 64 / LPR;                   // rows per read / store iteration
+  uint8_t* park = smem + wave * (128 * ROWB);     // <= 8 KiB per wave
+  const T* tab = reinterpret_cast<const T*>(tabp);
+  constexpr int RH = NI >= 8 ? 2 : 1, NIH = NI / RH;  // rows leave in halves, as below
+  float sc[NJ][4], bv[NJ][4];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int nl = wn * (NJ * 16) + j * 16 + (lane >> 4) * 4;  // the lane's four consecutive features inside the tile
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      sc[j][r] = E::to_f32(tab[nl + r]);       // 1.0 without a scale
+      bv[j][r] = E::to_f32(tab[BN + nl + r]);  // 0.0 without a bias (not added below)
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < RH; ++h) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+      for (int i = h * NIH; i < (h + 1) * NIH; ++i) {
+        float q[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = (float)acc[j][i][r] * sc[j][r];  // the statements of the epilogue below: fp32 product, rounded to fp32 ...
+          asm volatile("" : "+v"(v));                // ... and only then to T
+          if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[j][r];
+          const T t = E::from_f32(v);                // the element qbytes_mm_bias stores
+          q[r] = clamp_target<QDT>(quotient_in<ODT>(E::to_f32(t), os));
+        }
+        const int row = i * 16 + (lane & 15);
+        const int c16 = j ^ ((row / SWR) & (LPR - 1));
+        *reinterpret_cast<uint32_t*>(park + row * ROWB + c16 * 16 + (lane >> 4) * 4) = pack4<QDT>(q);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    constexpr int ROWS_H = NIH * 16, TH = (ROWS_H + RPI - 1) / RPI;  // (a 16-row slice of a 128-tile fills half an iteration)
+#pragma unroll
+    for (int t = 0; t < TH; ++t) {
+      const int rl = t * RPI + lane / LPR;
+      if (ROWS_H % RPI != 0 && rl >= ROWS_H) continue;
+      const int row = h * ROWS_H + rl;
+      const int c16 = lane % LPR;
+      const uint4 v = *reinterpret_cast<const uint4*>(park + row * ROWB + ((c16 ^ ((row / SWR) & (LPR - 1))) * 16));
+      const int m = m0 + wm * 128 + i0 * 16 + row;
+      const int n = n0 + wn * ROWB + c16 * 16;
+      if (full) {
+        typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+        __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), reinterpret_cast<u32x4*>(yq + (size_t)m * N + n));
+      } else if (m < M) {
+        const uint8_t* e = reinterpret_cast<const uint8_t*>(&v);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (n + r < N) yq[(size_t)m * N + n + r] = e[r];
+      }
+    }
+  }
+}
+
+// QOUT: the quantized-output form above (`y` holds codes); the existing instantiations compile the statements below, unchanged
+template <int ODT, int KIND, int NJ, int BM, int BN, int NI = 8, bool QOUT = false>
 __device__ __forceinline__ void epilogue(const Args& a, typename Acc<KIND>::V (&acc)[NJ][NI], uint8_t* smem, const uint8_t* tabp, int m0, int n0, int wm,
                                          int wn, int wave, int lane, int i0 = 0) {
+  if constexpr (QOUT) return epilogue_codes<ODT, KIND, NJ, BM, BN, NI>(a, acc, smem, tabp, m0, n0, wm, wn, wave, lane, i0);
   using E = Elem<ODT>;
   using T = typename E::T;
   const int M = a.M, N = a.N;
@@ -187,7 +274,7 @@ __device__ __forceinline__ void splitk_store(const Args& a, typename Acc<KIND>::
   __syncthreads();
 }
 
-template <int ODT, int KIND, int NJ, int BM, int BN, int NWAVES, int SS>
+template <int ODT, int KIND, int NJ, int BM, int BN, int NWAVES, int SS, bool QOUT = false>
 __device__ __forceinline__ void splitk_reduce(const Args& a, uint8_t* smem, const uint8_t* tabp, int tile_lin, int sp, int m0, int n0, int wm, int wn, int wave,
                                               int lane, int tid) {
   using AV = typename Acc<KIND>::V;
@@ -253,7 +340,7 @@ __device__ __forceinline__ void splitk_reduce(const Args& a, uint8_t* smem, cons
     // loop below; hipcc otherwise computes them once ahead of all of them and carries ~150 registers through the reduction (measured: 130 - 470 spills)
     int zero;
     asm volatile("s_mov_b32 %0, 0" : "=s"(zero));
-    epilogue<ODT, KIND, NJ, BM, BN, NI>(a, L[0], smem, tabp, m0, n0 + zero, wm, wn, wave, lane, s * NI);
+    epilogue<ODT, KIND, NJ, BM, BN, NI, QOUT>(a, L[0], smem, tabp, m0, n0 + zero, wm, wn, wave, lane, s * NI);
   };
   // completion: S slices + the last arriver's sweep; whoever counts the last one leaves the state words as found
   auto complete = [&]() {
@@ -288,7 +375,7 @@ __device__ __forceinline__ void splitk_reduce(const Args& a, uint8_t* smem, cons
 // at twice the rate of the 16x16x32 fp8 MFMA - see the paired loop below.
 // SMALL: 128x128 tile with four waves of 128 x 32 (16 KiB stages: two workgroups share a CU) for shapes whose 256-tiles cannot
 // occupy the chip; otherwise 256x256 with eight waves of 128 x 64.
-template <int ODT, int KIND, bool PAIRED = false, bool SMALL = false>
+template <int ODT, int KIND, bool PAIRED = false, bool SMALL = false, bool QOUT = false>
 __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_kernel(const Args a) {
   using AV = typename Acc<KIND>::V;
   constexpr int BM = SMALL ? 128 : 256, BN = BM;
@@ -554,7 +641,7 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_kernel(co
 
   }
 
-  epilogue<ODT, KIND, NJ, BM, BN>(a, acc, smem, smem + RING_BYTES, m0, n0, wm, wn, wave, lane);
+  epilogue<ODT, KIND, NJ, BM, BN, 8, QOUT>(a, acc, smem, smem + RING_BYTES, m0, n0, wm, wn, wave, lane);
 }
 
 // =============================================================================================================================
@@ -578,7 +665,7 @@ __device__ __forceinline__ int swz128(int row) { return (row >> 1) & 7; }
 // Tried and dropped (r5, profiles/r05_native8_row128.md): the eight DMA pieces of a pair behind the first four token fragments of the odd
 // step instead of one behind each of the eight (w8a8 4096^3 53.0 -> 54.6 us: two back-to-back DMA issues stall the MFMA stream for longer than
 // the earlier landing saves), and no lgkmcnt(0) in front of the barrier (52.9 vs 53.0: the wait is free, so the rigorous form stays).
-template <int ODT, int KIND, bool SMALL = false>
+template <int ODT, int KIND, bool SMALL = false, bool QOUT = false>
 __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_r128_kernel(const Args a) {
   using AV = typename Acc<KIND>::V;
   constexpr bool MX = KIND == K_F8E4M3 || KIND == K_F8E5M2;
@@ -803,14 +890,14 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_r128_kern
   if (S > 1) {
     splitk_store<KIND, NJ, NWAVES>(a, acc, S, tile_lin, sp, tid);
     if (S == 2)
-      splitk_reduce<ODT, KIND, NJ, BM, BN, NWAVES, 2>(a, smem, smem + RING_BYTES, tile_lin, sp, m0, n0, wm, wn, wave, lane, tid);
+      splitk_reduce<ODT, KIND, NJ, BM, BN, NWAVES, 2, QOUT>(a, smem, smem + RING_BYTES, tile_lin, sp, m0, n0, wm, wn, wave, lane, tid);
     else if (S == 4)
-      splitk_reduce<ODT, KIND, NJ, BM, BN, NWAVES, 4>(a, smem, smem + RING_BYTES, tile_lin, sp, m0, n0, wm, wn, wave, lane, tid);
+      splitk_reduce<ODT, KIND, NJ, BM, BN, NWAVES, 4, QOUT>(a, smem, smem + RING_BYTES, tile_lin, sp, m0, n0, wm, wn, wave, lane, tid);
     else
-      splitk_reduce<ODT, KIND, NJ, BM, BN, NWAVES, 8>(a, smem, smem + RING_BYTES, tile_lin, sp, m0, n0, wm, wn, wave, lane, tid);
+      splitk_reduce<ODT, KIND, NJ, BM, BN, NWAVES, 8, QOUT>(a, smem, smem + RING_BYTES, tile_lin, sp, m0, n0, wm, wn, wave, lane, tid);
     return;
   }
-  epilogue<ODT, KIND, NJ, BM, BN>(a, acc, smem, smem + RING_BYTES, m0, n0, wm, wn, wave, lane);
+  epilogue<ODT, KIND, NJ, BM, BN, 8, QOUT>(a, acc, smem, smem + RING_BYTES, m0, n0, wm, wn, wave, lane);
 #ifdef QH_N8_STAMPS
   QH_N8_STAMP(3);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -818,13 +905,13 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_r128_kern
 #endif
 }
 
-template <int ODT, int KIND, bool SMALL>
+template <int ODT, int KIND, bool SMALL, bool QOUT>
 static int launch_r128(const Args& a, hipStream_t stream) {
   constexpr int T = SMALL ? 128 : 256;
   constexpr int need = 2 * 2 * T * 128 + FeatureTable<ODT, T>::BYTES;  // two buffers of 128-byte rows: 128 KiB (64 KiB for the 128-tile; the epilogue parks in it) + scale / bias table
   const int tiles = ((a.N + T - 1) / T) * ((a.M + T - 1) / T);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_native8_r128_kernel<ODT, KIND, SMALL>), hipFuncAttributeMaxDynamicSharedMemorySize, need);
-  hipLaunchKernelGGL((qbytes_native8_r128_kernel<ODT, KIND, SMALL>), dim3(tiles * a.S), dim3(SMALL ? 256 : 512), need, stream, a);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_native8_r128_kernel<ODT, KIND, SMALL, QOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, need);
+  hipLaunchKernelGGL((qbytes_native8_r128_kernel<ODT, KIND, SMALL, QOUT>), dim3(tiles * a.S), dim3(SMALL ? 256 : 512), need, stream, a);
   return launch_status();
 }
 
@@ -835,14 +922,14 @@ static int raster_group() {
   return g < 1 ? 1 : g;
 }
 
-template <int ODT, int KIND, bool PAIRED, bool SMALL>
+template <int ODT, int KIND, bool PAIRED, bool SMALL, bool QOUT>
 static int launch_cfg(const Args& a, hipStream_t stream) {
   constexpr int T = SMALL ? 128 : 256;
   constexpr int need = STAGES * 2 * T * BK + FeatureTable<ODT, T>::BYTES;  // 128 KiB (64 KiB for the 128-tile: two workgroups per CU; the epilogue parks in it) + scale / bias table
   const int tiles = ((a.N + T - 1) / T) * ((a.M + T - 1) / T);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_native8_kernel<ODT, KIND, PAIRED, SMALL>),
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_native8_kernel<ODT, KIND, PAIRED, SMALL, QOUT>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, need);
-  hipLaunchKernelGGL((qbytes_native8_kernel<ODT, KIND, PAIRED, SMALL>), dim3(tiles), dim3(SMALL ? 256 : 512), need, stream, a);
+  hipLaunchKernelGGL((qbytes_native8_kernel<ODT, KIND, PAIRED, SMALL, QOUT>), dim3(tiles), dim3(SMALL ? 256 : 512), need, stream, a);
   return launch_status();
 }
 
@@ -898,7 +985,7 @@ static size_t plan_workspace(const Plan& p, int64_t M, int64_t N) {
   return (size_t)QUANTO_HIP_WS_COUNTER_BYTES + (size_t)tiles * p.S * ((size_t)T * T * 4);  // one 4-byte accumulator per tile element and split
 }
 
-template <int ODT, int KIND>
+template <int ODT, int KIND, bool QOUT = false>
 static int launch(Args a, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   constexpr int ES = (KIND == K_BF16 || KIND == K_F16) ? 2 : 1;
   const bool ws_ok = workspace && reinterpret_cast<uintptr_t>(workspace) % 16 == 0;
@@ -911,16 +998,16 @@ static int launch(Args a, void* workspace, size_t workspace_bytes, hipStream_t s
   const bool small = p.small;
   // 128-byte rows (full-line vector-L1 fills, one barrier per 128 bytes of K) whenever K allows
   if ((a.K * ES) % 128 == 0 && env_int("QUANTO_HIP_NATIVE8_ROW128", 1) != 0)
-    return small ? launch_r128<ODT, KIND, true>(a, stream) : launch_r128<ODT, KIND, false>(a, stream);
+    return small ? launch_r128<ODT, KIND, true, QOUT>(a, stream) : launch_r128<ODT, KIND, false, QOUT>(a, stream);
   // 64-byte rows: K * element size = 64 (mod 128).  (r6: the PAIRED instantiations of this kernel - two 64-byte tiles per K = 128 MX-format MFMA - were
   // reachable only where the 128-byte-row kernel applies as well, i.e. through QUANTO_HIP_NATIVE8_ROW128=0, and left the product library; the
   // loop stays in the source for probes built with -DQH_N8_EXPERIMENTS)
 #ifdef QH_N8_EXPERIMENTS
   constexpr bool FP8 = KIND == K_F8E4M3 || KIND == K_F8E5M2;
   if (FP8 && (a.K * ES) % 128 == 0 && env_int("QUANTO_HIP_PAIRED", 1) != 0)
-    return small ? launch_cfg<ODT, KIND, true, true>(a, stream) : launch_cfg<ODT, KIND, true, false>(a, stream);
+    return small ? launch_cfg<ODT, KIND, true, true, QOUT>(a, stream) : launch_cfg<ODT, KIND, true, false, QOUT>(a, stream);
 #endif
-  return small ? launch_cfg<ODT, KIND, false, true>(a, stream) : launch_cfg<ODT, KIND, false, false>(a, stream);
+  return small ? launch_cfg<ODT, KIND, false, true, QOUT>(a, stream) : launch_cfg<ODT, KIND, false, false, QOUT>(a, stream);
 }
 
 }  // namespace n8
@@ -974,6 +1061,23 @@ int qbytes_mm_native8(const void* a, const void* b, const void* s, const void* b
   if (out_dtype == QUANTO_HIP_BF16) { QH_KIND(QUANTO_HIP_BF16); }
   if (out_dtype == QUANTO_HIP_F16) { QH_KIND(QUANTO_HIP_F16); }
   QH_KIND(QUANTO_HIP_F32);
+#undef QH_KIND
+}
+
+// The same product with the output quantization of the layer in its epilogue (n8::epilogue_codes): yq[M, N] = codes in a_dtype of the mid_dtype-rounded
+// product at the per-tensor scale out_scale[0] - bit-identical to quantize_symmetric(qbytes_mm_native8(...)).  Serves what qbytes_native8_supported serves with
+// a 16-bit mid_dtype; plan, split and workspace are those of qbytes_mm_native8 (the planner does not look at the output).
+int qbytes_mm_native8_q(const void* a, const void* b, const void* s, const void* bias, const void* out_scale, void* yq, int64_t M, int64_t N, int64_t K,
+                        int a_dtype, int b_dtype, int mid_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (!qbytes_native8_supported(M, N, K, a_dtype, b_dtype, mid_dtype) || mid_dtype == QUANTO_HIP_F32) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(yq)) % 16) return QUANTO_HIP_EALIGN;
+  n8::Args args{{a, reinterpret_cast<const uint8_t*>(b), s, bias, yq, (int)M, (int)N, (int)K, n8::raster_group(), 1, nullptr, nullptr}, 0, out_scale};
+#define QH_KIND(ODT)                                                                                                          \
+  if (a_dtype == QUANTO_HIP_I8) return n8::launch<ODT, n8::K_I8, true>(args, workspace, workspace_bytes, stream);             \
+  if (a_dtype == QUANTO_HIP_F8_E4M3FN) return n8::launch<ODT, n8::K_F8E4M3, true>(args, workspace, workspace_bytes, stream);  \
+  return n8::launch<ODT, n8::K_F8E5M2, true>(args, workspace, workspace_bytes, stream)
+  if (mid_dtype == QUANTO_HIP_BF16) { QH_KIND(QUANTO_HIP_BF16); }
+  QH_KIND(QUANTO_HIP_F16);
 #undef QH_KIND
 }
 

@@ -8,7 +8,7 @@
 // to the tensor dtype T (what aten's div does through its opmath type); integer targets are then rounded half-to-even
 // *in T* (exact: |q| <= 256 after the clamp matters only) and clamped to [-128, 127]; float8 targets are clamped to the
 // finite range and converted with the hardware's round-to-nearest-even OCP converters (v_cvt_pk_fp8_f32 / bf8).
-#include "qh_common.h"
+#include "qh_quantize.h"  // clamp_target, pack4, quotient_in: shared with the code-storing GEMM epilogue (qmm_native8.hip)
 
 namespace qh {
 namespace {
@@ -16,32 +16,6 @@ namespace {
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 enum { SCALE_TENSOR = QUANTO_HIP_SCALE_PER_TENSOR, SCALE_FIRST = QUANTO_HIP_SCALE_AXIS_FIRST, SCALE_LAST = QUANTO_HIP_SCALE_AXIS_LAST };
-
-template <int ODT>
-__device__ __forceinline__ float clamp_target(float q) {
-  if constexpr (ODT == QUANTO_HIP_I8) {
-    q = __builtin_rintf(q);
-    return __builtin_fminf(__builtin_fmaxf(q, -128.f), 127.f);
-  } else if constexpr (ODT == QUANTO_HIP_F8_E4M3FN) {
-    return __builtin_fminf(__builtin_fmaxf(q, -448.f), 448.f);
-  } else {
-    return __builtin_fminf(__builtin_fmaxf(q, -57344.f), 57344.f);
-  }
-}
-
-template <int ODT>
-__device__ __forceinline__ uint32_t pack4(const float* q) {
-  if constexpr (ODT == QUANTO_HIP_I8) {
-    return ((uint32_t)(int)q[0] & 0xFFu) | (((uint32_t)(int)q[1] & 0xFFu) << 8) | (((uint32_t)(int)q[2] & 0xFFu) << 16) |
-           (((uint32_t)(int)q[3] & 0xFFu) << 24);
-  } else if constexpr (ODT == QUANTO_HIP_F8_E4M3FN) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
-    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], w, true);
-  } else {
-    int w = __builtin_amdgcn_cvt_pk_bf8_f32(q[0], q[1], 0, false);
-    return (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(q[2], q[3], w, true);
-  }
-}
 
 // 8 elements per thread and iteration: one 16-byte (16-bit T) or two 16-byte (fp32) loads, one 8-byte store.
 template <int IDT, int ODT, int MODE>
@@ -72,24 +46,24 @@ __global__ void __launch_bounds__(256) quantize_symmetric_kernel(const typename 
       const float s1 = left < 8 ? E::to_f32(scale[r0 + 1 < (numel / inner) ? r0 + 1 : r0]) : s0;
       if (inner >= 8) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) q[k] = E::to_f32(e[k]) / (k < left ? s0 : s1);
+        for (int k = 0; k < 8; ++k) q[k] = quotient_in<IDT>(E::to_f32(e[k]), k < left ? s0 : s1);
       } else {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) q[k] = E::to_f32(e[k]) / E::to_f32(scale[(i0 + k) / inner]);
+        for (int k = 0; k < 8; ++k) q[k] = quotient_in<IDT>(E::to_f32(e[k]), E::to_f32(scale[(i0 + k) / inner]));
       }
     } else if constexpr (MODE == SCALE_LAST) {
       int64_t c = i0 % inner;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        q[k] = E::to_f32(e[k]) / E::to_f32(scale[c]);
+        q[k] = quotient_in<IDT>(E::to_f32(e[k]), E::to_f32(scale[c]));
         c = c + 1 == inner ? 0 : c + 1;
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) q[k] = E::to_f32(e[k]) / s_tensor;
+      for (int k = 0; k < 8; ++k) q[k] = quotient_in<IDT>(E::to_f32(e[k]), s_tensor);
     }
 #pragma unroll
-    for (int k = 0; k < 8; ++k) q[k] = clamp_target<ODT>(E::to_f32(E::from_f32(q[k])));
+    for (int k = 0; k < 8; ++k) q[k] = clamp_target<ODT>(q[k]);
     uint2 w;
     w.x = pack4<ODT>(q);
     w.y = pack4<ODT>(q + 4);
@@ -105,7 +79,7 @@ __global__ void __launch_bounds__(256) quantize_symmetric_kernel(const typename 
         s = E::to_f32(scale[i % inner]);
       else
         s = s_tensor;
-      float q[4] = {clamp_target<ODT>(E::to_f32(E::from_f32(E::to_f32(x[i]) / s))), 0.f, 0.f, 0.f};
+      float q[4] = {clamp_target<ODT>(quotient_in<IDT>(E::to_f32(x[i]), s)), 0.f, 0.f, 0.f};
       out[i] = (uint8_t)(pack4<ODT>(q) & 0xFFu);
     }
   }

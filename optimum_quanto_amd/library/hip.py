@@ -121,6 +121,8 @@ _PROTOTYPES = {
     "quanto_hip_qbytes_mm_workspace_size": (_i64, [_i64] * 3 + [_ci] * 4),
     "quanto_hip_qbytes_mm_plan": (_ci, [_i64] * 3 + [_ci] * 4 + [_pci, _pi64]),
     "quanto_hip_qbytes_mm_pick": (_ci, [_i64] * 3 + [_ci] * 3),
+    "quanto_hip_qbytes_mm_q_ws": (_ci, [_vp] * 6 + [_i64] * 3 + [_ci] * 4 + [_vp, _sz, _vp]),
+    "quanto_hip_qbytes_mm_q_plan": (_ci, [_i64] * 3 + [_ci] * 4 + [_pci, _pi64]),
     "quanto_hip_quantize_symmetric": (_ci, [_vp] * 3 + [_i64] * 2 + [_ci] * 3 + [_vp]),
     "quanto_hip_dequantize_symmetric": (_ci, [_vp] * 3 + [_i64] + [_ci] * 2 + [_vp]),
     "quanto_hip_quantize_affine": (_ci, [_vp] * 4 + [_i64] * 2 + [_ci] * 4 + [_vp]),
@@ -720,6 +722,53 @@ class _Bindings:
             self._check(st, "qbytes_mm")
         return y if a.dim() == 2 else y.reshape(*a.shape[:-1], N)
 
+    # -- quanto::qbytes_mm_q ------------------------------------------------------------------------
+    def qbytes_mm_q(self, a, b, scales, bias, out_scale):
+        """``quantize_symmetric(qbytes_mm_bias(a, b, scales, bias), a.dtype, None, out_scale)`` in one launch (csrc/qmm_native8.hip, the epilogue that
+        stores codes), or None when the library does not serve the call (QUANTO_HIP_ENOTSUP: fp32 scales, mixed operand dtypes, K not a multiple of 64,
+        the size limits) or a view is misaligned: the caller then runs the two ops."""
+        if not (a.is_cuda and b.is_cuda and scales.is_cuda and out_scale.is_cuda and (bias is None or bias.is_cuda)):
+            raise QuantoHipError("quanto_hip kernels only accept tensors on a ROCm device")
+        N, K = b.shape
+        if scales.numel() != N:
+            raise QuantoHipError(f"qbytes_mm_q expects one scale per output feature ({N}), got {tuple(scales.shape)}")
+        if a.dim() == 0 or a.shape[-1] != K:
+            raise QuantoHipError(f"qbytes_mm_q: input of shape {tuple(a.shape)} does not end in in_features = {K}")
+        if out_scale.numel() != 1:
+            raise QuantoHipError("qbytes_mm_q: the output scale is per-tensor (one element)")
+        sdt = scales.dtype
+        adt, bdt, odt = _DTYPES.get(a.dtype), _DTYPES.get(b.dtype), _DTYPES.get(sdt)
+        if adt is None or bdt is None or odt is None or a.dtype.itemsize != 1:
+            return None
+        a2 = a if a.dim() == 2 and a.is_contiguous() else a.reshape(-1, K).contiguous()
+        if not b.is_contiguous():
+            b = b.contiguous()
+        s = scales if scales.dim() == 1 and scales.is_contiguous() else scales.reshape(-1).contiguous()
+        if bias is not None and (bias.dtype != sdt or not bias.is_contiguous()):
+            bias = bias.to(sdt).contiguous()
+        if out_scale.dtype != sdt:
+            out_scale = out_scale.to(sdt)  # what quantize_symmetric does with a scale of another dtype
+        M = a2.shape[0]
+        c = self._c
+        st, k, ws_bytes = 0, KERNEL_NATIVE8, 0
+        try:
+            k, ws_bytes = self._plan("qbytes_mm_q", (M, N, K, adt, bdt, odt),
+                                     lambda: self._ask(c.quanto_hip_qbytes_mm_q_plan, M, N, K, adt, bdt, odt, KERNEL_AUTO))
+        except QuantoHipError:
+            return None  # not served (the plan entry applies the rule of the launch entry)
+        yq = torch.empty((M, N), dtype=a.dtype, device=a.device)
+        if M == 0:
+            return yq.reshape(*a.shape[:-1], N)
+        if (a2.data_ptr() | b.data_ptr() | yq.data_ptr()) % 16:
+            return None
+        with _DeviceGuard(a.device) as stream:
+            wp = self._zeroed_workspace(a.device, ws_bytes, stream).data_ptr() if ws_bytes > 0 else 0  # split-K arrival counters: zero on entry, left zero
+            st = c.quanto_hip_qbytes_mm_q_ws(a2.data_ptr(), b.data_ptr(), s.data_ptr(), 0 if bias is None else bias.data_ptr(), out_scale.data_ptr(),
+                                             yq.data_ptr(), M, N, K, adt, bdt, odt, k, wp, max(ws_bytes, 0), stream)
+        if st != 0:
+            self._check(st, "qbytes_mm_q")
+        return yq if a.dim() == 2 else yq.reshape(*a.shape[:-1], N)
+
 
 class QuantoHipExtension(NativeLibrary):
     """The ``quanto_hip`` extension (name expected by the reference's tests/library/test_extensions.py:23-24)."""
@@ -731,7 +780,7 @@ class QuantoHipExtension(NativeLibrary):
             root_dir=csrc,
             lib_path=os.path.join(_PKG_DIR, "lib", "libquanto_hip.so"),
             sources=["c_api.hip", "unpack.hip", "naive_mm.hip", "qbits_gemv.hip", "qbytes_gemv.hip", "qmm_mfma.hip", "qconv_mfma.hip", "qconv_a8.hip", "qconv_depthwise.hip", "qmm_mfma_large.hip", "qmm_large_common.h", "qbits_skinny.hip", "qbits_mmv.hip", "qbits_mfma_fused.hip", "qbits_a8_fused.hip", "qbits_mfma_large.hip", "qbytes_skinny.hip", "qmm_native8.hip", "qmm_f32.hip", "quantize.hip",
-                     "qh_common.h", "qh_conv.h", "qh_mfma.h", os.path.join("..", "..", "include", "quanto_hip.h")],
+                     "qh_common.h", "qh_conv.h", "qh_mfma.h", "qh_quantize.h", os.path.join("..", "..", "include", "quanto_hip.h")],
         )
         self._bindings = None
 

@@ -147,6 +147,29 @@ _register("qbytes_mm", "(Tensor A, Tensor B, Tensor scales) -> Tensor", qbytes_m
 _register("qbytes_mm_bias", "(Tensor A, Tensor B, Tensor scales, Tensor? bias) -> Tensor", qbytes_mm_bias_hip, default=qbytes_mm_bias_default)
 
 
+def qbytes_mm_q_default(activations, weights, output_scales, bias, out_scale):
+    """The two-op sequence of a quantized-activation layer (tensor/weights/qbytes.py:72-81, then nn/qmodule.py:281-299): the product in the scales' dtype,
+    re-quantized per-tensor to the activations' own 8-bit dtype."""
+    out = torch.ops.quanto.qbytes_mm_bias(activations, weights, output_scales, bias)
+    return torch.ops.quanto.quantize_symmetric(out, activations.dtype, None, out_scale.to(out.dtype).reshape(()))
+
+
+def qbytes_mm_q_hip(activations, weights, output_scales, bias, out_scale):
+    """ROCm: the product kernel's epilogue stores the codes (csrc/qmm_native8.hip); what the library does not serve (ENOTSUP) and misaligned views run the
+    two-op sequence on the existing kernels - the caller always gets codes."""
+    n = weights.shape[0]
+    if weights.ndim == 2 and output_scales.numel() == n and out_scale.numel() == 1:
+        out = quanto_hip.lib.qbytes_mm_q(activations, weights, output_scales, bias, out_scale)
+        if out is not None:
+            return out
+    return qbytes_mm_q_default(activations, weights, output_scales, bias, out_scale)
+
+
+# new op: the product of a W8A8 layer with the layer's output quantization fused into the kernel epilogue - bit-identical to
+# quantize_symmetric(qbytes_mm_bias(...)), one launch and no [M, N] float tensor
+_register("qbytes_mm_q", "(Tensor A, Tensor B, Tensor scales, Tensor? bias, Tensor out_scale) -> Tensor", qbytes_mm_q_hip, default=qbytes_mm_q_default)
+
+
 def qbytes_conv2d_default(input, weight, scales, bias, stride, padding, dilation):
     """What the reference computes for F.conv2d on a WeightQBytesTensor (nn/qconv2d.py:54-55 -> qfallback): dequantize, float convolution."""
     w = scales.reshape(-1, 1, 1, 1).to(input.dtype) * weight.to(input.dtype)

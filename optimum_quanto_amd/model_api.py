@@ -4,10 +4,10 @@ from typing import Any, Dict, List, Optional, Union
 
 import torch
 
-from .nn import QModuleMixin, quantize_module
+from .nn import QLinear, QModuleMixin, quantize_module
 from .tensor import Optimizer, QTensor, qtype
 
-__all__ = ["quantize", "freeze", "requantize", "quantization_map"]
+__all__ = ["quantize", "freeze", "requantize", "quantization_map", "fuse_output_quantization"]
 
 
 def _set_module_by_name(parent: torch.nn.Module, name: str, child: torch.nn.Module) -> None:
@@ -156,3 +156,32 @@ def quantization_map(model: torch.nn.Module) -> Dict[str, Dict[str, str]]:
                 "activations": "none" if m.activation_qtype is None else m.activation_qtype.name,
             }
     return config
+
+
+_FUSED_OUTPUT_DTYPES = (torch.int8, torch.float8_e4m3fn, torch.float8_e5m2)  # the operand pairs quanto::qbytes_mm_q serves
+
+
+def fuse_output_quantization(model: torch.nn.Module, enable: bool = True) -> List[str]:
+    """Opt in to (``enable=False``: out of) fused output quantization: every frozen ``QLinear`` with an 8-bit weight qtype, an activation qtype of the
+    same family (qint8 x qint8, qfloat8_e4m3fn x qfloat8_e4m3fn, qfloat8_e5m2 x qfloat8_e5m2) and its output hook still registered is marked, and
+    its forward then gets the output codes from the product kernel's epilogue (``quanto::qbytes_mm_q``) instead of writing the float output and
+    quantizing it in a second pass - bit-identical codes, same ``output_scale``.  Returns the names of the marked (unmarked) modules.
+
+    Not automatic: forward hooks registered by the user and calibration passes read a module's float output before its own hook quantizes it; a marked
+    module hands them codes.  Calibrate first, then call this.  ``QConv2d``, sub-byte weights, fp32 modules and other module classes are never marked;
+    the mark is not saved with the state dict."""
+    names = []
+    for name, m in model.named_modules():
+        if type(m) is not QLinear:
+            continue
+        if not enable:
+            if m._fuse_output_quantization:
+                m._fuse_output_quantization = False
+                names.append(name)
+            continue
+        wq, aq = m.weight_qtype, m.activation_qtype
+        if (m.frozen and wq is not None and aq is not None and wq.bits == 8 and wq.dtype == aq.dtype and aq.dtype in _FUSED_OUTPUT_DTYPES and "output" in m._quantize_hooks
+                and m.weight._scale.dtype in (torch.bfloat16, torch.float16)):
+            m._fuse_output_quantization = True
+            names.append(name)
+    return names

@@ -3,7 +3,7 @@ from typing import Optional
 
 import torch
 
-from ..tensor import Optimizer, QTensor, qtype
+from ..tensor import ActivationQBytesTensor, Optimizer, QTensor, WeightQBytesTensor, qtype
 from .module import QModuleMixin, register_qmodule
 
 __all__ = ["QLinear"]
@@ -22,6 +22,20 @@ class QLinear(QModuleMixin, torch.nn.Linear):
         # activation tensor the weight class's handler is called directly: the same code path minus torch's override dispatch
         # (C++ -> handle_torch_function -> Python, ~2 us of the ~15 us a decode-shaped call costs on the host)
         w = self.qweight
+        if self._fuse_output_quantization and self._codes_from_epilogue(input, w):
+            # marked by fuse_output_quantization: product and output quantization in one op (quanto::qbytes_mm_q), bit-identical to the product
+            # followed by the output hook - which then passes these codes through
+            codes = torch.ops.quanto.qbytes_mm_q(input._data, w._data, input._scale * w._scale, self.bias, self.output_scale)
+            return ActivationQBytesTensor(self.activation_qtype, codes.size(), codes.stride(), codes, self.output_scale)
         if type(input) is torch.Tensor and isinstance(w, QTensor):
             return type(w).__torch_function__(torch.nn.functional.linear, (type(w),), (input, w, self.bias))
         return torch.nn.functional.linear(input, w, bias=self.bias)
+
+    def _codes_from_epilogue(self, input, w) -> bool:
+        """Whether this call is the one the fused op computes: stored codes of the module's own activation qtype with a scalar scale against a frozen
+        8-bit weight, the output hook still in place, no gradient wanted (the op has no backward)."""
+        if not (isinstance(input, ActivationQBytesTensor) and type(w) is WeightQBytesTensor and self.frozen and "output" in self._quantize_hooks):
+            return False
+        if input.qtype != self.activation_qtype or input._scale.numel() != 1 or input._data.dtype != w._data.dtype:
+            return False
+        return not (torch.is_grad_enabled() and (input.requires_grad or w.requires_grad or (self.bias is not None and self.bias.requires_grad)))

@@ -62,6 +62,8 @@ class QModuleMixin(ABC):
         self.weight_group_size = self._pick_group_size()
         self.optimizer = optimizer if optimizer is not None else self._default_optimizer()
         self._quantize_hooks = {}
+        # opt-in (model_api.fuse_output_quantization): the product kernel stores the output codes itself.  A plain attribute: not part of the state dict
+        self._fuse_output_quantization = False
         if self.activation_qtype is not None:
             self._hook_activations(quantize_input)
         # calibrated by a Calibration pass; scalars in the weight's dtype
@@ -98,6 +100,7 @@ class QModuleMixin(ABC):
         handle = self._quantize_hooks.pop("output", None)
         if handle is not None:
             handle.remove()
+        self._fuse_output_quantization = False  # the fused forward would quantize what the caller has just asked to keep float
 
     @classmethod
     def from_module(cls, module: torch.nn.Module, weights=None, activations=None, optimizer: Optional[Optimizer] = None):
@@ -158,6 +161,8 @@ class QModuleMixin(ABC):
         return first
 
     def quantize_output(self, module: torch.nn.Module, input: torch.Tensor, output: torch.Tensor) -> torch.Tensor:
+        if isinstance(output, ActivationQBytesTensor) and output.qtype == self.activation_qtype:
+            return output  # the forward already stored codes at output_scale (fused output quantization)
         return quantize_activation(output, qtype=self.activation_qtype, scale=self.output_scale)
 
     # -- serialisation: a frozen weight travels as its inner tensors (weight._data, weight._scale, ...) -----------------------
