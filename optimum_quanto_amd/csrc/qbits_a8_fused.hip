@@ -11,9 +11,10 @@
 // the other fused kernels.  For int8 activations the result is a pure function of the integers: bit-identical to an fp32 fma chain
 // over the exact group sums (oracle/quanto_oracle.py::qbits_mm_a8_chain), whichever tile or split computes it in the unsplit form.
 //
-// Structure = qbits_mfma_fused.hip (workgroup = 8 waves, BM tokens x 128 features, wave = all BM tokens x 16 features, K-tile = one group of 128, LDS-DMA
-// ring of two stages, scale tables parked in LDS, group accumulators double-buffered so that the fold of tile kt-1 is sliced over the matrix steps of tile
-// kt, split-K with a deterministic last-arriver reduce), with 1-byte activations (128-byte LDS rows) and:
+// Structure: the group-fused GEMM of qh_group_fused.h, which holds what this kernel shares with qbits_mfma_fused.hip (workgroup = 8 waves, BM tokens x 128
+// features, wave = all BM tokens x 16 features, K-tile = one group of 128, LDS-DMA ring of two stages, scale tables parked in LDS, group accumulators
+// double-buffered so that the fold of tile kt-1 is sliced over the matrix steps of tile kt, split-K with a deterministic last-arriver reduce, the planner),
+// with 1-byte activations (128-byte LDS rows) and:
 //   * int8: a weight operand is the lane's nibble plane of 16 packed bytes - ((raw >> 4 plane) & 0x0F0F0F0F), TWO VALU per four weights (the bf16 kernel: one
 //     per weight) -, two K = 64 MFMAs per fragment and group, int32 group accumulator -> v_cvt_f32_i32 + two FMAs in the fold;
 //   * fp8: nibbles -> e4m3 codes through a 16-entry byte table (two v_perm over the low / high half of the table + one v_perm that picks by bit 3: seven
@@ -25,14 +26,13 @@
 // e4m3 values, so nothing else changes.  e5m2 activations (r7): the MX-format instruction takes its A and B formats independently - the weight operand (A)
 // stays e4m3, the activation operand (B) is read as bf8 (blgp = 1) in the product and in the all-ones group sum; an e5m2 value times an integer below 16 is
 // exact in fp32, as for e4m3.  Instantiated: {bf16, fp16} x {int8, e4m3, e5m2} x {float shift, zero-point} x {64, 128 tokens} x {int4, int2}.
-#include <type_traits>
-
-#include "qh_mfma.h"
+#include "qh_group_fused.h"
 
 namespace qh {
 namespace a8 {
 
-constexpr int BK = 128, NF = 128, WAVES = 8, STAGES = 2;  // NF: output features per workgroup, either weight width
+using namespace gf;  // BK, NF, WAVES, STAGES and the shared pieces
+
 // weight geometry of a workgroup: VPI features per packed byte (planes), PR packed rows (NF / VPI), RW packed rows per wave (16 features / VPI),
 // WP waves that request a weight piece of 8 rows x 128 B per tile (int4: all eight, 8 KiB; int2: waves 0..3, 4 KiB)
 template <int BITS>
@@ -48,7 +48,6 @@ struct Geo {
   static_assert(XP >= 1 && (MI == 4 || MI == 8), "tile geometry");
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
@@ -112,13 +111,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
     m = m < M ? m : M - 1;
     xsrc[u] = (uint32_t)((size_t)m * K + c * 16);  // M * K < 4 GiB, checked by the launcher
   }
-  uint32_t wsrc;
-  {
-    const int r = (WP == WAVES ? wave : wave & (WP - 1)) * 8 + (lane >> 3), c = (lane & 7) ^ (r & 7);  // int2: waves >= WP request nothing
-    int p = p0 + r;
-    p = p < P ? p : P - 1;
-    wsrc = (uint32_t)((size_t)p * K + c * 16);
-  }
+  const uint32_t wsrc = weight_piece_src(WP == WAVES ? wave : wave & (WP - 1), lane, p0, P, K);  // int2: waves >= WP request nothing
   const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_ptr_t)smem;
   auto issue_tile = [&](int kt_tile, int stage) {
     if (a.ablate & 4) kt_tile = 0;
@@ -129,23 +122,10 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
   };
   const int last = nk - 1;
 
-  // ---- prologue: tiles 0 and 1 requested, tables parked (thread -> feature tid & 127 = plane f / PR, packed row f % PR; groups tid >> 7, + 4, ...),
-  // ONE drain ----
+  // ---- prologue: tiles 0 and 1 requested, tables parked, ONE drain ----
   issue_tile(0, 0);
   issue_tile(nk > 1 ? 1 : 0, 1);
-  {
-    const int f = tid & (NF - 1);
-    int p = p0 + (f & (PR - 1));
-    p = p < P ? p : P - 1;
-    const size_t row = (size_t)(p + (f / PR) * P) * G + kt0;
-    for (int g = tid >> 7; g < nk; g += (WAVES * 64) >> 7) {
-      sz[(g * 2 + 0) * NF + f] = reinterpret_cast<const T*>(a.scale)[row + g];
-      if constexpr (INT_SHIFT)
-        sz[(g * 2 + 1) * NF + f] = E::from_f32((float)(int8_t) reinterpret_cast<const uint8_t*>(a.shift)[row + g]);
-      else
-        sz[(g * 2 + 1) * NF + f] = reinterpret_cast<const T*>(a.shift)[row + g];
-    }
-  }
+  QH_GF_FILL_TABLES(E, INT_SHIFT, PR, sz, a.scale, a.shift, tid, p0, P, G, kt0, nk);
   const float sx = E::to_f32(*reinterpret_cast<const T*>(a.a_scale));
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // hand-counted waits start from a known state
 
@@ -157,7 +137,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
   {
     const int r = wave * RW + (fi & (RW - 1));
 #pragma unroll
-    for (int h = 0; h < 2; ++h) woff[h] = X_BYTES + r * 128 + (((4 * h + fg) ^ (r & 7)) << 4);
+    for (int h = 0; h < 2; ++h) woff[h] = QH_GF_WEIGHT_OFF(X_BYTES, r, 4 * h + fg);
   }
   const uint32_t nib_shift = (fi / RW) * BITS;
   // the lane's 4 consecutive matrix rows 4 fg .. 4 fg + 3 = 4 consecutive packed rows of plane 4 fg / RW: 4 consecutive features inside the block
@@ -176,35 +156,9 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
   GV accgA[MI], accgB[MI];
   float s4[4], z4[4], xsp[MI];
   const int my_xs = wave < MI ? wave : -1;
-  auto load_sz = [&](int g) {
-    T s4t[4], z4t[4];
-    *reinterpret_cast<uint2*>(s4t) = *reinterpret_cast<const uint2*>(sz + (g * 2 + 0) * NF + floc);
-    *reinterpret_cast<uint2*>(z4t) = *reinterpret_cast<const uint2*>(sz + (g * 2 + 1) * NF + floc);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      s4[r] = E::to_f32(s4t[r]);
-      const float z = E::to_f32(z4t[r]);
-      z4[r] = INT_SHIFT ? s4[r] * z : z;  // scale * (q - zp) = scale * q - (scale * zp): one fp32 rounding of the product, stated in the oracle
-    }
-  };
-  auto load_xs = [&](int kt_prev) {
-#pragma unroll
-    for (int i = 0; i < MI; ++i) xsp[i] = xs_slot[(kt_prev & 1) * BM + i * 16 + fi];
-  };
-  // one element of the fold of a group: acc = fma(-z, A_g, fma(s, P_g, acc)) - as asm so that hipcc neither sinks the fold behind the matrix steps
-  // nor packs it (qbits_mfma_fused.hip)
-  auto fold_slice = [&](const GV (&pg)[MI], int q) {
-    const int i = q >> 2, r = q & 3;
-    float v = acc[i][r];
-    if constexpr (AK == A_I8) {
-      float p;
-      asm volatile("v_cvt_f32_i32 %1, %2\n\tv_fmac_f32 %0, %3, %1\n\tv_fma_f32 %0, -%4, %5, %0"
-                   : "+v"(v), "=&v"(p)
-                   : "v"(pg[i][r]), "v"(s4[r]), "v"(z4[r]), "v"(xsp[i]));
-    } else {
-      asm volatile("v_fmac_f32 %0, %1, %2\n\tv_fma_f32 %0, -%3, %4, %0" : "+v"(v) : "v"(s4[r]), "v"(pg[i][r]), "v"(z4[r]), "v"(xsp[i]));
-    }
-    acc[i][r] = v;
+  auto load_fold_inputs = [&](int g) {  // of group g of this workgroup, folded one tile later; the operands are the plain codes: no offset in the shift term
+    load_sz<DT, INT_SHIFT, false>(sz, g, floc, s4, z4);
+    load_xs<BM>(xs_slot, g, fi, xsp);
   };
 
   constexpr int STEPS = AK == A_I8 ? 2 * MI : MI;   // matrix steps per tile
@@ -228,10 +182,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
       xl[i] = *reinterpret_cast<const uint4*>(st + xoff[0] + i * 2048);
       xh[i] = *reinterpret_cast<const uint4*>(st + xoff[1] + i * 2048);
     }
-    if constexpr (have_prev) {
-      load_sz(kt - 1);
-      load_xs(kt - 1);
-    }
+    if constexpr (have_prev) load_fold_inputs(kt - 1);
     // weight operand of the tile: the lane's nibble plane of its 32 packed bytes
     uint32_t op[8];
     {
@@ -272,7 +223,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
       if constexpr (have_prev) {
         if (!(a.ablate & 1)) {
 #pragma unroll
-          for (int q = s * FPS; q < (s + 1) * FPS; ++q) fold_slice(pg, q);
+          for (int q = s * FPS; q < (s + 1) * FPS; ++q) fold_slice(acc, pg, q, s4, z4, xsp);
         }
       }
       // the fragment two ahead, once per token fragment (int8: fragments 2p+2, 2p+3 behind steps 0 and 2 of pair p - their registers are free: the
@@ -309,110 +260,22 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    load_sz(nk - 1);
-    load_xs(nk - 1);
+    load_fold_inputs(nk - 1);
 #pragma unroll
-    for (int q = 0; q < 4 * MI; ++q) fold_slice(pg, q);
+    for (int q = 0; q < 4 * MI; ++q) fold_slice(acc, pg, q, s4, z4, xsp);
   };
-  using yes = std::integral_constant<bool, true>;
-  using st0 = std::integral_constant<int, 0>;
-  using st1 = std::integral_constant<int, 1>;
-  tile(0, accgA, accgB, std::integral_constant<bool, false>{}, st0{});
-  int kt = 1;
-  for (; kt + 2 <= nk; kt += 2) {
-    tile(kt, accgB, accgA, yes{}, st1{});
-    tile(kt + 1, accgA, accgB, yes{}, st0{});
-  }
-  if (kt < nk) {
-    tile(kt, accgB, accgA, yes{}, st1{});
-    final_fold(accgB);
-  } else {
-    final_fold(accgA);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the re-requested last tile: nothing may land in LDS after the kernel moved on
-
-  // ---- split-K: the tail of qh_mfma.h (write-through partial tiles, arrival counter, last arriver adds in split order) ----
-  if (S > 1) {
-    const int tile_id = blockIdx.y * gridDim.x + blockIdx.x;
-    int* flag = reinterpret_cast<int*>(smem);
-    QH_SPLITK_ARRIVE(MI, WAVES * 64, a.partials, tile_id * S + sp, acc, a.counters + tile_id, flag, tid, (void)0, (void)0);
-    if (*flag != S - 1) return;
-    QH_SPLITK_SUM(MI, WAVES * 64, (BM == 64 ? 4 : 2), MI, a.partials, tile_id, S, acc, a.counters + tile_id, tid, (void)0);
-  }
-
-  // ---- epilogue: x activation scale, (+ bias), 4 consecutive features of one token per fragment: 8-byte stores ----
-  T* yg = reinterpret_cast<T*>(a.y);
-  const bool has_bias = a.bias != nullptr;
-  const int pl = p0 + wave * RW + froff;
-  const int n0 = pl + fplane * P;
-  float bv[4] = {0.f, 0.f, 0.f, 0.f};
-  if (has_bias) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bv[r] = pl + r < P ? E::to_f32(reinterpret_cast<const T*>(a.bias)[n0 + r]) : 0.f;
-  }
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int m = m0 + i * 16 + fi;
-    if (m < M) {
-      T out[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[i][r] * sx;
-        asm volatile("" : "+v"(v));  // the product is rounded to fp32 before anything else happens to it
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[r];
-        out[r] = E::from_f32(v);
-      }
-      if (pl + 3 < P && (N & 3) == 0) {
-        *reinterpret_cast<uint2*>(yg + (size_t)m * N + n0) = *reinterpret_cast<const uint2*>(out);
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (pl + r < P) yg[(size_t)m * N + n0 + r] = out[r];
-      }
-    }
-  }
+  QH_GF_FOR_EACH_TILE(nk, tile, final_fold, accgA, accgB);
+  if (S > 1) QH_GF_SPLITK(BM, MI, acc, a.partials, a.counters, S, sp, tid, smem);
+  // x activation scale (the product is rounded to fp32 before anything else happens to it), (+ bias)
+  QH_GF_EPILOGUE(E, MI, acc, a.y, a.bias, m0, fi, N, P, p0 + wave * RW + froff, fplane, m < M, v = v * sx; asm volatile("" : "+v"(v)));
 }
 
-inline int w_bytes(int bits) { return bits == 2 ? WGeo<2>::W_BYTES : WGeo<4>::W_BYTES; }
-inline int lds_bytes(int groups, int bm, int bits) { return STAGES * (bm * BK + w_bytes(bits)) + 2 * bm * 4 + groups * 2 * NF * 2; }
-// output tiles of NF features x bm tokens: the same count for either weight width (int4: 64 packed rows, int2: 32)
-inline int tiles_of(int64_t M, int64_t N, int bm) { return (int)(((N + NF - 1) / NF) * ((M + bm - 1) / bm)); }
-
-// Token tile and K split from the time model of qbits_mfma_fused.hip with this kernel's tile times (r6 sweep, profiles/r06_w4a8_*): 128-token tiles
-// once they alone give every CU a workgroup, 64-token tiles (two workgroups per CU) below; K split for few tiles.  QUANTO_HIP_A8_BM / _SPLIT force.
-// int2 runs the same model: its tile is the int4 tile with half the weight bytes (16 + 4 instead of 16 + 8 KiB through the vector L1 per group at
-// bm = 128), the tile count and the matrix steps are the same, and the model's job - which token tile and split - does not move with that.
-struct Plan {
-  int bm, S;
-  float us;
-};
-inline float model_us(int tiles, int nk, int bm, int S) {
-  const int wgs = tiles * S, rounds = (wgs + 255) / 256;
-  const float tail = S > 1 ? 3.5f + 0.5f * (float)wgs * (float)(bm * 512) * 1e-6f : 0.f;
-  return 5.8f + (float)rounds * (float)nk * (bm == 64 ? 0.45f : 0.75f) + tail;
-}
-inline Plan make_plan(int64_t M, int64_t N, int G, int bits) {
-  const int fbm = env_int("QUANTO_HIP_A8_BM", 0), fs = env_int("QUANTO_HIP_A8_SPLIT", 0);  // experiments / tests
-  Plan best{0, 0, 0.f};
-  for (int bm = 64; bm <= 128; bm += 64) {
-    if ((fbm == 64 || fbm == 128) && bm != fbm) continue;
-    const int tiles = tiles_of(M, N, bm);
-    for (int S = 1; S <= 8; S *= 2) {
-      if (G % S) break;
-      const int nk = G / S;
-      if (fs > 0 ? (S != fs) : (S > 1 && nk < 4)) continue;
-      if (lds_bytes(nk, bm, bits) > 160 * 1024) continue;
-      if (S > 1 && !ws_counters_fit(tiles)) continue;
-      const float us = model_us(tiles, nk, bm, S);
-      if (best.bm == 0 || us < best.us * 0.97f) best = Plan{bm, S, us};
-    }
-  }
-  return best;
-}
+// tile times of the time model (r6 sweep, us per 64- / 128-token tile), the forcing knobs, 1-byte activations, the weight tile of either width
+inline Unit unit(int bits) { return Unit{0.45f, 0.75f, "QUANTO_HIP_A8_BM", "QUANTO_HIP_A8_SPLIT", 1, bits == 2 ? WGeo<2>::W_BYTES : WGeo<4>::W_BYTES}; }
 
 template <int DT, int AK, bool INT_SHIFT, int BM, int BITS>
 static int launch_bm(const Args& a, hipStream_t stream) {
-  const int lds = lds_bytes(a.G / a.S, BM, BITS);
+  const int lds = lds_bytes(unit(BITS), a.G / a.S, BM);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbits_a8_fused_kernel<DT, AK, INT_SHIFT, BM, BITS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             lds);
   const dim3 grid((unsigned)((a.N + NF - 1) / NF), (unsigned)((a.M + BM - 1) / BM), (unsigned)a.S);
@@ -450,25 +313,20 @@ bool qbits_a8_supported(int64_t M, const PackedGeom& g, int a_dtype, int dtype) 
         (a_dtype == QUANTO_HIP_I8 || a_dtype == QUANTO_HIP_F8_E4M3FN || a_dtype == QUANTO_HIP_F8_E5M2) && g.N < (1 << 30) && g.K < (1 << 30) &&
         M * g.K < (1ll << 32) && g.N * g.K < (1ll << 33) && grid_yz_fits(M, 64)))  // grid.y = token tiles of the smaller tile the plan may take
     return false;
-  return a8::make_plan(M, g.N, (int)g.G, g.bits).bm != 0;
+  return gf::make_plan(a8::unit(g.bits), M, g.N, (int)g.G).bm != 0;
 }
 
 size_t qbits_a8_workspace(int64_t M, const PackedGeom& g) {
-  const a8::Plan p = a8::make_plan(M, g.N, (int)g.G, g.bits);
-  if (p.bm == 0 || p.S == 1) return 0;
-  return QUANTO_HIP_WS_COUNTER_BYTES + (size_t)a8::tiles_of(M, g.N, p.bm) * p.S * (a8::WAVES * 64) * ((p.bm / 16) * 16);
+  return gf::workspace_bytes(gf::make_plan(a8::unit(g.bits), M, g.N, (int)g.G), M, g.N);
 }
 
 int qbits_mm_a8(const void* act, const void* act_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
                 const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!qbits_a8_supported(M, g, a_dtype, dtype)) return QUANTO_HIP_ENOTSUP;
   if ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
-  a8::Plan p = a8::make_plan(M, g.N, (int)g.G, g.bits);
-  if (p.S > 1 && !ws_holds(workspace, workspace_bytes, qbits_a8_workspace(M, g))) {
-    p.S = 1;  // no scratch: unsplit, with whichever token tile lets the whole scale table fit
-    if (a8::lds_bytes((int)g.G, p.bm, g.bits) > 160 * 1024) p.bm = 64;
-    if (a8::lds_bytes((int)g.G, p.bm, g.bits) > 160 * 1024) return QUANTO_HIP_EINVAL;
-  }
+  const gf::Unit unit = a8::unit(g.bits);
+  gf::Plan p = gf::make_plan(unit, M, g.N, (int)g.G);
+  if (!gf::settle_for_workspace(unit, p, M, g.N, (int)g.G, workspace, workspace_bytes)) return QUANTO_HIP_EINVAL;
   const a8::Args a{reinterpret_cast<const uint8_t*>(act), act_scale, packed, scale, shift, bias, y, (int)M, (int)g.N, (int)g.K, (int)g.G, p.S,
                    reinterpret_cast<int*>(workspace),
                    p.S > 1 ? ws_partials(workspace) : nullptr,

@@ -24,13 +24,13 @@
 // chunk ^ (row & 7)).  Scales / shifts of the workgroup's 128 features for its groups are parked in LDS once (16-byte loads, issued
 // in front of the first tiles' DMA).  Split-K where the scale table does not fit (K = 14336 with 128-token tiles) and, with 64-token
 // tiles, to fill the chip: fp32 partial tiles through the workspace, write-through stores, arrival counter, the last workgroup adds
-// them in split order - the split-K tail of qh_mfma.h.
-#include <type_traits>
-
-#include "qh_mfma.h"
+// them in split order - the split-K tail of qh_mfma.h.  What this kernel has in common with qbits_a8_fused.hip is in qh_group_fused.h.
+#include "qh_group_fused.h"
 
 namespace qh {
 namespace fused4 {
+
+using namespace gf;  // BK, NF, WAVES, STAGES and the shared pieces
 
 // Token tile: BM = 128 (MI = 8 fragments per wave) for grids that fill the chip - 32 KiB of activations per 8 KiB of packed weights
 // and tile -, BM = 64 (MI = 4) for short prefills whose 128-token tiles would leave CUs idle ((512,4096,4096): 128 -> 256 workgroups).
@@ -38,7 +38,7 @@ namespace fused4 {
 // the tables of 32 groups and TWO workgroups share a CU (the kernel's 106-124 VGPRs always allowed four waves per SIMD) - out of phase, they
 // fill each other's barrier and wait slots: (1024,4096,4096) as 512 workgroups of 64 tokens 56.7 -> 49.5 us, (1536,...) 79.3 -> 73.3, (2048,...)
 // 98 -> 92.6; grids of one workgroup per CU do not notice the shallower ring ((512,4096,4096) 29.4 -> 29.3, (128,...) unsplit 27.6 -> 26.1).
-constexpr int BK = 128, PR = 64, WAVES = 8, DEPTH = 1, STAGES = 2;
+constexpr int PR = 64, DEPTH = 1;
 constexpr int W_BYTES = PR * BK;  // 8 KiB
 template <int BM>
 struct Geo {
@@ -48,8 +48,6 @@ struct Geo {
   static constexpr int OPS = XP + 1;            // vector-memory instructions per wave and tile: activation pieces + weight piece
   static_assert(W_BYTES == WAVES * 1024 && DEPTH * OPS <= 63 && (MI == 4 || MI == 8), "tile geometry");
 };
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct Args {
   const void* x;       // [M, K]
@@ -81,7 +79,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
   // its time (0.74 -> 0.67 us per 64-token tile), the tail cost 3.4 us per workgroup: (512,4096,4096) 28.5 -> 30.2 us.
   // layout: [STAGES x (activation tile | weight tile)] [xs: 2 x BM fp32 group sums of x] [sz: G x 2 x 128 features of T]
   float* xs_slot = reinterpret_cast<float*>(smem + STAGES * STAGE_BYTES);
-  constexpr int NF = 2 * PR;
+  static_assert(NF == 2 * PR, "two planes");
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -114,13 +112,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
     m = m < M ? m : M - 1;
     xsrc[u] = (uint32_t)(((size_t)m * K + c * 8) * 2);
   }
-  uint32_t wsrc;  // this wave's weight piece: packed rows 8*wave .. +7 of the tile, lane -> row lane>>3, position lane&7 holds chunk pos ^ (row & 7)
-  {
-    const int r = wave * 8 + (lane >> 3), c = (lane & 7) ^ (r & 7);
-    int p = p0 + r;
-    p = p < P ? p : P - 1;
-    wsrc = (uint32_t)((size_t)p * K + c * 16);  // (N/2) * K < 4 GiB, checked by the launcher
-  }
+  const uint32_t wsrc = weight_piece_src(wave, lane, p0, P, K);  // this wave's weight piece: packed rows 8*wave .. +7 of the tile
   const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_ptr_t)smem;
   const uint8_t* xbase = reinterpret_cast<const uint8_t*>(a.x);
   auto issue_tile = [&](int kt_tile, int stage) {  // activation pieces + weight piece of one tile: XP + 1 DMA instructions
@@ -174,18 +166,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
       }
     }
   } else {
-    // thread -> feature tid & 127 (plane = bit 6), groups (tid >> 7), +4, ...: no division in front of the loop
-    const int f = tid & (NF - 1);
-    int p = p0 + (f & (PR - 1));
-    p = p < P ? p : P - 1;
-    const size_t row = (size_t)(p + (f >> 6) * P) * G + kt0;
-    for (int g = tid >> 7; g < nk; g += (WAVES * 64) >> 7) {
-      sz[(g * 2 + 0) * NF + f] = reinterpret_cast<const T*>(a.scale)[row + g];
-      if constexpr (INT_SHIFT)
-        sz[(g * 2 + 1) * NF + f] = E::from_f32((float)(int8_t) reinterpret_cast<const uint8_t*>(a.shift)[row + g]);
-      else
-        sz[(g * 2 + 1) * NF + f] = reinterpret_cast<const T*>(a.shift)[row + g];
-    }
+    QH_GF_FILL_TABLES(E, INT_SHIFT, PR, sz, a.scale, a.shift, tid, p0, P, G, kt0, nk);
   }
   // the table code contains compiler-visible loads with compiler-placed waits: drain once so that the hand-counted waits below
   // start from a known state (tiles 0 and 1 have landed, nothing outstanding)
@@ -203,7 +184,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
   {
     const int r = wave * 8 + (fi & 7);
 #pragma unroll
-    for (int h = 0; h < 2; ++h) woff[h] = X_BYTES + r * 128 + (((4 * h + fg) ^ (r & 7)) << 4);
+    for (int h = 0; h < 2; ++h) woff[h] = QH_GF_WEIGHT_OFF(X_BYTES, r, 4 * h + fg);
   }
   const uint32_t nib_shift = (fi >> 3) * 4;
   // this lane's 4 consecutive features inside the block: plane fg >> 1, local packed rows wave*8 + 4*(fg & 1) + r
@@ -231,30 +212,9 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
   // r3: every wave used to run these products for all its fragments (a third of its MFMAs); now wave w runs them for fragment w only
   // and leaves the sums in LDS (xs_slot, double-buffered by tile parity) - the fold runs one tile later anyway, behind a barrier.
   const int my_xs = wave < MI ? wave : -1;
-  auto load_sz = [&](int g) {
-    T s4t[4], z4t[4];
-    *reinterpret_cast<uint2*>(s4t) = *reinterpret_cast<const uint2*>(sz + (g * 2 + 0) * NF + floc);
-    *reinterpret_cast<uint2*>(z4t) = *reinterpret_cast<const uint2*>(sz + (g * 2 + 1) * NF + floc);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      s4[r] = E::to_f32(s4t[r]);
-      const float z = E::to_f32(z4t[r]);
-      z4[r] = INT_SHIFT ? s4[r] * (z + Mma<DT>::OFFSET) : z + Mma<DT>::OFFSET * s4[r];
-    }
-  };
-  auto load_xs = [&](int kt_prev) {
-#pragma unroll
-    for (int i = 0; i < MI; ++i) xsp[i] = xs_slot[(kt_prev & 1) * BM + i * 16 + fi];
-  };
-  // slice q (0 .. 4 MI - 1) of the fold of one group: feature r = q & 3 of fragment i = q >> 2
-  // Two FMAs, as asm: left as C++, hipcc SINKS the whole fold (pure arithmetic whose result nobody reads before the next fold)
-  // out of the MFMA steps to the end of the loop body, where it runs as one block while the matrix pipe idles (and its SLP
-  // vectorizer turns it into v_pk_* there).  The operands were produced a tile ago (pg) or by LDS reads hipcc waits for.
-  auto fold_slice = [&](const f32x4 (&pg)[MI], int q) {
-    const int i = q >> 2, r = q & 3;
-    float v = acc[i][r];
-    asm volatile("v_fmac_f32 %0, %1, %2\n\tv_fma_f32 %0, -%3, %4, %0" : "+v"(v) : "v"(s4[r]), "v"(pg[i][r]), "v"(z4[r]), "v"(xsp[i]));
-    acc[i][r] = v;
+  auto load_fold_inputs = [&](int g) {  // of group g of this workgroup, folded one tile later
+    load_sz<DT, INT_SHIFT, true>(sz, g, floc, s4, z4);
+    load_xs<BM>(xs_slot, g, fi, xsp);
   };
 
   static_assert(STAGES == 2 && DEPTH == 1, "the stage of a tile is its parity: a compile-time tag below");
@@ -283,10 +243,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
     V8 xf[XR];
 #pragma unroll
     for (int u = 0; u < XD; ++u) xf[u] = *reinterpret_cast<const V8*>(st + xoff[u / MI] + (u % MI) * 4096);
-    if constexpr (have_prev) {
-      load_sz(kt - 1);
-      load_xs(kt - 1);
-    }
+    if constexpr (have_prev) load_fold_inputs(kt - 1);
 
     // 4 * MI steps (k-step t, token fragment i) of ONE product MFMA (+ the ones-product in the steps of this wave's XS fragment);
     // behind it a slice of the NEXT k-step's operand construction, a slice of the previous group's fold and the activation fragment
@@ -319,7 +276,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
 #pragma unroll
         for (int o = i * 8 / MI; o < (i + 1) * 8 / MI; ++o) conv_op(t + 1, o);
       }
-      if constexpr (have_prev) fold_slice(pg, s);
+      if constexpr (have_prev) fold_slice(acc, pg, s, s4, z4, xsp);
       if (s + XD < 4 * MI) xf[(s + XD) % XR] = *reinterpret_cast<const V8*>(st + xoff[(s + XD) / MI] + ((s + XD) % MI) * 4096);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -337,114 +294,22 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // the XS sums of the last tile
     asm volatile("" ::: "memory");
-    load_sz(nk_run - 1);
-    load_xs(nk_run - 1);
+    load_fold_inputs(nk_run - 1);
 #pragma unroll
-    for (int q = 0; q < 4 * MI; ++q) fold_slice(pg, q);
+    for (int q = 0; q < 4 * MI; ++q) fold_slice(acc, pg, q, s4, z4, xsp);
   };
-  using yes = std::integral_constant<bool, true>;
-  using st0 = std::integral_constant<int, 0>;
-  using st1 = std::integral_constant<int, 1>;
-  tile(0, accgA, accgB, std::integral_constant<bool, false>{}, st0{});
-  int kt = 1;
-  for (; kt + 2 <= nk_run; kt += 2) {
-    tile(kt, accgB, accgA, yes{}, st1{});
-    tile(kt + 1, accgA, accgB, yes{}, st0{});
-  }
-  if (kt < nk_run) {
-    tile(kt, accgB, accgA, yes{}, st1{});  // nk even: the last tile landed in set B
-    final_fold(accgB);
-  } else {
-    final_fold(accgA);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the re-requested tiles past the end: nothing may land in LDS after the kernel moved on
-
-  // ---- split-K: fp32 partial tiles through the workspace, the last workgroup of a tile adds them in split order (qh_mfma.h) ----
-  if (S > 1) {
-    const int tile_id = blockIdx.y * gridDim.x + blockIdx.x;
-    int* flag = reinterpret_cast<int*>(smem);
-    QH_SPLITK_ARRIVE(MI, WAVES * 64, a.partials, tile_id * S + sp, acc, a.counters + tile_id, flag, tid, (void)0, (void)0);
-    if (*flag != S - 1) return;
-    QH_SPLITK_SUM(MI, WAVES * 64, (BM == 64 ? 4 : 2), MI, a.partials, tile_id, S, acc, a.counters + tile_id, tid, (void)0);  // QB * MI float4 registers
-  }
-
-  // ---- epilogue: 4 consecutive features of one token per fragment: 8-byte stores -------------------------------------------------------
-  T* yg = reinterpret_cast<T*>(a.y);
-  const bool has_bias = a.bias != nullptr;
-  const int pl = p0 + wave * 8 + 4 * (fg & 1);  // first of the lane's 4 packed rows
-  const int n0 = pl + (fg >> 1) * P;            // 4 consecutive output features n0 .. n0+3
-  float bv[4] = {0.f, 0.f, 0.f, 0.f};
-  if (has_bias) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bv[r] = pl + r < P ? E::to_f32(reinterpret_cast<const T*>(a.bias)[n0 + r]) : 0.f;
-  }
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int m = m0 + i * 16 + fi;
-    if (m < M && !(a.ablate & 2)) {
-      T out[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[i][r];
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[r];
-        out[r] = E::from_f32(v);
-      }
-      if (pl + 3 < P && (N & 3) == 0) {
-        *reinterpret_cast<uint2*>(yg + (size_t)m * N + n0) = *reinterpret_cast<const uint2*>(out);
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (pl + r < P) yg[(size_t)m * N + n0 + r] = out[r];
-      }
-    }
-  }
+  QH_GF_FOR_EACH_TILE(nk_run, tile, final_fold, accgA, accgB);
+  if (S > 1) QH_GF_SPLITK(BM, MI, acc, a.partials, a.counters, S, sp, tid, smem);
+  // the lane's 4 packed rows wave*8 + 4*(fg & 1) .. + 3 of plane fg >> 1
+  QH_GF_EPILOGUE(E, MI, acc, a.y, a.bias, m0, fi, N, P, p0 + wave * 8 + 4 * (fg & 1), fg >> 1, m < M && !(a.ablate & 2), (void)0);
 }
 
-inline int lds_bytes(int groups, int bm) { return STAGES * (bm * BK * 2 + W_BYTES) + 2 * bm * 4 + groups * 2 * (2 * PR) * 2; }
-
-inline int tiles_of(int64_t M, int64_t N, int bm) { return (int)(((N / 2 + PR - 1) / PR) * ((M + bm - 1) / bm)); }
-
-// Token tile and K split, chosen together from a small time model fitted to r3's sweeps (profiles/r03_fused_int4_gemm.md; us):
-//   t = 5.8 + rounds * groups_per_workgroup * t_tile + tail,   rounds = ceil(workgroups / 256 CUs),
-//   t_tile = 0.68 (64-token tiles) / 1.2 (128-token tiles),     tail = 3.5 + 0.5 per MB of fp32 partial tiles when K is split
-//   (1.2 per MB until the partial tiles were laid out fragment-major: whole lines per write-through store instruction).
-// 128 tokens per workgroup halve the activation bytes per weight byte, but a short prefill then leaves CUs idle ((512,4096,4096) is
-// 128 tiles of 128 tokens on 256 CUs: 46.7 us against 28.5 with 64-token tiles); a split costs its tail (a 32 / 64 KiB partial tile
-// per workgroup through the fabric and back, arrival counter, one more round trip for the last workgroup), so it pays for few
-// tiles or long K only: (128,4096,4096) 27.6 / 20.0 / 16.2 / 17.9 us with 1 / 2 / 4 / 8 splits, (128,14336,4096) 83 / 48 / 34 / 34,
-// (256,4096,4096) 27.9 / 21.5 / 20.8 / 28.7, but (512,4096,4096) 29.4 / 36.1.  The scale tables of a workgroup's groups must fit the LDS next to the ring (K = 14336 with 128-token
-// tiles needs a split for that alone).
-struct Plan {
-  int bm, S;
-  float us;
-};
-inline float model_us(int tiles, int nk, int bm, int S) {
-  const int wgs = tiles * S, rounds = (wgs + 255) / 256;
-  const float tail = S > 1 ? 3.5f + 0.5f * (float)wgs * (float)(bm * 512) * 1e-6f : 0.f;
-  return 5.8f + (float)rounds * (float)nk * (bm == 64 ? 0.68f : 1.2f) + tail;
-}
-inline Plan make_plan(int64_t M, int64_t N, int G) {
-  const int fbm = env_int("QUANTO_HIP_FUSED4_BM", 0), fs = env_int("QUANTO_HIP_FUSED4_SPLIT", 0);  // experiments / tests
-  Plan best{0, 0, 0.f};
-  for (int bm = 64; bm <= 128; bm += 64) {
-    if ((fbm == 64 || fbm == 128) && bm != fbm) continue;
-    const int tiles = tiles_of(M, N, bm);
-    for (int S = 1; S <= 8; S *= 2) {
-      if (G % S) break;
-      const int nk = G / S;
-      if (fs > 0 ? (S != fs) : (S > 1 && nk < 4)) continue;
-      if (lds_bytes(nk, bm) > 160 * 1024) continue;
-      if (S > 1 && !ws_counters_fit(tiles)) continue;
-      const float us = model_us(tiles, nk, bm, S);
-      if (best.bm == 0 || us < best.us * 0.97f) best = Plan{bm, S, us};  // ties: the smaller tile, fewer splits
-    }
-  }
-  return best;  // bm == 0: no configuration fits (a forced split that does not divide the groups, tables that never fit)
-}
+// tile times of the time model (r3 sweeps, us per 64- / 128-token tile), the forcing knobs, 2-byte activations
+constexpr Unit kUnit{0.68f, 1.2f, "QUANTO_HIP_FUSED4_BM", "QUANTO_HIP_FUSED4_SPLIT", 2, W_BYTES};
 
 template <int DT, bool INT_SHIFT, int BM>
 static int launch_bm(const Args& a, hipStream_t stream) {
-  const int lds = lds_bytes(a.G / a.S, BM);
+  const int lds = lds_bytes(kUnit, a.G / a.S, BM);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbits_mfma_fused_kernel<DT, INT_SHIFT, BM>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   const dim3 grid((unsigned)((a.N / 2 + PR - 1) / PR), (unsigned)((a.M + BM - 1) / BM), (unsigned)a.S);
   hipLaunchKernelGGL((qbits_mfma_fused_kernel<DT, INT_SHIFT, BM>), grid, dim3(WAVES * 64), lds, stream, a);
@@ -462,39 +327,31 @@ bool qbits_mfma_fused_supported(int64_t M, const PackedGeom& g, int dtype) {
   if (!(g.bits == 4 && g.C == 128 && (g.N % 8 == 0) && (g.K % 128 == 0) && M >= 1 && (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) &&
         g.N < (1 << 30) && g.K < (1 << 30) && M * g.K < (1ll << 31) && g.N * g.K < (1ll << 33) && grid_yz_fits(M, 64)))  // grid.y: 64-token tiles
     return false;
-  return fused4::make_plan(M, g.N, (int)g.G).bm != 0;
+  return gf::make_plan(fused4::kUnit, M, g.N, (int)g.G).bm != 0;
 }
 
 // modelled time of the configuration make_plan picks, in units of "one round of 128-token tiles at this K" (46 us at K = 4096): what
 // c_api.hip compares with the dequantize + dense GEMM path (flat in M up to ~1 k rows)
 float qbits_mfma_fused_cost(int64_t M, const PackedGeom& g) {
-  const fused4::Plan p = fused4::make_plan(M, g.N, (int)g.G);
+  const gf::Plan p = gf::make_plan(fused4::kUnit, M, g.N, (int)g.G);
   return p.bm == 0 ? 1e9f : p.us / (46.f * (float)g.K / 4096.f);
 }
 
 // true when the problem cannot run without the split-K scratch (no unsplit configuration fits the LDS: the scale tables of K = 14336)
 bool qbits_mfma_fused_needs_workspace(const PackedGeom& g) {
-  return fused4::lds_bytes((int)g.G, 128) > 160 * 1024 && fused4::lds_bytes((int)g.G, 64) > 160 * 1024;
+  return gf::lds_bytes(fused4::kUnit, (int)g.G, 128) > kMaxLdsBytes && gf::lds_bytes(fused4::kUnit, (int)g.G, 64) > kMaxLdsBytes;
 }
 
-// [counters (zero on entry, zero on exit) | fp32 partial tiles]; 0 when K is not split (the group sums of x come from the matrix pipe)
 size_t qbits_mfma_fused_workspace(int64_t M, const PackedGeom& g) {
-  const fused4::Plan p = fused4::make_plan(M, g.N, (int)g.G);
-  if (p.bm == 0 || p.S == 1) return 0;
-  return QUANTO_HIP_WS_COUNTER_BYTES + (size_t)fused4::tiles_of(M, g.N, p.bm) * p.S * (fused4::WAVES * 64) * ((p.bm / 16) * 16);
+  return gf::workspace_bytes(gf::make_plan(fused4::kUnit, M, g.N, (int)g.G), M, g.N);
 }
 
 int qbits_mm_mfma_fused(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
                         const PackedGeom& g, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!qbits_mfma_fused_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
-  fused4::Plan p = fused4::make_plan(M, g.N, (int)g.G);
-  if (p.S > 1 && !ws_holds(workspace, workspace_bytes, qbits_mfma_fused_workspace(M, g))) {
-    // no scratch: unsplit, with whichever token tile lets the whole scale table fit
-    p.S = 1;
-    if (fused4::lds_bytes((int)g.G, p.bm) > 160 * 1024) p.bm = 64;
-    if (fused4::lds_bytes((int)g.G, p.bm) > 160 * 1024) return QUANTO_HIP_EINVAL;
-  }
+  gf::Plan p = gf::make_plan(fused4::kUnit, M, g.N, (int)g.G);
+  if (!gf::settle_for_workspace(fused4::kUnit, p, M, g.N, (int)g.G, workspace, workspace_bytes)) return QUANTO_HIP_EINVAL;
   const int bm = p.bm, S = p.S;
   fused4::Args a{x, packed, scale, shift, bias, y, (int)M, (int)g.N, (int)g.K, (int)g.G, S, reinterpret_cast<int*>(workspace),
                  S > 1 ? ws_partials(workspace) : nullptr,

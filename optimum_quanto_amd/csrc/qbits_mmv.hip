@@ -287,7 +287,7 @@ static int launch_shape(const Args& a, hipStream_t stream) {
 bool qbits_mmv_supported(int64_t M, const PackedGeom& g, int dtype) {
   return g.bits == 4 && g.C == 128 && g.N % 16 == 0 && g.K % 128 == 0 && M >= 1 && M <= 32 &&
          (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && (g.N / 2) * g.K < (int64_t)1 << 31 && 32 * g.K * 2 < (int64_t)1 << 31 &&
-         mmv::lds_bytes(2, 2, (int)g.G) <= 160 * 1024;
+         mmv::lds_bytes(2, 2, (int)g.G) <= kMaxLdsBytes;
 }
 
 int qbits_mm_mmv(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,

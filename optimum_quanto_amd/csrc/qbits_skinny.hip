@@ -27,8 +27,6 @@ namespace skinny {
 
 constexpr int BK = 128;  // byte-columns (= k) per tile = one group
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 struct Args {
   const void* x;        // [M, K]
   const uint8_t* w;     // packed [N/2, K]
@@ -597,14 +595,14 @@ bool qbits_skinny_supported(int64_t M, const PackedGeom& g, int dtype) {
   if (g.bits == 4 && g.C == 96 && !per_channel)  // group size 96 (r4): tiles of 96 k, 64-feature blocks
     return g.N % 64 == 0 && g.K % 96 == 0 && g.K >= 192 && M >= 1 && M <= QUANTO_HIP_SKINNY_MAX_M &&
            (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && g.N < (1 << 30) && g.K < (1 << 30) &&
-           skinny::lds_bytes(tf, 4, (int)g.G, 4) <= 160 * 1024;
+           skinny::lds_bytes(tf, 4, (int)g.G, 4) <= kMaxLdsBytes;
   if (g.bits == 2)  // qint2 (r4): group size 128, 64-feature blocks (16 packed rows x 4 planes)
     return g.C == 128 && g.N % 64 == 0 && g.K % 128 == 0 && M >= 1 && M <= QUANTO_HIP_SKINNY_MAX_M &&
            (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && g.N < (1 << 30) && g.K < (1 << 30) &&
-           skinny::lds_bytes(tf, 4, (int)g.G, 4, 4) <= 160 * 1024;
+           skinny::lds_bytes(tf, 4, (int)g.G, 4, 4) <= kMaxLdsBytes;
   return g.bits == 4 && (grouped || per_channel) && (g.N % 16 == 0) && (g.K % 128 == 0) && M >= 1 && M <= QUANTO_HIP_SKINNY_MAX_M &&
          (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && g.N < (1 << 30) && g.K < (1 << 30) &&
-         skinny::lds_bytes(tf, 4, groups, skinny::pick_waves((int)g.N)) <= 160 * 1024;
+         skinny::lds_bytes(tf, 4, groups, skinny::pick_waves((int)g.N)) <= kMaxLdsBytes;
 }
 
 // [counters (zero on entry, zero on exit) | fp32 partial sums]; 0 when the problem is not split

@@ -21,8 +21,6 @@ namespace skinny8 {
 
 constexpr int BK = 128;  // k per tile = bytes per weight row and tile
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 using namespace w8;  // qh_mfma.h: W_I8 .. W_F8E4M3FNUZ, convert_pair
 
 struct Args {

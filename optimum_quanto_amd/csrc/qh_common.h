@@ -16,6 +16,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 constexpr int kWave = 64;
+constexpr int kMaxLdsBytes = 160 * 1024;  // LDS of a CU: the most dynamic shared memory a workgroup can ask for
 
 // qbits GEMV load policy used when QUANTO_HIP_GEMV_VARIANT is unset (see qbits_gemv.hip): bit 0 = x / scale loads first,
 // bit 1 = non-temporal weight loads.  Measured (r2, hipGraph replay, us per launch, variant 0 / 1 / 2 / 3): (1,4096,4096) 4.54 /

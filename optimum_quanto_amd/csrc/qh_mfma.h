@@ -45,6 +45,7 @@ __device__ __forceinline__ uint32_t pack_exact(float a, float b) {
 #ifndef QH_GLDS_POLICY
 #define QH_GLDS_POLICY ""  // cache policy bits of the operand DMA (probes: " sc1", " nt", " sc0 sc1": profiles/r06_glds_cache_policy_ab.jsonl)
 #endif
+typedef __attribute__((address_space(3))) void* lds_ptr_t;  // (uint32_t)(uintptr_t)(lds_ptr_t)smem: the LDS byte address glds16 takes
 // wave-uniform 64-bit base in SGPRs + per-lane 32-bit byte offset
 __device__ __forceinline__ void glds16(const void* sbase, uint32_t voff, uint32_t lds_dst) {
   asm volatile(

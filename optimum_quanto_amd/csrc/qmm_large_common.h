@@ -13,7 +13,7 @@ namespace lt {
 constexpr int BK = 64;
 constexpr int STAGES = 3;
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
+using qh::lds_ptr_t;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
 using namespace w8;  // qh_mfma.h: W_I8 .. W_F8E4M3FNUZ, W_DENSE, convert_pair

@@ -252,6 +252,24 @@ def test_qbits_mfma_fused4_split_k(dt, split, M, N, K, zp, bm, monkeypatch):
     np.testing.assert_array_equal(_run_qbits(p, "mfma_fused4", bias), O.round_to((y0 + bias).astype(np.float32), dt))
 
 
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+@pytest.mark.parametrize("zp", [False, True])
+@pytest.mark.parametrize("bm", [64, 128])
+def test_qbits_mfma_fused4_split_k_three_tiles_per_split(dt, zp, bm, monkeypatch):
+    """An odd tile count above 1 behind a split: 6 groups over 2 workgroups = 3 tiles each, so the two-stage loop (csrc/qh_group_fused.h) runs its
+    pair once AND its odd tail, the last group accumulator is set B, and the second split starts at an odd group; ragged M / N, both token
+    tiles.  The workspace size shows that both knobs took effect; exact-math gate; a second call on the same workspace gives the same bits."""
+    M, N, K = 130, 136, 768
+    monkeypatch.setenv("QUANTO_HIP_FUSED4_SPLIT", "2")
+    monkeypatch.setenv("QUANTO_HIP_FUSED4_BM", str(bm))
+    ws = quanto_hip.cdll.quanto_hip_qbits_mm_workspace_size(M, N, K, 4, 128, DT_CODE[dt], 8)  # QUANTO_HIP_KERNEL_MFMA_FUSED4
+    assert ws == 4096 + 2 * -(-M // bm) * 2 * 512 * bm  # counters + (2 feature blocks x token tiles) x 2 splits x 512 lanes x bm / 16 float4
+    p = make_qbits_problem(M, N, K, dt, zeropoint=zp, seed=M + N + bm)
+    y0 = _run_qbits(p, "mfma_fused4")
+    assert_close_to_exact(y0, _exact_qbits(p), dt, f"mfma_fused4 split 2, 3 tiles per split, bm {bm}")
+    np.testing.assert_array_equal(_run_qbits(p, "mfma_fused4"), y0)
+
+
 # Forced K splits of the streaming and large-tile kernels (their automatic rules pick powers of two): 3, 5 and 6 are not multiples of the splits
 # the split-K tail loads per wait (qbits_skinny: four), so its last batch re-loads the last split and drops it.  The workspace size shows that the
 # knob took effect; a second call on the same workspace gives the same bits (the arrival counters were left zero); bias bit for bit against the

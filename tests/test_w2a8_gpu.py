@@ -89,6 +89,22 @@ def test_w2a8_split_k_exact_math_and_deterministic(monkeypatch, act, split, M, N
     np.testing.assert_array_equal(_run(p, ta, sx, "bf16", 2), y)
 
 
+def test_w2a8_split_k_three_tiles_per_split(monkeypatch):
+    """int2 weights, an odd tile count above 1 behind a split, 64-token tiles forced: 6 groups over 2 workgroups = 3 tiles each (the two-stage loop of
+    csrc/qh_group_fused.h runs its pair once and its odd tail); ragged M, N = 144 (the second feature block holds 16 of its 128 features); int8 activations."""
+    M, N, K = 130, 144, 768
+    monkeypatch.setenv("QUANTO_HIP_A8_SPLIT", "2")
+    monkeypatch.setenv("QUANTO_HIP_A8_BM", "64")
+    p = make_qbits_problem(2, N, K, "bf16", bits=2, seed=N + K)
+    a, sx = _act_int8(M, K, seed=M)
+    ta = torch.from_numpy(a).to(DEV)
+    assert quanto_hip.lib.qbits_mm_a8_workspace(M, N, K, 2, 128, ta.dtype, torch.bfloat16) == 4096 + 2 * 3 * 2 * 512 * 64  # the knobs took effect
+    y = _run(p, ta, sx, "bf16", 2)
+    assert quanto_hip.lib.last_kernel() == "a8_fused_int8_w2"
+    assert_close_to_exact(y, O.qbits_mm_a8_exact(a, sx, p["packed"], 2, p["scale"], p["shift"], 128, N, K), "bf16", "w2a8 int8 split 2, 3 tiles, bm 64")
+    np.testing.assert_array_equal(_run(p, ta, sx, "bf16", 2), y)
+
+
 @pytest.mark.parametrize("bits,kind", [(2, "e4m3fn"), (2, "e5m2"), (4, "e5m2")])
 @pytest.mark.parametrize("bm", ["64", "128"])
 @pytest.mark.parametrize("dt", ["bf16", "fp16"])

@@ -66,6 +66,54 @@ def test_w4a8_int8_split_k_exact_math_and_deterministic(monkeypatch, split, M, N
         np.testing.assert_array_equal(_run(p, ta, sx, "bf16"), y)
 
 
+def _split_workspace(M, N, K, bits, act, bm, split):
+    """What the forced token tile and split must make of the scratch: counters + tiles x splits x 512 lanes x bm / 16 float4."""
+    ws = quanto_hip.lib.qbits_mm_a8_workspace(M, N, K, bits, 128, act, torch.bfloat16)
+    assert ws == 4096 + -(-N // 128) * -(-M // bm) * split * 512 * bm
+    return ws
+
+
+@pytest.mark.parametrize("bm", [64, 128])
+@pytest.mark.parametrize("act", ["int8", "e4m3fn"])
+def test_w4a8_split_k_three_tiles_per_split(monkeypatch, bm, act):
+    """An odd tile count above 1 behind a split, with the token tile forced: 6 groups over 2 workgroups = 3 tiles each, so the two-stage loop
+    (csrc/qh_group_fused.h) runs its pair once AND its odd tail, the last group accumulator is set B, and the second split starts at an odd group; ragged
+    M and N.  Exact-math gate; int8 activations: three more runs give the same bits."""
+    M, N, K = 130, 136, 768
+    monkeypatch.setenv("QUANTO_HIP_A8_SPLIT", "2")
+    monkeypatch.setenv("QUANTO_HIP_A8_BM", str(bm))
+    p = make_qbits_problem(2, N, K, "bf16", seed=N + K + bm)
+    if act == "int8":
+        a, sx = _act_int8(M, K, seed=M)
+        ta, av = torch.from_numpy(a).to(DEV), a
+    else:
+        codes = O.fp8_encode((np.random.default_rng(M + K).standard_normal((M, K)) * 40).astype(np.float32), "e4m3fn")
+        sx = O.round_to(np.array([0.021], np.float32), "bf16")
+        ta, av = fp8_tensor(codes, "e4m3fn", DEV), O.fp8_decode(codes, "e4m3fn")
+    _split_workspace(M, N, K, 4, ta.dtype, bm, 2)
+    y = _run(p, ta, sx, "bf16")
+    assert quanto_hip.lib.last_kernel() == ("a8_fused_int8" if act == "int8" else "a8_fused_fp8")
+    assert_close_to_exact(y, O.qbits_mm_a8_exact(av, sx, p["packed"], 4, p["scale"], p["shift"], 128, N, K), "bf16", f"w4a8 {act} split 2, 3 tiles, bm {bm}")
+    if act == "int8":
+        for _ in range(3):
+            np.testing.assert_array_equal(_run(p, ta, sx, "bf16"), y)
+
+
+@pytest.mark.parametrize("bm", [64, 128])
+def test_w4a8_split_k_one_tile_per_split(monkeypatch, bm):
+    """One tile per split (2 groups over 2 workgroups): neither the pair loop nor the odd tail runs, the first tile's set A is folded; int8 activations."""
+    M, N, K = 65, 128, 256
+    monkeypatch.setenv("QUANTO_HIP_A8_SPLIT", "2")
+    monkeypatch.setenv("QUANTO_HIP_A8_BM", str(bm))
+    p = make_qbits_problem(2, N, K, "bf16", seed=N + K + bm)
+    a, sx = _act_int8(M, K, seed=M)
+    ta = torch.from_numpy(a).to(DEV)
+    _split_workspace(M, N, K, 4, ta.dtype, bm, 2)
+    y = _run(p, ta, sx, "bf16")
+    assert_close_to_exact(y, O.qbits_mm_a8_exact(a, sx, p["packed"], 4, p["scale"], p["shift"], 128, N, K), "bf16", f"w4a8 int8 split 2, 1 tile, bm {bm}")
+    np.testing.assert_array_equal(_run(p, ta, sx, "bf16"), y)
+
+
 @pytest.mark.parametrize("bm", ["64", "128"])
 @pytest.mark.parametrize("dt", ["bf16", "fp16"])
 @pytest.mark.parametrize("zp", [False, True])
