@@ -328,6 +328,23 @@ int quanto_hip_qbits_mm_a8(const void* a, const void* a_scale, const uint8_t* pa
 int64_t quanto_hip_qbits_mm_a8_workspace_size(int64_t M, int64_t N, int64_t K, int bits, int group_size, int a_dtype, int dtype);
 
 /*
+ * quanto::qbits_mm_a8_q(Tensor input, Tensor input_scale, Tensor packed, Tensor scale, Tensor shift, Tensor? bias, Tensor out_scale, int bits,
+ *                       int? group_size, int out_features, int in_features) -> Tensor
+ *   replaces, for a W4A8 / W2A8 layer, the product AND the re-quantization of its output (nn/qmodule.py:281-299 -> library/quantize.py:26-55):
+ *   yq = quantize_symmetric(qbits_mm_a8(a, ...) (+ bias), a_dtype, per-tensor, out_scale) in ONE launch, the [M, N] tensor of `dtype` never written.
+ *   Bit-identical to quanto_hip_qbits_mm_a8 followed by quanto_hip_quantize_symmetric.
+ * a / a_scale / packed / scale / shift / bias as for quanto_hip_qbits_mm_a8; out_scale: dtype[1] (device); yq: a_dtype[M, N] codes.
+ * a, packed and yq 16-byte aligned (QUANTO_HIP_EALIGN otherwise).
+ * Served: exactly what quanto_hip_qbits_mm_a8 serves.  Everything else returns QUANTO_HIP_ENOTSUP - ahead of any look at the data pointers - and writes
+ * nothing: the caller runs the two entries.  workspace: the split-K scratch of quanto_hip_qbits_mm_a8, same contract, same
+ * quanto_hip_qbits_mm_a8_workspace_size bytes (the plan does not look at the output).  M == 0 returns QUANTO_HIP_OK.
+ * quanto_hip_last_kernel() reports the unfused route's name plus "_q" ("a8_fused_int8_q", "a8_fused_fp8_w2_q", ...) after a successful launch.
+ */
+int quanto_hip_qbits_mm_a8_q(const void* a, const void* a_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
+                             const void* out_scale, void* yq, int64_t M, int64_t N, int64_t K, int bits, int group_size, int a_dtype, int dtype,
+                             int shift_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * F.conv2d with an int8 / fp8 weight - what QConv2d.forward (nn/qconv2d.py:54-55) reaches through WeightQBytesTensor's dispatch, where the
  * reference dequantizes the whole weight per call (qfallback) and runs a float convolution.  Dense convolution (groups = 1) as an IMPLICIT
  * GEMM: y[b, n, oh, ow] = scale[n] * sum_{c,i,j} x[b, c, oh*sh - ph + i*dh, ow*sw - pw + j*dw] * w[n, c, i, j] (+ bias[n]); the im2col operand

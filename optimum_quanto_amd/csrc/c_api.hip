@@ -101,6 +101,8 @@ int qbytes_mm_f32(const void*, const void*, const void*, const void*, void*, int
 // quantized activations x int4 / int2 weights (qbits_a8_fused.hip)
 bool qbits_a8_supported(int64_t, const PackedGeom&, int, int);
 size_t qbits_a8_workspace(int64_t, const PackedGeom&);
+int qbits_mm_a8_q(const void*, const void*, const uint8_t*, const void*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, int, bool,
+                  void*, size_t, hipStream_t);
 int qbits_mm_a8(const void*, const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, int, bool, void*, size_t,
                 hipStream_t);
 
@@ -430,6 +432,28 @@ int quanto_hip_qbits_mm_a8(const void* a, const void* a_scale, const uint8_t* pa
                             reinterpret_cast<hipStream_t>(stream));
   if (r == QUANTO_HIP_OK) {
     static const char* const names[2][3] = {{"a8_fused_int8", "a8_fused_fp8", "a8_fused_bf8"}, {"a8_fused_int8_w2", "a8_fused_fp8_w2", "a8_fused_bf8_w2"}};
+    set_last_kernel(names[bits == 2][a_dtype == QUANTO_HIP_I8 ? 0 : a_dtype == QUANTO_HIP_F8_E4M3FN ? 1 : 2]);
+  }
+  return r;
+}
+
+// ---- qbits_mm_a8 with the layer's output quantization in the epilogue: the checks of the entry above, every reason not to serve -> ENOTSUP ahead of
+// any look at the data pointers; the plan and the workspace are those of the unfused entry (quanto_hip_qbits_mm_a8_workspace_size) ----
+int quanto_hip_qbits_mm_a8_q(const void* a, const void* a_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
+                             const void* out_scale, void* yq, int64_t M, int64_t N, int64_t K, int bits, int group_size, int a_dtype, int dtype,
+                             int shift_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  bool int_shift = false;
+  const int st = check_qbits(M, N, K, bits, group_size, dtype, shift_dtype, &int_shift);
+  if (st != QUANTO_HIP_OK) return st;
+  const PackedGeom g = make_geom(N, K, bits, group_size);
+  if (!qbits_a8_supported(M > 0 ? M : 1, g, a_dtype, dtype)) return QUANTO_HIP_ENOTSUP;
+  if (M == 0) return QUANTO_HIP_OK;
+  if (!a || !a_scale || !packed || !scale || !shift || !out_scale || !yq) return QUANTO_HIP_EINVAL;
+  const int r = qbits_mm_a8_q(a, a_scale, packed, scale, shift, bias, out_scale, yq, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes,
+                              reinterpret_cast<hipStream_t>(stream));
+  if (r == QUANTO_HIP_OK) {
+    static const char* const names[2][3] = {{"a8_fused_int8_q", "a8_fused_fp8_q", "a8_fused_bf8_q"},
+                                            {"a8_fused_int8_w2_q", "a8_fused_fp8_w2_q", "a8_fused_bf8_w2_q"}};
     set_last_kernel(names[bits == 2][a_dtype == QUANTO_HIP_I8 ? 0 : a_dtype == QUANTO_HIP_F8_E4M3FN ? 1 : 2]);
   }
   return r;

@@ -25,7 +25,8 @@
 // 4 planes; the operand is ((raw >> 2 plane) & 0x03030303) for int8 and ONE v_perm into the codes 0, 1, 2, 3 of the e4m3 table for fp8.  Codes 0..3 are exact
 // e4m3 values, so nothing else changes.  e5m2 activations (r7): the MX-format instruction takes its A and B formats independently - the weight operand (A)
 // stays e4m3, the activation operand (B) is read as bf8 (blgp = 1) in the product and in the all-ones group sum; an e5m2 value times an integer below 16 is
-// exact in fp32, as for e4m3.  Instantiated: {bf16, fp16} x {int8, e4m3, e5m2} x {float shift, zero-point} x {64, 128 tokens} x {int4, int2}.
+// exact in fp32, as for e4m3.  Instantiated: {bf16, fp16} x {int8, e4m3, e5m2} x {float shift, zero-point} x {64, 128 tokens} x {int4, int2}, each
+// storing y or (QOUT) the codes of y at the layer's output scale.
 #include "qh_group_fused.h"
 
 namespace qh {
@@ -66,6 +67,7 @@ struct Args {
   int* counters;         // [tiles] arrival counters, zero on entry and on exit (S > 1)
   float* partials;       // [tiles][S][MI][512 lanes] float4
   int ablate;            // QUANTO_HIP_A8_ABLATE (timing experiments, WRONG results): 1 no fold, 2 no matrix steps, 4 the DMA re-reads tile 0, 8 no weight unpack
+  const void* out_scale; // QOUT kernels only: one element of the output dtype, the per-tensor scale of the codes they store into `y` ([M, N] bytes)
 };
 
 template <int AK>
@@ -77,7 +79,8 @@ struct Acc<A_I8> {
   using V = i32x4;
 };
 
-template <int DT, int AK, bool INT_SHIFT, int BM, int BITS>
+// QOUT: the quantized-output form (`y` holds codes of the activation's own type, gf::epilogue_codes); the existing instantiations compile the epilogue they had
+template <int DT, int AK, bool INT_SHIFT, int BM, int BITS, bool QOUT = false>
 __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Args a) {
   using E = Elem<DT>;
   using T = typename E::T;
@@ -267,40 +270,47 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
   QH_GF_FOR_EACH_TILE(nk, tile, final_fold, accgA, accgB);
   if (S > 1) QH_GF_SPLITK(BM, MI, acc, a.partials, a.counters, S, sp, tid, smem);
   // x activation scale (the product is rounded to fp32 before anything else happens to it), (+ bias)
-  QH_GF_EPILOGUE(E, MI, acc, a.y, a.bias, m0, fi, N, P, p0 + wave * RW + froff, fplane, m < M, v = v * sx; asm volatile("" : "+v"(v)));
+  if constexpr (QOUT) {
+    // ... and what quantize_symmetric makes of that element at the layer's output scale: the split-K tile's last arriver gets here with the summed accumulators
+    constexpr int ODT = AK == A_I8 ? QUANTO_HIP_I8 : AK == A_F8E4M3 ? QUANTO_HIP_F8_E4M3FN : QUANTO_HIP_F8_E5M2;
+    const float os = E::to_f32(*reinterpret_cast<const T*>(a.out_scale));
+    epilogue_codes<DT, ODT, MI>(acc, a.y, a.bias, sx, os, M, m0, fi, N, P, p0 + wave * RW + froff, fplane);
+  } else {
+    QH_GF_EPILOGUE(E, MI, acc, a.y, a.bias, m0, fi, N, P, p0 + wave * RW + froff, fplane, m < M, v = v * sx; asm volatile("" : "+v"(v)));
+  }
 }
 
 // tile times of the time model (r6 sweep, us per 64- / 128-token tile), the forcing knobs, 1-byte activations, the weight tile of either width
 inline Unit unit(int bits) { return Unit{0.45f, 0.75f, "QUANTO_HIP_A8_BM", "QUANTO_HIP_A8_SPLIT", 1, bits == 2 ? WGeo<2>::W_BYTES : WGeo<4>::W_BYTES}; }
 
-template <int DT, int AK, bool INT_SHIFT, int BM, int BITS>
+template <int DT, int AK, bool INT_SHIFT, int BM, int BITS, bool QOUT>
 static int launch_bm(const Args& a, hipStream_t stream) {
   const int lds = lds_bytes(unit(BITS), a.G / a.S, BM);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbits_a8_fused_kernel<DT, AK, INT_SHIFT, BM, BITS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbits_a8_fused_kernel<DT, AK, INT_SHIFT, BM, BITS, QOUT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             lds);
   const dim3 grid((unsigned)((a.N + NF - 1) / NF), (unsigned)((a.M + BM - 1) / BM), (unsigned)a.S);
-  hipLaunchKernelGGL((qbits_a8_fused_kernel<DT, AK, INT_SHIFT, BM, BITS>), grid, dim3(WAVES * 64), lds, stream, a);
+  hipLaunchKernelGGL((qbits_a8_fused_kernel<DT, AK, INT_SHIFT, BM, BITS, QOUT>), grid, dim3(WAVES * 64), lds, stream, a);
   return launch_status();
 }
-template <int DT, int AK, int BITS>
+template <int DT, int AK, int BITS, bool QOUT>
 static int launch(const Args& a, int bm, bool int_shift, hipStream_t stream) {
-  if (int_shift) return bm == 64 ? launch_bm<DT, AK, true, 64, BITS>(a, stream) : launch_bm<DT, AK, true, 128, BITS>(a, stream);
-  return bm == 64 ? launch_bm<DT, AK, false, 64, BITS>(a, stream) : launch_bm<DT, AK, false, 128, BITS>(a, stream);
+  if (int_shift) return bm == 64 ? launch_bm<DT, AK, true, 64, BITS, QOUT>(a, stream) : launch_bm<DT, AK, true, 128, BITS, QOUT>(a, stream);
+  return bm == 64 ? launch_bm<DT, AK, false, 64, BITS, QOUT>(a, stream) : launch_bm<DT, AK, false, 128, BITS, QOUT>(a, stream);
 }
-template <int DT, int BITS>
+template <int DT, int BITS, bool QOUT>
 static int launch_act(const Args& a, int a_dtype, int bm, bool int_shift, hipStream_t stream) {
   switch (a_dtype) {
     case QUANTO_HIP_I8:
-      return launch<DT, A_I8, BITS>(a, bm, int_shift, stream);
+      return launch<DT, A_I8, BITS, QOUT>(a, bm, int_shift, stream);
     case QUANTO_HIP_F8_E4M3FN:
-      return launch<DT, A_F8E4M3, BITS>(a, bm, int_shift, stream);
+      return launch<DT, A_F8E4M3, BITS, QOUT>(a, bm, int_shift, stream);
     default:
-      return launch<DT, A_F8E5M2, BITS>(a, bm, int_shift, stream);
+      return launch<DT, A_F8E5M2, BITS, QOUT>(a, bm, int_shift, stream);
   }
 }
-template <int DT>
+template <int DT, bool QOUT>
 static int launch_bits(const Args& a, int bits, int a_dtype, int bm, bool int_shift, hipStream_t stream) {
-  return bits == 2 ? launch_act<DT, 2>(a, a_dtype, bm, int_shift, stream) : launch_act<DT, 4>(a, a_dtype, bm, int_shift, stream);
+  return bits == 2 ? launch_act<DT, 2, QOUT>(a, a_dtype, bm, int_shift, stream) : launch_act<DT, 4, QOUT>(a, a_dtype, bm, int_shift, stream);
 }
 
 }  // namespace a8
@@ -320,19 +330,36 @@ size_t qbits_a8_workspace(int64_t M, const PackedGeom& g) {
   return gf::workspace_bytes(gf::make_plan(a8::unit(g.bits), M, g.N, (int)g.G), M, g.N);
 }
 
-int qbits_mm_a8(const void* act, const void* act_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// out_scale == nullptr: y = dtype[M, N]; otherwise the code-storing kernels: y = a_dtype[M, N] codes at the per-tensor scale out_scale[0], 16-byte aligned
+template <bool QOUT>
+static int mm_a8(const void* act, const void* act_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
+                 const void* out_scale, void* y, int64_t M, const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace,
+                 size_t workspace_bytes, hipStream_t stream) {
   if (!qbits_a8_supported(M, g, a_dtype, dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
+  if ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(packed) | (QOUT ? reinterpret_cast<uintptr_t>(y) : 0)) % 16) return QUANTO_HIP_EALIGN;
   const gf::Unit unit = a8::unit(g.bits);
   gf::Plan p = gf::make_plan(unit, M, g.N, (int)g.G);
   if (!gf::settle_for_workspace(unit, p, M, g.N, (int)g.G, workspace, workspace_bytes)) return QUANTO_HIP_EINVAL;
   const a8::Args a{reinterpret_cast<const uint8_t*>(act), act_scale, packed, scale, shift, bias, y, (int)M, (int)g.N, (int)g.K, (int)g.G, p.S,
                    reinterpret_cast<int*>(workspace),
                    p.S > 1 ? ws_partials(workspace) : nullptr,
-                   env_int("QUANTO_HIP_A8_ABLATE", 0)};
-  return dtype == QUANTO_HIP_BF16 ? a8::launch_bits<QUANTO_HIP_BF16>(a, g.bits, a_dtype, p.bm, int_shift, stream)
-                                  : a8::launch_bits<QUANTO_HIP_F16>(a, g.bits, a_dtype, p.bm, int_shift, stream);
+                   env_int("QUANTO_HIP_A8_ABLATE", 0),
+                   out_scale};
+  return dtype == QUANTO_HIP_BF16 ? a8::launch_bits<QUANTO_HIP_BF16, QOUT>(a, g.bits, a_dtype, p.bm, int_shift, stream)
+                                  : a8::launch_bits<QUANTO_HIP_F16, QOUT>(a, g.bits, a_dtype, p.bm, int_shift, stream);
+}
+
+int qbits_mm_a8(const void* act, const void* act_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
+                const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return mm_a8<false>(act, act_scale, packed, scale, shift, bias, nullptr, y, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes, stream);
+}
+
+// The same product with the output quantization of the layer in its epilogue (gf::epilogue_codes): yq[M, N] = codes in a_dtype of the dtype-rounded
+// product at the per-tensor scale out_scale[0] - bit-identical to quantize_symmetric(qbits_mm_a8(...)).  Same gate, same plan, same workspace.
+int qbits_mm_a8_q(const void* act, const void* act_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
+                  const void* out_scale, void* yq, int64_t M, const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace,
+                  size_t workspace_bytes, hipStream_t stream) {
+  return mm_a8<true>(act, act_scale, packed, scale, shift, bias, out_scale, yq, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes, stream);
 }
 
 }  // namespace qh

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "qh_mfma.h"
+#include "qh_quantize.h"
 
 namespace qh {
 namespace gf {
@@ -156,6 +157,50 @@ __device__ __forceinline__ void fold_slice(f32x4 (&acc)[MI], const GV (&pg)[MI],
       }                                                                                                                     \
     }                                                                                                                       \
   }
+
+// ---- the same epilogue storing OUTPUT CODES (quantized-activation kernel, QOUT): what quanto::quantize_symmetric(y, activation dtype, None, out_scale)
+// makes of the element the epilogue above stores.  Per element the two kernels back to back: t as above - the accumulator times the activation scale sx
+// (rounded to fp32 in front of anything else), rounded to T, the bias added, rounded again - then the rule of qh_quantize.h on t: T(fp32(t) / fp32(os))
+// with a correctly rounded divide, clamp_target, pack4.  A lane's 4 consecutive features of a token are one dword of codes: P % 4 == 0 (the launcher's
+// N % 8 / N % 16) and pl % 4 == 0 make (m * N + n0) a multiple of 4, the launcher checks the base; per byte on the ragged edge; rows m >= M are not stored.
+template <int DT, int ODT, int MI>
+__device__ __forceinline__ void epilogue_codes(const f32x4 (&acc)[MI], void* yq, const void* bias, float sx, float os, int M, int m0, int fi, int N,
+                                               int P, int pl, int plane) {
+  using E = Elem<DT>;
+  using T = typename E::T;
+  uint8_t* const y = reinterpret_cast<uint8_t*>(yq);
+  const bool has_bias = bias != nullptr;
+  const int n0 = pl + plane * P;  // 4 consecutive output features n0 .. n0 + 3
+  float bv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (has_bias) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bv[r] = pl + r < P ? E::to_f32(reinterpret_cast<const T*>(bias)[n0 + r]) : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int m = m0 + i * 16 + fi;
+    if (m < M) {
+      float q[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = acc[i][r];
+        v = v * sx;
+        asm volatile("" : "+v"(v));
+        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[r];
+        const T t = E::from_f32(v);  // the element QH_GF_EPILOGUE stores
+        q[r] = clamp_target<ODT>(quotient_in<DT>(E::to_f32(t), os));
+      }
+      const uint32_t codes = pack4<ODT>(q);
+      if (pl + 3 < P) {
+        *reinterpret_cast<uint32_t*>(y + (size_t)m * N + n0) = codes;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (pl + r < P) y[(size_t)m * N + n0 + r] = (uint8_t)(codes >> (8 * r));
+      }
+    }
+  }
+}
 
 // ---- the weight tile in LDS: 128-byte rows (one packed row x 128 k), 16-byte chunk c of row r at position c ^ (r & 7) --------------------------
 // DMA source of weight piece `piece` (8 packed rows = 1 KiB, one per wave): lane -> row lane >> 3, position lane & 7 holds chunk pos ^ (row & 7);

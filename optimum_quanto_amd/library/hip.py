@@ -116,6 +116,7 @@ _PROTOTYPES = {
     "quanto_hip_qbits_mm_pick": (_ci, [_i64] * 3 + [_ci] * 3),
     "quanto_hip_qbits_mm_a8": (_ci, [_vp] * 7 + [_i64] * 3 + [_ci] * 5 + [_vp, _sz, _vp]),
     "quanto_hip_qbits_mm_a8_workspace_size": (_i64, [_i64] * 3 + [_ci] * 4),
+    "quanto_hip_qbits_mm_a8_q": (_ci, [_vp] * 8 + [_i64] * 3 + [_ci] * 5 + [_vp, _sz, _vp]),
     "quanto_hip_qbytes_mm": (_ci, [_vp] * 5 + [_i64] * 3 + [_ci] * 4 + [_vp]),
     "quanto_hip_qbytes_mm_ws": (_ci, [_vp] * 5 + [_i64] * 3 + [_ci] * 4 + [_vp, _sz, _vp]),
     "quanto_hip_qbytes_mm_workspace_size": (_i64, [_i64] * 3 + [_ci] * 4),
@@ -600,6 +601,39 @@ class _Bindings:
         if st != 0:
             self._check(st, "qbits_mm_a8")
         return y if a.dim() == 2 else y.reshape(*a.shape[:-1], out_features)
+
+    # -- quanto::qbits_mm_a8_q ----------------------------------------------------------------------
+    def qbits_mm_a8_q(self, a, a_scale, packed, scale, shift, bias, out_scale, bits: int, group_size, out_features: int, in_features: int, _out=None):
+        """``quantize_symmetric(qbits_mm_a8(a, ...), a.dtype, None, out_scale)`` in one launch (csrc/qbits_a8_fused.hip, the epilogue that stores codes):
+        the same plan cache, zeroed workspace and device guard as ``qbits_mm_a8``.  Raises QuantoHipError for what the library does not serve
+        (QUANTO_HIP_ENOTSUP) or a misaligned view (QUANTO_HIP_EALIGN): ``ops.qbits_mm_a8_q_hip`` asks first and runs the two ops then.
+        ``_out`` (tests): a contiguous [M, out_features] buffer of ``a.dtype`` to store into."""
+        if not (a.is_cuda and a_scale.is_cuda and packed.is_cuda and scale.is_cuda and shift.is_cuda and out_scale.is_cuda and (bias is None or bias.is_cuda)):
+            raise QuantoHipError("quanto_hip kernels only accept tensors on a ROCm device")
+        if a.dim() == 0 or a.shape[-1] != in_features:
+            raise QuantoHipError(f"qbits_mm_a8_q: input of shape {tuple(a.shape)} does not end in in_features = {in_features}")
+        if a_scale.numel() != 1 or out_scale.numel() != 1:
+            raise QuantoHipError("qbits_mm_a8_q expects per-tensor activation and output scales")
+        sdt = scale.dtype
+        a2 = a if a.dim() == 2 and a.is_contiguous() else a.reshape(-1, in_features).contiguous()
+        a_scale = a_scale.reshape(1).to(sdt).contiguous()
+        out_scale = out_scale.reshape(1).to(sdt).contiguous()  # what quantize_symmetric does with a scale of another dtype
+        packed, scale, shift = packed.contiguous(), scale.contiguous(), shift.contiguous()
+        if bias is not None:
+            bias = bias.to(sdt).contiguous()
+        M = a2.shape[0]
+        ws_bytes = self.qbits_mm_a8_workspace(M, out_features, in_features, bits, group_size, a2.dtype, sdt)
+        if ws_bytes < 0:
+            self._check(int(ws_bytes), "qbits_mm_a8_q")
+        yq = torch.empty((M, out_features), dtype=a2.dtype, device=a.device) if _out is None else _out
+        with _DeviceGuard(a.device) as stream:
+            wp = self._zeroed_workspace(a.device, ws_bytes, stream).data_ptr() if ws_bytes > 0 else 0
+            st = self._c.quanto_hip_qbits_mm_a8_q(a2.data_ptr(), a_scale.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                                  0 if bias is None else bias.data_ptr(), out_scale.data_ptr(), yq.data_ptr(), M, out_features,
+                                                  in_features, bits, group_size or 0, _DTYPES[a2.dtype], _DTYPES[sdt], _dt(shift), wp, ws_bytes, stream)
+        if st != 0:
+            self._check(st, "qbits_mm_a8_q")
+        return yq if a.dim() == 2 else yq.reshape(*a.shape[:-1], out_features)
 
     # -- quanto::qbits_mm_multi ---------------------------------------------------------------------
     MAX_MULTI = 4  # QUANTO_HIP_MAX_MULTI

@@ -352,7 +352,8 @@ def _a8_max_tiles() -> int:
 _A8_MAX_TILES_W2_INT8 = 448
 
 
-def qbits_mm_a8_hip(input, input_scale, packed, scale, shift, bias, bits: int, group_size: Optional[int], out_features: int, in_features: int):
+def _a8_kernel_takes(input, input_scale, scale, bits: int, group_size: Optional[int], out_features: int, in_features: int) -> bool:
+    """Whether this call goes to the W4A8 / W2A8 kernel (csrc/qbits_a8_fused.hip): one predicate for ``qbits_mm_a8_hip`` and ``qbits_mm_a8_q_hip``."""
     lib = quanto_hip.lib
     m = input.numel() // in_features if in_features else 0
     # batched-decode sizes keep the weight-streaming kernels (the activation is dequantized: M x K elements, nothing next to the weight stream);
@@ -365,14 +366,46 @@ def qbits_mm_a8_hip(input, input_scale, packed, scale, shift, bias, bits: int, g
     cap = _a8_max_tiles()
     if bits == 2 and input.dtype == torch.int8:
         cap = min(cap, _A8_MAX_TILES_W2_INT8)
-    if (64 < m and tiles <= cap and input.dtype in lib.A8_DTYPES and input_scale.numel() == 1
-            and lib.qbits_mm_a8_workspace(m, out_features, in_features, bits, group_size, input.dtype, scale.dtype) >= 0):
-        return lib.qbits_mm_a8(input, input_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features)
+    return (64 < m and tiles <= cap and input.dtype in lib.A8_DTYPES and input_scale.numel() == 1
+            and lib.qbits_mm_a8_workspace(m, out_features, in_features, bits, group_size, input.dtype, scale.dtype) >= 0)
+
+
+def qbits_mm_a8_hip(input, input_scale, packed, scale, shift, bias, bits: int, group_size: Optional[int], out_features: int, in_features: int):
+    if _a8_kernel_takes(input, input_scale, scale, bits, group_size, out_features, in_features):
+        return quanto_hip.lib.qbits_mm_a8(input, input_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features)
     return qbits_mm_a8_default(input, input_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features)
 
 
 _register("qbits_mm_a8", "(Tensor input, Tensor input_scale, Tensor packed, Tensor scale, Tensor shift, Tensor? bias, int bits, int? group_size, "
           "int out_features, int in_features) -> Tensor", qbits_mm_a8_hip, default=qbits_mm_a8_default)
+
+
+def qbits_mm_a8_q_default(input, input_scale, packed, scale, shift, bias, out_scale, bits: int, group_size: Optional[int], out_features: int,
+                          in_features: int):
+    """The two-op sequence of a W4A8 / W2A8 layer (quanto::qbits_mm_a8, then nn/qmodule.py:281-299): the product in the scales' dtype, re-quantized
+    per-tensor to the activation's own 8-bit dtype."""
+    out = torch.ops.quanto.qbits_mm_a8(input, input_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features)
+    return torch.ops.quanto.quantize_symmetric(out, input.dtype, None, out_scale.to(out.dtype).reshape(()))
+
+
+def qbits_mm_a8_q_hip(input, input_scale, packed, scale, shift, bias, out_scale, bits: int, group_size: Optional[int], out_features: int,
+                      in_features: int):
+    """ROCm: the a8 kernel's epilogue stores the codes exactly when quanto::qbits_mm_a8 runs that kernel for this call (_a8_kernel_takes).  Every other
+    call - up to 64 rows, beyond the tile cap, formats the kernel does not take (QUANTO_HIP_ENOTSUP), a misaligned view of the codes - runs the two-op
+    sequence on the existing ops: the caller always gets the sequence's codes.  (A contiguous view of the codes that does not start on a 16-byte boundary is
+    copied for the sequence: the a8 kernel of quanto::qbits_mm_a8 answers QUANTO_HIP_EALIGN to it; non-contiguous views are copied by the bindings anyway.)"""
+    misaligned = input.is_contiguous() and input.data_ptr() % 16 != 0
+    if out_scale.numel() == 1 and not misaligned and _a8_kernel_takes(input, input_scale, scale, bits, group_size, out_features, in_features):
+        return quanto_hip.lib.qbits_mm_a8_q(input, input_scale, packed, scale, shift, bias, out_scale, bits, group_size, out_features, in_features)
+    if misaligned:
+        input = input.clone()
+    return qbits_mm_a8_q_default(input, input_scale, packed, scale, shift, bias, out_scale, bits, group_size, out_features, in_features)
+
+
+# new op: the product of a W4A8 / W2A8 layer with the layer's output quantization fused into the kernel epilogue - bit-identical to
+# quantize_symmetric(qbits_mm_a8(...)), one launch and no [M, N] float tensor
+_register("qbits_mm_a8_q", "(Tensor input, Tensor input_scale, Tensor packed, Tensor scale, Tensor shift, Tensor? bias, Tensor out_scale, int bits, "
+          "int? group_size, int out_features, int in_features) -> Tensor", qbits_mm_a8_q_hip, default=qbits_mm_a8_q_default)
 
 
 def qbits_conv2d_default(input, packed, scale, shift, bias, bits: int, group_size: Optional[int], weight_size, stride, padding, dilation):

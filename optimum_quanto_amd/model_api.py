@@ -5,7 +5,8 @@ from typing import Any, Dict, List, Optional, Union
 import torch
 
 from .nn import QLinear, QModuleMixin, quantize_module
-from .tensor import Optimizer, QTensor, qtype
+from .tensor import Optimizer, QTensor, WeightQBitsTensor, qint2, qint4, qtype
+from .tensor.weights import _fusable
 
 __all__ = ["quantize", "freeze", "requantize", "quantization_map", "fuse_output_quantization"]
 
@@ -158,18 +159,30 @@ def quantization_map(model: torch.nn.Module) -> Dict[str, Dict[str, str]]:
     return config
 
 
-_FUSED_OUTPUT_DTYPES = (torch.int8, torch.float8_e4m3fn, torch.float8_e5m2)  # the operand pairs quanto::qbytes_mm_q serves
+_FUSED_OUTPUT_DTYPES = (torch.int8, torch.float8_e4m3fn, torch.float8_e5m2)  # the operand pairs quanto::qbytes_mm_q serves; the activations of qbits_mm_a8_q
+
+
+def _a8_gate_admits(m: QLinear) -> bool:
+    """The weight formats the W4A8 / W2A8 kernel takes (csrc/qbits_a8_fused.hip, qbits_a8_supported): groups of 128 along in_features (per-channel with
+    128 inputs included), a whole number of them, and out_features a multiple of 4 packed rows (8 features for int4, 16 for int2)."""
+    w = m.weight
+    if not (isinstance(w, WeightQBitsTensor) and _fusable(w)):
+        return False
+    group = w._group_size if w._group_size is not None else m.in_features
+    return group == 128 and m.in_features % 128 == 0 and m.out_features % (32 // m.weight_qtype.bits) == 0
 
 
 def fuse_output_quantization(model: torch.nn.Module, enable: bool = True) -> List[str]:
-    """Opt in to (``enable=False``: out of) fused output quantization: every frozen ``QLinear`` with an 8-bit weight qtype, an activation qtype of the
-    same family (qint8 x qint8, qfloat8_e4m3fn x qfloat8_e4m3fn, qfloat8_e5m2 x qfloat8_e5m2) and its output hook still registered is marked, and
-    its forward then gets the output codes from the product kernel's epilogue (``quanto::qbytes_mm_q``) instead of writing the float output and
+    """Opt in to (``enable=False``: out of) fused output quantization: every frozen ``QLinear`` with 16-bit scales and its output hook still registered is
+    marked when it has an 8-bit weight qtype and an activation qtype of the same family (qint8 x qint8, qfloat8_e4m3fn x qfloat8_e4m3fn, qfloat8_e5m2 x
+    qfloat8_e5m2: ``quanto::qbytes_mm_q``), or a qint4 / qint2 weight in a format the W4A8 / W2A8 kernel takes (groups of 128 or per-channel with 128
+    inputs, ``in_features`` a multiple of 128, ``out_features`` a multiple of 8 / 16) and a qint8 / qfloat8_e4m3fn / qfloat8_e5m2 activation qtype
+    (``quanto::qbits_mm_a8_q``).  Its forward then gets the output codes from the product kernel's epilogue instead of writing the float output and
     quantizing it in a second pass - bit-identical codes, same ``output_scale``.  Returns the names of the marked (unmarked) modules.
 
     Not automatic: forward hooks registered by the user and calibration passes read a module's float output before its own hook quantizes it; a marked
-    module hands them codes.  Calibrate first, then call this.  ``QConv2d``, sub-byte weights, fp32 modules and other module classes are never marked;
-    the mark is not saved with the state dict."""
+    module hands them codes.  Calibrate first, then call this.  ``QConv2d``, sub-byte weights outside that format, fp32 modules and other module classes
+    are never marked; the mark is not saved with the state dict."""
     names = []
     for name, m in model.named_modules():
         if type(m) is not QLinear:
@@ -180,8 +193,10 @@ def fuse_output_quantization(model: torch.nn.Module, enable: bool = True) -> Lis
                 names.append(name)
             continue
         wq, aq = m.weight_qtype, m.activation_qtype
-        if (m.frozen and wq is not None and aq is not None and wq.bits == 8 and wq.dtype == aq.dtype and aq.dtype in _FUSED_OUTPUT_DTYPES and "output" in m._quantize_hooks
+        if not (m.frozen and wq is not None and aq is not None and aq.dtype in _FUSED_OUTPUT_DTYPES and "output" in m._quantize_hooks
                 and m.weight._scale.dtype in (torch.bfloat16, torch.float16)):
+            continue
+        if (wq.bits == 8 and wq.dtype == aq.dtype) or (wq in (qint4, qint2) and _a8_gate_admits(m)):
             m._fuse_output_quantization = True
             names.append(name)
     return names

@@ -3,7 +3,7 @@ from typing import Optional
 
 import torch
 
-from ..tensor import ActivationQBytesTensor, Optimizer, QTensor, WeightQBytesTensor, qtype
+from ..tensor import ActivationQBytesTensor, Optimizer, QTensor, WeightQBitsTensor, WeightQBytesTensor, qtype
 from .module import QModuleMixin, register_qmodule
 
 __all__ = ["QLinear"]
@@ -25,7 +25,13 @@ class QLinear(QModuleMixin, torch.nn.Linear):
         if self._fuse_output_quantization and self._codes_from_epilogue(input, w):
             # marked by fuse_output_quantization: product and output quantization in one op (quanto::qbytes_mm_q), bit-identical to the product
             # followed by the output hook - which then passes these codes through
-            codes = torch.ops.quanto.qbytes_mm_q(input._data, w._data, input._scale * w._scale, self.bias, self.output_scale)
+            # (8-bit weights: quanto::qbytes_mm_q; int4 / int2 weights: quanto::qbits_mm_a8_q on the packed data as stored)
+            if isinstance(w, WeightQBitsTensor):
+                n, k = w.shape
+                codes = torch.ops.quanto.qbits_mm_a8_q(input._data, input._scale, w._data._data, w._scale, w._shift, self.bias, self.output_scale,
+                                                       w._data.bits, w._group_size, n, k)
+            else:
+                codes = torch.ops.quanto.qbytes_mm_q(input._data, w._data, input._scale * w._scale, self.bias, self.output_scale)
             return ActivationQBytesTensor(self.activation_qtype, codes.size(), codes.stride(), codes, self.output_scale)
         if type(input) is torch.Tensor and isinstance(w, QTensor):
             return type(w).__torch_function__(torch.nn.functional.linear, (type(w),), (input, w, self.bias))
@@ -33,9 +39,11 @@ class QLinear(QModuleMixin, torch.nn.Linear):
 
     def _codes_from_epilogue(self, input, w) -> bool:
         """Whether this call is the one the fused op computes: stored codes of the module's own activation qtype with a scalar scale against a frozen
-        8-bit weight, the output hook still in place, no gradient wanted (the op has no backward)."""
-        if not (isinstance(input, ActivationQBytesTensor) and type(w) is WeightQBytesTensor and self.frozen and "output" in self._quantize_hooks):
+        8-bit weight of the same dtype or a frozen int4 / int2 weight (the marking checked its format), the output hook still in place, no gradient
+        wanted (the op has no backward)."""
+        sub_byte = isinstance(w, WeightQBitsTensor)
+        if not (isinstance(input, ActivationQBytesTensor) and (sub_byte or type(w) is WeightQBytesTensor) and self.frozen and "output" in self._quantize_hooks):
             return False
-        if input.qtype != self.activation_qtype or input._scale.numel() != 1 or input._data.dtype != w._data.dtype:
+        if input.qtype != self.activation_qtype or input._scale.numel() != 1 or not (sub_byte or input._data.dtype == w._data.dtype):
             return False
         return not (torch.is_grad_enabled() and (input.requires_grad or w.requires_grad or (self.bias is not None and self.bias.requires_grad)))
