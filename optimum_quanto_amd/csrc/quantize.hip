@@ -108,6 +108,16 @@ int launch_mode(const void* x, const void* s, void* out, int64_t numel, int64_t 
 // (tensor/qbytes.py:23-36: `scale * data.to(dtype)` = a cast kernel and a multiply kernel, 7 bytes of traffic per element in bf16 - here 3).  Every int8 / fp8
 // value is exact in bf16 / fp16 / fp32, so T(q) is exact and the product has one rounding: fp32 multiply, rounded to T - what aten's mul does through its
 // opmath type.  16 elements per thread and iteration: one 16-byte load, two 16-byte (16-bit T) or four (fp32) stores.
+//
+// The fp32 product passes an optimisation barrier before it is rounded to T.  Without it the compiler folds multiply and fp16 conversion into
+// v_fma_mix{lo,hi}_f16 with a +0 addend for some of the 16 elements, and (-0) * s + (+0) is +0: the -0 code of a float8 kind came out as +0 there.
+template <int QDT, int ODT>
+__device__ __forceinline__ typename Elem<ODT>::T dequantize_one(uint8_t b, float s) {
+  float p = decode8<QDT>(b) * s;
+  if constexpr (ODT == QUANTO_HIP_F16) asm("" : "+v"(p));
+  return Elem<ODT>::from_f32(p);
+}
+
 template <int QDT, int ODT>
 __global__ void __launch_bounds__(256) dequantize_symmetric_kernel(const uint8_t* __restrict__ q, const typename Elem<ODT>::T* __restrict__ scale,
                                                                    typename Elem<ODT>::T* __restrict__ out, int64_t numel) {
@@ -121,13 +131,13 @@ __global__ void __launch_bounds__(256) dequantize_symmetric_kernel(const uint8_t
     *reinterpret_cast<u32x4*>(b) = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(q) + v);
     T o[16];
 #pragma unroll
-    for (int k = 0; k < 16; ++k) o[k] = E::from_f32(decode8<QDT>(b[k]) * s);
+    for (int k = 0; k < 16; ++k) o[k] = dequantize_one<QDT, ODT>(b[k], s);
 #pragma unroll
     for (int k = 0; k < (int)(16 * sizeof(T) / 16); ++k)
       __builtin_nontemporal_store(reinterpret_cast<const u32x4*>(o)[k], reinterpret_cast<u32x4*>(out + (v << 4)) + k);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (int64_t i = nvec << 4; i < numel; ++i) out[i] = E::from_f32(decode8<QDT>(q[i]) * s);
+    for (int64_t i = nvec << 4; i < numel; ++i) out[i] = dequantize_one<QDT, ODT>(q[i], s);
 }
 
 template <int QDT, int ODT>

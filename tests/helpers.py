@@ -200,3 +200,124 @@ class observed_activation_scales:
     def __exit__(self, *exc):
         for h in self.handles:
             h.remove()
+
+
+# ---- designed input sets of the elementwise quantize / dequantize tests (test_elementwise_values_cpu.py, test_elementwise_values_gpu.py) ------------------
+TARGETS = {"int8": torch.int8, "e4m3fn": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
+FINITE_CODES = {"int8": 256, "e4m3fn": 254, "e5m2": 248}  # distinct finite codes of each 8-bit target
+# per-tensor scales of the 16-bit sets, each rounded to the dtype: six shared ones, one that makes fp16 quotients overflow / bf16 quotients leave fp32's
+# range and one at the other end (a subnormal fp16 scale)
+SCALES_16 = {"fp16": (1.0, 0.5, 3.0, 0.0123, 1e-4, 700.0, 6e-8, 60000.0), "bf16": (1.0, 0.5, 3.0, 0.0123, 1e-4, 700.0, 1e-30, 1e30)}
+SCALES_32 = (1.0, 2.0 ** -7, 3.0, 0.0123, 1e-4)
+AFFINE_SCALES = (1.0, 0.5, 3.0, 0.0123, 0.37)
+AFFINE_ROTATIONS = 20  # rotation r gives group g the scale (g + r) % 5 and the shift (g + r) % 4: every group meets the twenty pairs
+
+
+def scale_tensor(values, dt: str) -> torch.Tensor:
+    """The listed scales, rounded to ``dt``."""
+    return torch.tensor(values, dtype=torch.float64).to(TORCH_DT[dt])
+
+
+def finite_values_16(dt: str, limit=None) -> torch.Tensor:
+    """Every finite bit pattern of a 16-bit float dtype in bit order (both zeros, every subnormal): 63488 fp16 / 65280 bf16 values; ``limit``: only
+    those with |x| <= limit."""
+    v = torch.arange(65536, dtype=torch.int32).to(torch.int16).view(TORCH_DT[dt])
+    keep = torch.isfinite(v) if limit is None else v.to(torch.float32).abs() <= limit
+    return v[keep].clone()
+
+
+def value_vector_16(dt: str) -> torch.Tensor:
+    """finite_values_16 plus its first three values again: both counts are multiples of 8, and with three more an 8-wide vector straddles two rows of
+    the repeated vector, the columns of seven rotations do not fill a vector and the per-tensor launch has a ragged tail."""
+    v = finite_values_16(dt)
+    return torch.cat([v, v[:3]])
+
+
+def fp8_boundaries(kind: str) -> np.ndarray:
+    """float64: every finite value of the float8 kind (both zeros) and every midpoint between adjacent ones - the points where the code changes."""
+    vals = O.fp8_decode(np.arange(256, dtype=np.uint8), kind).astype(np.float64)
+    vals = vals[np.isfinite(vals)]
+    u = np.unique(vals)
+    return np.concatenate([vals, (u[:-1] + u[1:]) / 2])
+
+
+def symmetric_boundaries(target: str) -> np.ndarray:
+    if target == "int8":
+        return np.arange(-130, 130, dtype=np.float64) + 0.5
+    return fp8_boundaries(target)
+
+
+def tie_inputs(boundaries: np.ndarray, scale: float, dt: str = "fp32") -> torch.Tensor:
+    """fl32(b * s) for every boundary b and its three fp32 neighbours on each side, in one fp32 tensor; for a 16-bit ``dt`` those values rounded to it,
+    the ones that leave its finite range dropped (s is then the scale rounded to ``dt``)."""
+    s = np.float32(scale_tensor([scale], dt).to(torch.float32).item())
+    b = boundaries.astype(np.float32)
+    assert (b.astype(np.float64) == boundaries).all(), "boundaries are exact in fp32"
+    centre = b * s
+    cols = [centre]
+    for direction in (-np.inf, np.inf):
+        x = centre
+        for _ in range(3):
+            x = np.nextafter(x, np.float32(direction), dtype=np.float32)
+            cols.append(x)
+    x = torch.from_numpy(np.stack(cols, axis=1).reshape(-1)).to(TORCH_DT[dt])
+    return x[torch.isfinite(x)].clone()
+
+
+def axis_first_case(dt: str):
+    """([8, n] base whose rows are the value vector, [8, 1] scales): n is no multiple of 8, vectors straddle rows."""
+    return value_vector_16(dt).repeat(8, 1), scale_tensor(SCALES_16[dt], dt).reshape(8, 1)
+
+
+def axis_last_case(dt: str):
+    """([n, 7] base whose column c is the value vector rotated by 9001 c, [1, 7] scales): 7 does not divide the 8-wide vector."""
+    v = value_vector_16(dt)
+    return torch.stack([torch.roll(v, 9001 * c) for c in range(7)], dim=1).contiguous(), scale_tensor(SCALES_16[dt][:7], dt).reshape(1, 7)
+
+
+def affine_case_16(dt: str, bits: int, int_shift: bool, rotation: int = 0):
+    """(base [N, 256], scale [2N, 1], shift [2N, 1]) for groups of 128: every finite value with |x| <= 64 in bit order, padded with zeros; group g has
+    scale AFFINE_SCALES[(g + r) % 5] and the float shift (0, 0.5 s, 7.5 s, 1.25)[(g + r) % 4] or the zero-point (g + r) % 2^bits."""
+    v = finite_values_16(dt, limit=64.0)
+    K = 256
+    N = -(-v.numel() // K)
+    base = torch.zeros(N * K, dtype=v.dtype)
+    base[: v.numel()] = v
+    g = torch.arange(N * K // 128) + rotation
+    s64 = torch.tensor(AFFINE_SCALES, dtype=torch.float64)[g % 5]
+    scale = s64.to(v.dtype).reshape(-1, 1)
+    if int_shift:
+        shift = (g % (1 << bits)).to(torch.uint8).reshape(-1, 1)
+    else:
+        s = scale.reshape(-1).to(torch.float64)
+        table = torch.stack([torch.zeros_like(s), 0.5 * s, 7.5 * s, torch.full_like(s, 1.25)])
+        shift = table[g % 4, torch.arange(g.numel())].to(v.dtype).reshape(-1, 1)
+    return base.reshape(N, K), scale, shift
+
+
+def affine_case_32(bits: int, int_shift: bool):
+    """fp32 ties of the affine quantizer: for each scale of SCALES_32 two groups of 128 holding fl32((k + 0.5) s), k = -2 .. 2^bits, with three fp32
+    neighbours on each side, padded with zeros; group g has the float shift (g % 3) s (the tie moves up by whole codes) or the zero-point g % 2^bits."""
+    rows, scales = [], []
+    for s in SCALES_32:
+        x = tie_inputs(np.arange(-2, (1 << bits) + 1, dtype=np.float64) + 0.5, s)
+        assert x.numel() <= 256
+        row = torch.zeros(256, dtype=torch.float32)
+        row[: x.numel()] = x
+        rows.append(row)
+        scales += [s, s]
+    scale = torch.tensor(scales, dtype=torch.float64).to(torch.float32).reshape(-1, 1)
+    g = torch.arange(scale.numel())
+    shift = (g % (1 << bits)).to(torch.uint8).reshape(-1, 1) if int_shift else ((g % 3).to(torch.float32).reshape(-1, 1) * scale)
+    return torch.stack(rows), scale, shift
+
+
+def dequantize_codes(numel: int) -> torch.Tensor:
+    """uint8: the 256 byte values, tiled to ``numel``."""
+    return (torch.arange(numel, dtype=torch.int32) % 256).to(torch.uint8)
+
+
+def dequantize_scales(dt: str) -> torch.Tensor:
+    """Every scale of the 16-bit lists that ``dt`` can hold (fp32: all ten), rounded to it."""
+    values = SCALES_16[dt] if dt in SCALES_16 else tuple(dict.fromkeys(SCALES_16["fp16"] + SCALES_16["bf16"]))
+    return scale_tensor(values, dt)
