@@ -394,6 +394,27 @@ int quanto_hip_qbytes_conv2d_a8(const void* x, const void* a_scale, const void* 
                                 void* stream);
 
 /*
+ * quanto::qbytes_conv2d_a8_q(Tensor input, Tensor input_scale, Tensor weight, Tensor weight_scale, Tensor? bias, Tensor out_scale, int[] stride,
+ *                            int[] padding, int[] dilation) -> Tensor
+ *   replaces, for a QConv2d with quantized activations, the convolution AND the re-quantization of its output (nn/qmodule.py:281-299 ->
+ *   library/quantize.py:26-55): yq = quantize_symmetric(qbytes_conv2d_a8(x, ...) (+ bias), a_dtype, per-tensor, out_scale) in ONE launch (two when the K
+ *   split runs: the reduce kernel stores the codes), the [B, OC, OH, OW] tensor of `mid_dtype` never written.  Bit-identical to
+ *   quanto_hip_qbytes_conv2d_a8 followed by quanto_hip_quantize_symmetric.
+ * x / a_scale / w / w_scale / bias as for quanto_hip_qbytes_conv2d_a8 with out_dtype = mid_dtype; out_scale: mid_dtype[1] (device); yq:
+ * a_dtype[B, OC, OH, OW] codes (I8 / F8_E4M3FN / F8_E5M2: the activation's own type).  No alignment rule: a yq off a 4-byte boundary is stored per byte.
+ * Served: exactly what quanto_hip_qbytes_conv2d_a8 serves, mid_dtype in {F32, F16, BF16}.  The checks run in that entry's order - inconsistent
+ * geometry QUANTO_HIP_EINVAL, a format or geometry that is not served QUANTO_HIP_ENOTSUP, both ahead of any look at the data pointers and with yq
+ * untouched (the caller runs the two entries); B OH OW = 0: QUANTO_HIP_OK, nothing launched; then a NULL x, a_scale, w, w_scale, out_scale or yq:
+ * QUANTO_HIP_EINVAL.  workspace: the K-split scratch of quanto_hip_qbytes_conv2d_a8, same contract, same
+ * quanto_hip_qbytes_conv2d_a8_workspace_size bytes (the plan does not look at the output).
+ * quanto_hip_last_kernel() reports the unfused name plus "_q" ("conv2d_a8_int8_q", "conv2d_a8_fp8_q", "conv2d_a8_fp8_w8_q") after a successful launch.
+ */
+int quanto_hip_qbytes_conv2d_a8_q(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, const void* out_scale, void* yq,
+                                  int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h,
+                                  int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int mid_dtype, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
+/*
  * Scratch bytes quanto_hip_qbytes_conv2d_a8 wants for its K split (0: unsplit, or B OH OW = 0): partial tiles that a separate kernel adds in split
  * order (deterministic, no atomics, nothing to zero).  QUANTO_HIP_EINVAL for inconsistent geometry, QUANTO_HIP_ENOTSUP for a format or geometry the
  * kernel does not serve.  Needs no device.

@@ -45,6 +45,8 @@ int qdense_conv2d_rows(const void*, const void*, const void*, void*, const ConvG
 int qbytes_conv2d_a8_kind(int, int, int);
 size_t conv2d_a8_workspace(int64_t, int64_t, int64_t);
 int qbytes_conv2d_a8(const void*, const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t, hipStream_t, int*);
+int qbytes_conv2d_a8_q(const void*, const void*, const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t,
+                       hipStream_t, int*);
 int qbytes_conv2d_mfma(const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t, hipStream_t, bool* rows);
 int qbytes_mm_gemv_multi(const void*, int, const void* const*, const void* const*, const void* const*, void* const*, const int64_t*, int64_t,
                          int64_t, int, int, hipStream_t);
@@ -895,6 +897,27 @@ int quanto_hip_qbytes_conv2d_a8(const void* x, const void* a_scale, const void* 
   int kind = -1;
   const int r = qbytes_conv2d_a8(x, a_scale, w, w_scale, bias, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), &kind);
   static const char* const names[3] = {"conv2d_a8_int8", "conv2d_a8_fp8", "conv2d_a8_fp8_w8"};
+  if (r == QUANTO_HIP_OK) set_last_kernel(names[kind]);
+  return r;
+}
+
+// the same convolution with the layer's output quantization in the epilogue: the checks of the entry above in its order - format and geometry are
+// refused ahead of any look at the data pointers - then the same plan and workspace
+int quanto_hip_qbytes_conv2d_a8_q(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, const void* out_scale, void* yq,
+                                  int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h,
+                                  int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int mid_dtype, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  ConvGeom g;
+  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, &g);
+  if (geo != QUANTO_HIP_OK) return geo;
+  if (qbytes_conv2d_a8_kind(a_dtype, b_dtype, mid_dtype) < 0) return QUANTO_HIP_ENOTSUP;
+  if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
+  if (!conv_geometry_ok(g)) return QUANTO_HIP_ENOTSUP;
+  if (!x || !a_scale || !w || !w_scale || !out_scale || !yq) return QUANTO_HIP_EINVAL;
+  int kind = -1;
+  const int r = qbytes_conv2d_a8_q(x, a_scale, w, w_scale, bias, out_scale, yq, g, a_dtype, b_dtype, mid_dtype, workspace, workspace_bytes,
+                                   reinterpret_cast<hipStream_t>(stream), &kind);
+  static const char* const names[3] = {"conv2d_a8_int8_q", "conv2d_a8_fp8_q", "conv2d_a8_fp8_w8_q"};
   if (r == QUANTO_HIP_OK) set_last_kernel(names[kind]);
   return r;
 }

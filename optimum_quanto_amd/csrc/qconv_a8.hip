@@ -27,10 +27,14 @@
 // an integer of magnitude <= 128 is exact in fp32), no extra accumulator set, no fp32 math between the MFMAs.
 // K split (grids that cannot fill the chip): split z parks its int32 / fp32 tile in `partials`, a separate kernel adds the
 // splits in split order (deterministic; int32: bit-identical to the unsplit result) and runs the epilogue.
+// QOUT: the quantized-output form (`y` holds codes of the activation's own type, store_codes): what quanto::quantize_symmetric(y, activation dtype,
+// None, out_scale) makes of the element the epilogue above stores, from the same accumulators - the tile kernel when unsplit, the reduce kernel when
+// split.  The existing instantiations compile the epilogue they had.
 #include <type_traits>
 
 #include "qh_conv.h"
 #include "qh_mfma.h"
+#include "qh_quantize.h"  // quotient_in, clamp_target, pack4: the rule of quantize.hip, shared with the code-storing GEMM epilogues
 
 namespace qh {
 namespace conv8 {
@@ -60,6 +64,7 @@ struct Args {
   int S;                  // K split over blockIdx.z
   void* partials;         // [S][tiles][8 waves][8 fragments][64 lanes] 16 bytes (int32 / fp32)
   uint32_t khw_magic, kw_magic;  // ceil(2^32 / (KH KW)), ceil(2^32 / KW); 0 when the divisor is 1 (conv_fill_ktab)
+  const void* out_scale;  // QOUT: one element, out dtype - `y` then holds [B, OC, OH, OW] one-byte codes of the activation's type
 };
 
 // ---- epilogue (conv_store_tile): the channel's factor is the scale product rounded to the output dtype, as torch multiplies the two scale tensors
@@ -81,6 +86,79 @@ __device__ __forceinline__ void store_tile(const Args& a, const AV (&acc)[4][2],
     store_tile_dt<QUANTO_HIP_F32>(a, acc, m0, nt, wm, wn, lane);
 }
 
+// ---- the same epilogue storing OUTPUT CODES (QOUT).  Per element the two kernels back to back: t = the element conv_store_tile<DT, 1, CONV_EPI_8BIT>
+// stores, by its statements - fp32(acc) * sc[n] behind the asm volatile, rounded to T, the bias added, rounded again - then the rule of qh_quantize.h
+// on t: T(fp32(t) / fp32(out_scale)) with a correctly rounded divide, clamp_target, pack4.  ODT: the activation's own type.  A lane's four
+// accumulator rows are four neighbouring pixels of one channel plane = one dword of codes: ONE 4-byte store when they lie in one image, the plane
+// size is a multiple of 4 and yq is 4-byte aligned; per byte otherwise, with conv_store_tile's walk over image ends.
+template <int DT, int ODT, typename AV>
+__device__ __forceinline__ void store_codes_dt(const Args& a, const AV (&acc)[4][2], int m0, int nt, int wm, int wn, int lane) {
+  using E = Elem<DT>;
+  using T = typename E::T;
+  uint8_t* yq = reinterpret_cast<uint8_t*>(a.y);
+  const int M = a.M, N = a.N, L = a.OH * a.OW;
+  const float as = E::to_f32(*reinterpret_cast<const T*>(a.a_scale));
+  const float os = E::to_f32(*reinterpret_cast<const T*>(a.out_scale));
+  const bool vec = (L & 3) == 0 && (reinterpret_cast<uintptr_t>(a.y) & 3) == 0;
+  int bq[4], lq[4];  // image and offset inside the plane of the first of the lane's four pixels of fragment i
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
+    const int b = m / L;
+    bq[i] = b;
+    lq[i] = m - b * L;
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int n = nt * BN + wn * 32 + j * 16 + (lane & 15);
+    if (n >= N) continue;
+    const float sc = E::to_f32(E::from_f32(as * E::to_f32(reinterpret_cast<const T*>(a.w_scale)[n])));
+    const bool has_bias = a.bias != nullptr;
+    const float bv = has_bias ? E::to_f32(reinterpret_cast<const T*>(a.bias)[n]) : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
+      if (m >= M) continue;
+      float q[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = (float)acc[i][j][r] * sc;
+        asm volatile("" : "+v"(v));  // product rounded to fp32 first, with and without bias (no single-rounding v_fma_mixlo_f16)
+        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv;  // the reference's order: rounded convolution output + bias, rounded again
+        const T t = E::from_f32(v);  // the element conv_store_tile stores
+        q[r] = clamp_target<ODT>(quotient_in<DT>(E::to_f32(t), os));
+      }
+      const uint32_t codes = pack4<ODT>(q);
+      if (vec && m + 3 < M) {  // (L % 4 == 0 and m % 4 == 0: the four pixels are in one image, aligned)
+        *reinterpret_cast<uint32_t*>(yq + ((size_t)bq[i] * N + n) * L + lq[i]) = codes;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (m + r < M) {
+            int bb = bq[i], ll = lq[i] + r;
+            while (ll >= L) {  // an image ends inside the lane's four pixels (planes of fewer than 4 pixels: more than once)
+              ll -= L;
+              ++bb;
+            }
+            yq[((size_t)bb * N + n) * L + ll] = (uint8_t)(codes >> (8 * r));
+          }
+      }
+    }
+  }
+}
+template <int ODT, typename AV>
+__device__ __forceinline__ void store_codes(const Args& a, const AV (&acc)[4][2], int m0, int nt, int wm, int wn, int lane) {
+  if (a.out_dtype == QUANTO_HIP_BF16)
+    store_codes_dt<QUANTO_HIP_BF16, ODT>(a, acc, m0, nt, wm, wn, lane);
+  else if (a.out_dtype == QUANTO_HIP_F16)
+    store_codes_dt<QUANTO_HIP_F16, ODT>(a, acc, m0, nt, wm, wn, lane);
+  else
+    store_codes_dt<QUANTO_HIP_F32, ODT>(a, acc, m0, nt, wm, wn, lane);
+}
+// the code type of a kernel: the activation's own (int8 x int8 -> int8; fp8 activations: AF)
+template <bool INT, int AF>
+constexpr int code_dtype() { return INT ? QUANTO_HIP_I8 : AF == F_E5M2 ? QUANTO_HIP_F8_E5M2 : QUANTO_HIP_F8_E4M3FN; }
+
 // int8 weight codes (4 per dword) -> e4m3 codes of lo = q & 15 and of hi = q >> 4 (16-entry tables, three v_perm each)
 __device__ __forceinline__ uint32_t nibble_codes(uint32_t s, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3) {
   const uint32_t q7 = s & 0x07070707u;
@@ -88,7 +166,7 @@ __device__ __forceinline__ uint32_t nibble_codes(uint32_t s, uint32_t t0, uint32
   return __builtin_amdgcn_perm(hi, lo, ((s >> 1) & 0x04040404u) | 0x03020100u);  // byte i from hi when bit 3 of nibble i is set
 }
 
-template <int KIND, int AF, int BF, bool WIDE>
+template <int KIND, int AF, int BF, bool WIDE, bool QOUT = false>
 __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
   constexpr int NO_TAP = WIDE ? 127 : 31;
   using AV = typename std::conditional<KIND == K_I8, i32x4, f32x4>::type;
@@ -260,30 +338,46 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
   }
 
   if (S > 1) return conv_park_tile(a.partials, sp, nt, wave, lane, acc);
-  store_tile(a, acc, m0, nt, wm, wn, lane);
+  if constexpr (QOUT)
+    store_codes<code_dtype<KIND == K_I8, AF>()>(a, acc, m0, nt, wm, wn, lane);
+  else
+    store_tile(a, acc, m0, nt, wm, wn, lane);
 }
 
 // split-K tail: one wave per (output tile, wave slot) adds that slot's eight fragments over the S partial tiles in split order, then the epilogue
-template <bool INT>
+// (AF: the fp8 activation format, which only the code-storing epilogue needs - it names the code type)
+template <bool INT, int AF = F_E4M3, bool QOUT = false>
 __global__ void __launch_bounds__(64) qconv2d_a8_reduce_kernel(const Args a) {
   using AV = typename std::conditional<INT, i32x4, f32x4>::type;
   const int lane = threadIdx.x, wave = blockIdx.z, S = a.S;
   AV acc[4][2];
   QH_CONV_SPLIT_SUM(AV, a.partials, S, lane, wave, acc);
-  store_tile(a, acc, blockIdx.y * BM, blockIdx.x, wave >> 2, wave & 3, lane);
+  if constexpr (QOUT)
+    store_codes<code_dtype<INT, AF>()>(a, acc, blockIdx.y * BM, blockIdx.x, wave >> 2, wave & 3, lane);
+  else
+    store_tile(a, acc, blockIdx.y * BM, blockIdx.x, wave >> 2, wave & 3, lane);
 }
 
-template <int KIND, int AF, int BF, bool WIDE>
+template <int KIND, int AF, int BF, bool WIDE, bool QOUT>
 static void launch_k(const Args& a, int ntiles, int mtiles, hipStream_t stream) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qconv2d_a8_kernel<KIND, AF, BF, WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-  hipLaunchKernelGGL((qconv2d_a8_kernel<KIND, AF, BF, WIDE>), dim3(ntiles, mtiles, a.S), dim3(NT), LDS_BYTES, stream, a);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qconv2d_a8_kernel<KIND, AF, BF, WIDE, QOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  hipLaunchKernelGGL((qconv2d_a8_kernel<KIND, AF, BF, WIDE, QOUT>), dim3(ntiles, mtiles, a.S), dim3(NT), LDS_BYTES, stream, a);
 }
-template <int KIND, int AF, int BF>
+// the tile kernel, then - split - the reduce kernel; QOUT reaches whichever of the two runs the epilogue (a split tile kernel parks: it stays the
+// existing instantiation)
+template <int KIND, int AF, int BF, bool QOUT>
 static void launch_w(const Args& a, int ntiles, int mtiles, hipStream_t stream) {
-  if (a.KH * a.KW > 31)
-    launch_k<KIND, AF, BF, true>(a, ntiles, mtiles, stream);
-  else
-    launch_k<KIND, AF, BF, false>(a, ntiles, mtiles, stream);
+  if (a.S > 1) {
+    if (a.KH * a.KW > 31)
+      launch_k<KIND, AF, BF, true, false>(a, ntiles, mtiles, stream);
+    else
+      launch_k<KIND, AF, BF, false, false>(a, ntiles, mtiles, stream);
+    hipLaunchKernelGGL((qconv2d_a8_reduce_kernel<KIND == K_I8, QOUT ? AF : F_E4M3, QOUT>), dim3(ntiles, mtiles, 8), dim3(64), 0, stream, a);
+  } else if (a.KH * a.KW > 31) {
+    launch_k<KIND, AF, BF, true, QOUT>(a, ntiles, mtiles, stream);
+  } else {
+    launch_k<KIND, AF, BF, false, QOUT>(a, ntiles, mtiles, stream);
+  }
 }
 
 }  // namespace conv8
@@ -302,37 +396,44 @@ int qbytes_conv2d_a8_kind(int a_dtype, int b_dtype, int out_dtype) {
 size_t conv2d_a8_workspace(int64_t M, int64_t N, int64_t K) { return conv_split_workspace<conv8::BM, conv8::BN>(M, N, conv_pick_split<conv8::BK, conv8::BM, conv8::BN>(M, N, K)); }
 
 // *kind: the conv8::Kind that ran.  The caller has validated the arguments and the format (qbytes_conv2d_a8_kind >= 0, conv_geometry_ok).
-int qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, const ConvGeom& g, int a_dtype,
-                     int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
+// QOUT: `y` receives a_dtype codes at *out_scale (store_codes); plan, split and workspace do not look at the output.
+template <bool QOUT>
+static int conv2d_a8_run(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, const void* out_scale, void* y,
+                         const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
   using namespace conv8;
   const int k = qbytes_conv2d_a8_kind(a_dtype, b_dtype, out_dtype);
   if (k < 0 || !conv_geometry_ok(g)) return QUANTO_HIP_ENOTSUP;
   Args a{};
   a.x = reinterpret_cast<const uint8_t*>(x), a.a_scale = a_scale, a.w = reinterpret_cast<const uint8_t*>(w), a.w_scale = w_scale, a.bias = bias, a.y = y;
   a.out_dtype = out_dtype;
+  a.out_scale = out_scale;
   conv_set_geometry(a, g);
-  const int S = a.S = conv_plan_split<BK, BM, BN>(a.M, a.N, a.K, workspace, workspace_bytes);
+  a.S = conv_plan_split<BK, BM, BN>(a.M, a.N, a.K, workspace, workspace_bytes);
   a.partials = workspace;
   const int ntiles = (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;
   const bool ae5 = a_dtype == QUANTO_HIP_F8_E5M2, be5 = b_dtype == QUANTO_HIP_F8_E5M2;
   if (k == K_I8) {
-    launch_w<K_I8, 0, 0>(a, ntiles, mtiles, stream);
+    launch_w<K_I8, 0, 0, QOUT>(a, ntiles, mtiles, stream);
   } else if (k == K_F8) {
     if (ae5)
-      be5 ? launch_w<K_F8, F_E5M2, F_E5M2>(a, ntiles, mtiles, stream) : launch_w<K_F8, F_E5M2, F_E4M3>(a, ntiles, mtiles, stream);
+      be5 ? launch_w<K_F8, F_E5M2, F_E5M2, QOUT>(a, ntiles, mtiles, stream) : launch_w<K_F8, F_E5M2, F_E4M3, QOUT>(a, ntiles, mtiles, stream);
     else
-      be5 ? launch_w<K_F8, F_E4M3, F_E5M2>(a, ntiles, mtiles, stream) : launch_w<K_F8, F_E4M3, F_E4M3>(a, ntiles, mtiles, stream);
+      be5 ? launch_w<K_F8, F_E4M3, F_E5M2, QOUT>(a, ntiles, mtiles, stream) : launch_w<K_F8, F_E4M3, F_E4M3, QOUT>(a, ntiles, mtiles, stream);
   } else {
-    ae5 ? launch_w<K_F8W8, F_E5M2, F_E4M3>(a, ntiles, mtiles, stream) : launch_w<K_F8W8, F_E4M3, F_E4M3>(a, ntiles, mtiles, stream);
-  }
-  if (S > 1) {
-    if (k == K_I8)
-      hipLaunchKernelGGL((qconv2d_a8_reduce_kernel<true>), dim3(ntiles, mtiles, 8), dim3(64), 0, stream, a);
-    else
-      hipLaunchKernelGGL((qconv2d_a8_reduce_kernel<false>), dim3(ntiles, mtiles, 8), dim3(64), 0, stream, a);
+    ae5 ? launch_w<K_F8W8, F_E5M2, F_E4M3, QOUT>(a, ntiles, mtiles, stream) : launch_w<K_F8W8, F_E4M3, F_E4M3, QOUT>(a, ntiles, mtiles, stream);
   }
   *kind = k;
   return launch_status();
+}
+
+int qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, const ConvGeom& g, int a_dtype,
+                     int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
+  return conv2d_a8_run<false>(x, a_scale, w, w_scale, bias, nullptr, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream, kind);
+}
+// the same convolution with the layer's output quantization in its epilogue: yq = a_dtype codes of the mid_dtype-rounded output at *out_scale
+int qbytes_conv2d_a8_q(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, const void* out_scale, void* yq,
+                       const ConvGeom& g, int a_dtype, int b_dtype, int mid_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
+  return conv2d_a8_run<true>(x, a_scale, w, w_scale, bias, out_scale, yq, g, a_dtype, b_dtype, mid_dtype, workspace, workspace_bytes, stream, kind);
 }
 
 }  // namespace qh

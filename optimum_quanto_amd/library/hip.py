@@ -133,6 +133,7 @@ _PROTOTYPES = {
     "quanto_hip_qbytes_conv2d_depthwise": (_ci, [_vp] * 5 + [_i64] * 9 + [_ci] * 9 + [_vp]),
     "quanto_hip_qbytes_conv2d_a8": (_ci, [_vp] * 6 + [_i64] * 9 + [_ci] * 9 + [_vp, _sz, _vp]),
     "quanto_hip_qbytes_conv2d_a8_workspace_size": (_i64, [_i64] * 9 + [_ci] * 9),
+    "quanto_hip_qbytes_conv2d_a8_q": (_ci, [_vp] * 7 + [_i64] * 9 + [_ci] * 9 + [_vp, _sz, _vp]),
     "quanto_hip_conv2d_workspace_size": (_i64, [_i64] * 5),
     "quanto_hip_qbits_conv2d_workspace_size": (_i64, [_i64] * 5),
     "quanto_hip_qbits_conv2d_workspace_size_geom": (_i64, [_i64] * 8 + [_ci] * 2),
@@ -433,16 +434,28 @@ class _Bindings:
         """Dense convolution of quantized activation codes ``x`` (per-tensor scale ``x_scale``, one element) with an 8-bit weight [OC, C, KH, KW]
         (per-channel scales ``w_scale``): y = conv(x, w) * round(x_scale * w_scale) (+ bias), in w_scale's dtype.  Raises QuantoHipError(ENOTSUP)
         for formats the kernel does not take."""
-        self._require_cuda(x, x_scale, w, w_scale, bias)
+        return self._conv2d_a8("qbytes_conv2d_a8", x, x_scale, w, w_scale, bias, None, stride, padding, dilation)
+
+    def qbytes_conv2d_a8_q(self, x, x_scale, w, w_scale, bias, out_scale, stride, padding, dilation):
+        """``qbytes_conv2d_a8`` with the layer's output quantization in the kernel epilogue: codes in ``x.dtype`` of the convolution output at the
+        per-tensor ``out_scale`` (one element), bit-identical to ``quantize_symmetric(qbytes_conv2d_a8(...), x.dtype, None, out_scale)``.  Same
+        formats, plan cache entry and scratch as ``qbytes_conv2d_a8``."""
+        if out_scale.numel() != 1:
+            raise QuantoHipError("qbytes_conv2d_a8_q: the output scale is per-tensor (one element)")
+        return self._conv2d_a8("qbytes_conv2d_a8_q", x, x_scale, w, w_scale, bias, out_scale, stride, padding, dilation)
+
+    def _conv2d_a8(self, what, x, x_scale, w, w_scale, bias, out_scale, stride, padding, dilation):
+        """The one host path of both entries: ``out_scale`` None -> the float output, else the codes."""
+        self._require_cuda(x, x_scale, w, w_scale, bias, out_scale)
         if x_scale.numel() != 1:
-            raise QuantoHipError("qbytes_conv2d_a8 expects a per-tensor activation scale")
+            raise QuantoHipError(f"{what} expects a per-tensor activation scale")
         x, w = x.contiguous(), w.contiguous()
         B, C, H, W = x.shape
         OC, _, KH, KW = w.shape
         odt = w_scale.dtype
         ws_bytes = self._conv2d_a8_workspace(tuple(x.shape), tuple(w.shape), x.dtype, w.dtype, odt, stride, padding, dilation)
         if ws_bytes < 0:
-            self._check(int(ws_bytes), "qbytes_conv2d_a8")
+            self._check(int(ws_bytes), what)
         OH = self.conv2d_out_size(H, KH, stride[0], padding[0], dilation[0])
         OW = self.conv2d_out_size(W, KW, stride[1], padding[1], dilation[1])
         s = w_scale.reshape(-1).contiguous()
@@ -451,13 +464,17 @@ class _Bindings:
         xs = x_scale.reshape(1).to(odt).contiguous()
         if bias is not None:
             bias = bias.to(odt).contiguous()
-        y = torch.empty((B, OC, max(OH, 0), max(OW, 0)), dtype=odt, device=x.device)
+        y = torch.empty((B, OC, max(OH, 0), max(OW, 0)), dtype=odt if out_scale is None else x.dtype, device=x.device)
+        geometry = (B, C, H, W, OC, KH, KW, OH, OW, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], _dt(x), _dt(w), _DTYPES[odt])
         with _DeviceGuard(x.device) as stream:
             ws = self._scratch(x.device, ws_bytes, stream) if ws_bytes > 0 else None
-            st = self._c.quanto_hip_qbytes_conv2d_a8(_ptr(x), _ptr(xs), _ptr(w), _ptr(s), _ptr(bias), _ptr(y), B, C, H, W, OC, KH, KW, OH, OW,
-                                                     stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], _dt(x), _dt(w), _dt(y),
-                                                     _ptr(ws), ws_bytes, stream)
-        self._check(st, "qbytes_conv2d_a8")
+            if out_scale is None:
+                st = self._c.quanto_hip_qbytes_conv2d_a8(_ptr(x), _ptr(xs), _ptr(w), _ptr(s), _ptr(bias), _ptr(y), *geometry, _ptr(ws), ws_bytes, stream)
+            else:
+                os_ = out_scale.reshape(1).to(odt).contiguous()
+                st = self._c.quanto_hip_qbytes_conv2d_a8_q(_ptr(x), _ptr(xs), _ptr(w), _ptr(s), _ptr(bias), _ptr(os_), _ptr(y), *geometry, _ptr(ws),
+                                                           ws_bytes, stream)
+        self._check(st, what)
         return y
 
     # -- quanto::qbits_conv2d (implicit GEMM, int4 dequantized while staged) -----------------------------------

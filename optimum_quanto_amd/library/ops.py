@@ -209,6 +209,30 @@ _register("qbytes_conv2d_a8", "(Tensor input, Tensor input_scale, Tensor weight,
           "int[] dilation) -> Tensor", qbytes_conv2d_a8_hip, default=qbytes_conv2d_a8_default)
 
 
+def qbytes_conv2d_a8_q_default(input, input_scale, weight, weight_scale, bias, out_scale, stride, padding, dilation):
+    """The two-op sequence of a QConv2d with quantized activations: the convolution in the weight scale's dtype, re-quantized per-tensor to the
+    activations' own 8-bit dtype (nn/qmodule.py:281-299)."""
+    out = torch.ops.quanto.qbytes_conv2d_a8(input, input_scale, weight, weight_scale, bias, stride, padding, dilation)
+    return torch.ops.quanto.quantize_symmetric(out, input.dtype, None, out_scale.to(out.dtype).reshape(()))
+
+
+def qbytes_conv2d_a8_q_hip(input, input_scale, weight, weight_scale, bias, out_scale, stride, padding, dilation):
+    """ROCm: the convolution kernel's epilogue stores the codes (csrc/qconv_a8.hip) exactly when ``qbytes_conv2d_a8_hip`` takes that kernel; everything
+    else runs the two-op sequence on the existing ops - the caller always gets codes."""
+    lib = quanto_hip.lib
+    stride, padding, dilation = tuple(stride), tuple(padding), tuple(dilation)
+    if (input_scale.numel() == 1 and out_scale.numel() == 1
+            and lib.qbytes_conv2d_a8_supported(input, weight, weight_scale.dtype, stride, padding, dilation)):
+        return lib.qbytes_conv2d_a8_q(input, input_scale, weight, weight_scale, bias, out_scale, stride, padding, dilation)
+    return qbytes_conv2d_a8_q_default(input, input_scale, weight, weight_scale, bias, out_scale, stride, padding, dilation)
+
+
+# new op: the convolution of a QConv2d with quantized activations with the layer's output quantization fused into the kernel epilogue - bit-identical
+# to quantize_symmetric(qbytes_conv2d_a8(...)), one launch and no [B, OC, OH, OW] float tensor
+_register("qbytes_conv2d_a8_q", "(Tensor input, Tensor input_scale, Tensor weight, Tensor weight_scale, Tensor? bias, Tensor out_scale, int[] stride, "
+          "int[] padding, int[] dilation) -> Tensor", qbytes_conv2d_a8_q_hip, default=qbytes_conv2d_a8_q_default)
+
+
 # ------------------------------------------------------------------------------------------------
 # quanto::quantize_symmetric / quantize_affine (quantize-time, plain torch on every device)
 # ------------------------------------------------------------------------------------------------

@@ -4,8 +4,8 @@ from typing import Any, Dict, List, Optional, Union
 
 import torch
 
-from .nn import QLinear, QModuleMixin, quantize_module
-from .tensor import Optimizer, QTensor, WeightQBitsTensor, qint2, qint4, qtype
+from .nn import QConv2d, QLinear, QModuleMixin, quantize_module
+from .tensor import Optimizer, QTensor, WeightQBitsTensor, WeightQBytesTensor, qint2, qint4, qtype
 from .tensor.weights import _fusable
 
 __all__ = ["quantize", "freeze", "requantize", "quantization_map", "fuse_output_quantization"]
@@ -172,20 +172,39 @@ def _a8_gate_admits(m: QLinear) -> bool:
     return group == 128 and m.in_features % 128 == 0 and m.out_features % (32 // m.weight_qtype.bits) == 0
 
 
+def _conv_a8_gate_admits(m: QConv2d) -> bool:
+    """The layers ``quanto::qbytes_conv2d_a8_q`` serves (csrc/qconv_a8.hip): dense, zero padding given as numbers, an 8-bit weight, and a served
+    (activation, weight) pair - qint8 x qint8, or qfloat8_e4m3fn / qfloat8_e5m2 activations x qfloat8_e4m3fn / qfloat8_e5m2 / qint8 weights, except
+    e5m2 activations with fp16 scales (their scale product underflows fp16: tensor/weights.py, conv2d_a8_eligible)."""
+    wq, aq = m.weight_qtype, m.activation_qtype
+    if wq.bits != 8 or m.groups != 1 or m.padding_mode != "zeros" or isinstance(m.padding, str) or not isinstance(m.weight, WeightQBytesTensor):
+        return False
+    fp8 = (torch.float8_e4m3fn, torch.float8_e5m2)
+    if aq.dtype == torch.int8:
+        return wq.dtype == torch.int8
+    if aq.dtype == torch.float8_e5m2 and m.weight._scale.dtype == torch.float16:
+        return False
+    return aq.dtype in fp8 and (wq.dtype in fp8 or wq.dtype == torch.int8)
+
+
 def fuse_output_quantization(model: torch.nn.Module, enable: bool = True) -> List[str]:
     """Opt in to (``enable=False``: out of) fused output quantization: every frozen ``QLinear`` with 16-bit scales and its output hook still registered is
     marked when it has an 8-bit weight qtype and an activation qtype of the same family (qint8 x qint8, qfloat8_e4m3fn x qfloat8_e4m3fn, qfloat8_e5m2 x
     qfloat8_e5m2: ``quanto::qbytes_mm_q``), or a qint4 / qint2 weight in a format the W4A8 / W2A8 kernel takes (groups of 128 or per-channel with 128
     inputs, ``in_features`` a multiple of 128, ``out_features`` a multiple of 8 / 16) and a qint8 / qfloat8_e4m3fn / qfloat8_e5m2 activation qtype
-    (``quanto::qbits_mm_a8_q``).  Its forward then gets the output codes from the product kernel's epilogue instead of writing the float output and
-    quantizing it in a second pass - bit-identical codes, same ``output_scale``.  Returns the names of the marked (unmarked) modules.
+    (``quanto::qbits_mm_a8_q``); and every frozen ``QConv2d`` with bf16 / fp16 / fp32 scales and its output hook still registered when it is dense
+    (``groups == 1``) with ``padding_mode == "zeros"`` and numeric padding, has an 8-bit weight qtype and a pair the quantized-activation convolution
+    serves - qint8 x qint8, or qfloat8_e4m3fn / qfloat8_e5m2 activations with a qfloat8_e4m3fn / qfloat8_e5m2 / qint8 weight, but not e5m2 activations
+    with fp16 scales (``quanto::qbytes_conv2d_a8_q``).  Its forward then gets the output codes from the product kernel's epilogue instead of writing
+    the float output and quantizing it in a second pass - bit-identical codes, same ``output_scale``.  Returns the names of the marked (unmarked)
+    Linear and Conv modules in ``named_modules()`` order.
 
     Not automatic: forward hooks registered by the user and calibration passes read a module's float output before its own hook quantizes it; a marked
-    module hands them codes.  Calibrate first, then call this.  ``QConv2d``, sub-byte weights outside that format, fp32 modules and other module classes
-    are never marked; the mark is not saved with the state dict."""
+    module hands them codes.  Calibrate first, then call this.  Sub-byte ``QLinear`` weights outside that format, fp32 ``QLinear`` modules, ``QConv2d``
+    with sub-byte weights, groups, string or non-zero-mode padding, and other module classes are never marked; the mark is not saved with the state dict."""
     names = []
     for name, m in model.named_modules():
-        if type(m) is not QLinear:
+        if type(m) is not QLinear and type(m) is not QConv2d:
             continue
         if not enable:
             if m._fuse_output_quantization:
@@ -193,8 +212,14 @@ def fuse_output_quantization(model: torch.nn.Module, enable: bool = True) -> Lis
                 names.append(name)
             continue
         wq, aq = m.weight_qtype, m.activation_qtype
-        if not (m.frozen and wq is not None and aq is not None and aq.dtype in _FUSED_OUTPUT_DTYPES and "output" in m._quantize_hooks
-                and m.weight._scale.dtype in (torch.bfloat16, torch.float16)):
+        if not (m.frozen and wq is not None and aq is not None and aq.dtype in _FUSED_OUTPUT_DTYPES and "output" in m._quantize_hooks):
+            continue
+        if type(m) is QConv2d:
+            if m.weight._scale.dtype in (torch.bfloat16, torch.float16, torch.float32) and _conv_a8_gate_admits(m):
+                m._fuse_output_quantization = True
+                names.append(name)
+            continue
+        if m.weight._scale.dtype not in (torch.bfloat16, torch.float16):
             continue
         if (wq.bits == 8 and wq.dtype == aq.dtype) or (wq in (qint4, qint2) and _a8_gate_admits(m)):
             m._fuse_output_quantization = True

@@ -13,12 +13,18 @@ both go to the 8-bit matrix instructions, gathered inside the kernel - no dequan
 (integer / fp8 products scaled by ``input_scale * weight_scale``).  Served pairs: int8 x int8, fp8 x fp8 and fp8 x int8.  Int8 activations
 with fp8 weights, e4m3fnuz, int4 / int2 weights, grouped convolutions, fp16 outputs with e5m2 activations and calls that want a gradient
 keep the dequantizing route.
+
+Fused output quantization: a frozen module marked by ``fuse_output_quantization`` (model_api.py) takes its output codes from that kernel's
+epilogue (``quanto::qbytes_conv2d_a8_q``) whenever the call is one ``quanto::qbytes_conv2d_a8`` would serve - the float [B, OC, OH, OW] output
+is never written and the output hook passes the codes through.  Bit-identical to the convolution followed by the hook; every other call
+(CPU tensors, float inputs, a gradient wanted, ``padding_mode != "zeros"``) runs the forward below.
 """
 from typing import Optional
 
 import torch
 
-from ..tensor import Optimizer, qtype
+from ..tensor import ActivationQBytesTensor, Optimizer, WeightQBytesTensor, qtype
+from ..tensor.weights import conv2d_a8_eligible
 from .module import QModuleMixin, register_qmodule
 
 __all__ = ["QConv2d"]
@@ -38,5 +44,23 @@ class QConv2d(QModuleMixin, torch.nn.Conv2d):
                    activations=activations, optimizer=optimizer)
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if self._fuse_output_quantization and self._codes_from_epilogue(input):
+            # marked by fuse_output_quantization: convolution and output quantization in one op (quanto::qbytes_conv2d_a8_q), bit-identical to the
+            # convolution followed by the output hook - which then passes these codes through
+            w = self.weight
+            codes = torch.ops.quanto.qbytes_conv2d_a8_q(input._data, input._scale, w._data, w._scale, self.bias, self.output_scale,
+                                                        list(self.stride), list(self.padding), list(self.dilation))
+            return ActivationQBytesTensor(self.activation_qtype, codes.size(), codes.stride(), codes, self.output_scale)
         # F.conv2d is intercepted by the weight's __torch_function__ (im2col + fused GEMM on a ROCm device)
         return self._conv_forward(input, self.qweight, self.bias)
+
+    def _codes_from_epilogue(self, input) -> bool:
+        """Whether this call is the one the fused op computes: stored codes of the module's own activation qtype against a frozen 8-bit weight, zero
+        padding, the output hook still in place, and a call ``quanto::qbytes_conv2d_a8`` serves (conv2d_a8_eligible: ROCm device, scalar input scale,
+        dense, a served format pair, no gradient wanted - the op has no backward)."""
+        w = self.weight
+        if not (isinstance(input, ActivationQBytesTensor) and input.qtype == self.activation_qtype and type(w) is WeightQBytesTensor):
+            return False
+        if self.padding_mode != "zeros" or "output" not in self._quantize_hooks:
+            return False
+        return conv2d_a8_eligible(input, w, self.bias, self.stride, self.padding, self.dilation, self.groups)

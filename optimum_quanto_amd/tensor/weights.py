@@ -102,26 +102,34 @@ def _implicit_conv2d(input, weight, scale, bias, stride, padding, dilation, grou
     return torch.ops.quanto.qbytes_conv2d(input, weight._data, scale, bias, pair(stride), pair(padding), pair(dilation))
 
 
-def _implicit_conv2d_a8(input, weight, bias, stride, padding, dilation, groups):
-    """``quanto::qbytes_conv2d_a8`` - quantized activation codes x 8-bit weight codes on the 8-bit matrix instructions, im2col inside the kernel's
-    staging loads, no dequantized activation - when the call is eligible: a per-tensor quantized 4-D input (QBytesTensor) on a ROCm device, dense
-    (groups = 1), no gradient wanted, a served (activation, weight) format pair (int8 x int8, fp8 x fp8, fp8 x int8).  None otherwise: the caller
-    keeps today's route (dequantize + im2col + GEMM, or the reference behaviour)."""
+def conv2d_a8_eligible(input, weight, bias, stride, padding, dilation, groups) -> bool:
+    """Whether ``F.conv2d(input, weight, bias, ...)`` is a call the quantized-activation convolution kernel takes (csrc/qconv_a8.hip) - one predicate
+    for ``quanto::qbytes_conv2d_a8`` (_implicit_conv2d_a8) and ``quanto::qbytes_conv2d_a8_q`` (a marked QConv2d): a per-tensor quantized 4-D input
+    (QBytesTensor) on a ROCm device, dense (groups = 1), no string padding, no gradient wanted, a served (activation, weight) format pair (int8 x
+    int8, fp8 x fp8, fp8 x int8)."""
     from ..library.hip import quanto_hip
 
     if groups != 1 or isinstance(padding, str) or not isinstance(input, QBytesTensor) or input.dim() != 4 or input.device.type != "cuda":
-        return None
+        return False
     if input.axis is not None or input._scale.numel() != 1 or weight.dim() != 4:
-        return None
+        return False
     # the op's scale is the product of both scales rounded to the output dtype (the W8A8 QLinear contract); an e5m2 activation scale (absmax / 57344)
     # times a weight scale lies below fp16's normal range (~5e-8 against 6.1e-5) and would lose all or most of its bits: that pair keeps dequantizing
     if input._data.dtype == torch.float8_e5m2 and weight._scale.dtype == torch.float16:
-        return None
+        return False
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, weight, bias)):
+        return False
+    stride, padding, dilation = _pair(stride), _pair(padding), _pair(dilation)
+    return quanto_hip.lib.qbytes_conv2d_a8_supported(input._data, weight._data, weight._scale.dtype, stride, padding, dilation)
+
+
+def _implicit_conv2d_a8(input, weight, bias, stride, padding, dilation, groups):
+    """``quanto::qbytes_conv2d_a8`` - quantized activation codes x 8-bit weight codes on the 8-bit matrix instructions, im2col inside the kernel's
+    staging loads, no dequantized activation - when the call is eligible (conv2d_a8_eligible).  None otherwise: the caller keeps today's route
+    (dequantize + im2col + GEMM, or the reference behaviour)."""
+    if not conv2d_a8_eligible(input, weight, bias, stride, padding, dilation, groups):
         return None
     stride, padding, dilation = _pair(stride), _pair(padding), _pair(dilation)
-    if not quanto_hip.lib.qbytes_conv2d_a8_supported(input._data, weight._data, weight._scale.dtype, stride, padding, dilation):
-        return None
     return torch.ops.quanto.qbytes_conv2d_a8(input._data, input._scale, weight._data, weight._scale, bias, stride, padding, dilation)
 
 
