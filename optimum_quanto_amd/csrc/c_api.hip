@@ -44,9 +44,9 @@ int qdense_conv2d_rows(const void*, const void*, const void*, void*, const ConvG
 // convolution with quantized activations on the 8-bit matrix instructions (qconv_a8.hip)
 int qbytes_conv2d_a8_kind(int, int, int);
 size_t conv2d_a8_workspace(int64_t, int64_t, int64_t);
-int qbytes_conv2d_a8(const void*, const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t, hipStream_t, int*);
-int qbytes_conv2d_a8_q(const void*, const void*, const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t,
-                       hipStream_t, int*);
+// (x, a_scale, w, w_scale, bias, out_scale, y, ...): out_scale == nullptr -> the float output, else the output codes (the three products below alike)
+int qbytes_conv2d_a8(const void*, const void*, const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t,
+                     hipStream_t, int*);
 int qbytes_conv2d_mfma(const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t, hipStream_t, bool* rows);
 int qbytes_mm_gemv_multi(const void*, int, const void* const*, const void* const*, const void* const*, void* const*, const int64_t*, int64_t,
                          int64_t, int, int, hipStream_t);
@@ -63,9 +63,8 @@ bool dense_mm_wd_supported(int64_t, int64_t, int64_t, int);
 int dense_mm_wd(const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, hipStream_t);
 bool qbytes_native8_supported(int64_t, int64_t, int64_t, int, int, int);
 size_t qbytes_native8_workspace(int64_t, int64_t, int64_t, int, int, int);
-int qbytes_mm_native8(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, void*, size_t, hipStream_t);
-int qbytes_mm_native8_q(const void*, const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, void*, size_t,
-                        hipStream_t);
+int qbytes_mm_native8(const void*, const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, void*, size_t,
+                      hipStream_t);
 bool qbits_skinny_multi_supported(int, const int64_t*, int64_t, int64_t, int);
 size_t qbits_skinny_multi_workspace(int, const int64_t*, int64_t, int64_t);
 int qbits_mm_skinny_multi(const void*, int, const uint8_t* const*, const void* const*, const void* const*, const void* const*, void* const*,
@@ -103,10 +102,8 @@ int qbytes_mm_f32(const void*, const void*, const void*, const void*, void*, int
 // quantized activations x int4 / int2 weights (qbits_a8_fused.hip)
 bool qbits_a8_supported(int64_t, const PackedGeom&, int, int);
 size_t qbits_a8_workspace(int64_t, const PackedGeom&);
-int qbits_mm_a8_q(const void*, const void*, const uint8_t*, const void*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, int, bool,
-                  void*, size_t, hipStream_t);
-int qbits_mm_a8(const void*, const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, int, bool, void*, size_t,
-                hipStream_t);
+int qbits_mm_a8(const void*, const void*, const uint8_t*, const void*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, int, bool,
+                void*, size_t, hipStream_t);
 
 static bool is_float_dtype(int dt) { return dt == QUANTO_HIP_F32 || dt == QUANTO_HIP_F16 || dt == QUANTO_HIP_BF16; }
 
@@ -421,44 +418,43 @@ int64_t quanto_hip_qbits_mm_a8_workspace_size(int64_t M, int64_t N, int64_t K, i
   return (int64_t)qbits_a8_workspace(M, g);
 }
 
-int quanto_hip_qbits_mm_a8(const void* a, const void* a_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y,
-                           int64_t M, int64_t N, int64_t K, int bits, int group_size, int a_dtype, int dtype, int shift_dtype, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  bool int_shift = false;
-  const int st = check_qbits(M, N, K, bits, group_size, dtype, shift_dtype, &int_shift);
-  if (st != QUANTO_HIP_OK) return st;
-  if (M == 0) return QUANTO_HIP_OK;
-  if (!a || !a_scale || !packed || !scale || !shift || !y) return QUANTO_HIP_EINVAL;
-  const PackedGeom g = make_geom(N, K, bits, group_size);
-  const int r = qbits_mm_a8(a, a_scale, packed, scale, shift, bias, y, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes,
-                            reinterpret_cast<hipStream_t>(stream));
-  if (r == QUANTO_HIP_OK) {
-    static const char* const names[2][3] = {{"a8_fused_int8", "a8_fused_fp8", "a8_fused_bf8"}, {"a8_fused_int8_w2", "a8_fused_fp8_w2", "a8_fused_bf8_w2"}};
-    set_last_kernel(names[bits == 2][a_dtype == QUANTO_HIP_I8 ? 0 : a_dtype == QUANTO_HIP_F8_E4M3FN ? 1 : 2]);
-  }
-  return r;
-}
-
-// ---- qbits_mm_a8 with the layer's output quantization in the epilogue: the checks of the entry above, every reason not to serve -> ENOTSUP ahead of
-// any look at the data pointers; the plan and the workspace are those of the unfused entry (quanto_hip_qbits_mm_a8_workspace_size) ----
-int quanto_hip_qbits_mm_a8_q(const void* a, const void* a_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
-                             const void* out_scale, void* yq, int64_t M, int64_t N, int64_t K, int bits, int group_size, int a_dtype, int dtype,
+// Both forms of qbits_mm_a8: `codes` = the entry with the layer's output quantization in the epilogue (out_scale, y = a_dtype codes).  The two entries
+// differ in one place, kept: the code form refuses what qbits_a8_supported does not serve ahead of any look at M == 0 and at the data pointers (its
+// caller runs the two-op sequence then); the float form answers OK to M == 0 and leaves that refusal to the launcher.  The plan and the workspace are
+// the same (quanto_hip_qbits_mm_a8_workspace_size).
+static int qbits_mm_a8_entry(bool codes, const void* a, const void* a_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
+                             const void* out_scale, void* y, int64_t M, int64_t N, int64_t K, int bits, int group_size, int a_dtype, int dtype,
                              int shift_dtype, void* workspace, size_t workspace_bytes, void* stream) {
   bool int_shift = false;
   const int st = check_qbits(M, N, K, bits, group_size, dtype, shift_dtype, &int_shift);
   if (st != QUANTO_HIP_OK) return st;
   const PackedGeom g = make_geom(N, K, bits, group_size);
-  if (!qbits_a8_supported(M > 0 ? M : 1, g, a_dtype, dtype)) return QUANTO_HIP_ENOTSUP;
+  if (codes && !qbits_a8_supported(M > 0 ? M : 1, g, a_dtype, dtype)) return QUANTO_HIP_ENOTSUP;
   if (M == 0) return QUANTO_HIP_OK;
-  if (!a || !a_scale || !packed || !scale || !shift || !out_scale || !yq) return QUANTO_HIP_EINVAL;
-  const int r = qbits_mm_a8_q(a, a_scale, packed, scale, shift, bias, out_scale, yq, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes,
-                              reinterpret_cast<hipStream_t>(stream));
+  if (!a || !a_scale || !packed || !scale || !shift || !y || (codes && !out_scale)) return QUANTO_HIP_EINVAL;
+  const int r = qbits_mm_a8(a, a_scale, packed, scale, shift, bias, codes ? out_scale : nullptr, y, M, g, a_dtype, dtype, int_shift, workspace,
+                            workspace_bytes, reinterpret_cast<hipStream_t>(stream));
   if (r == QUANTO_HIP_OK) {
-    static const char* const names[2][3] = {{"a8_fused_int8_q", "a8_fused_fp8_q", "a8_fused_bf8_q"},
-                                            {"a8_fused_int8_w2_q", "a8_fused_fp8_w2_q", "a8_fused_bf8_w2_q"}};
-    set_last_kernel(names[bits == 2][a_dtype == QUANTO_HIP_I8 ? 0 : a_dtype == QUANTO_HIP_F8_E4M3FN ? 1 : 2]);
+    static const char* const names[2][2][3] = {{{"a8_fused_int8", "a8_fused_fp8", "a8_fused_bf8"}, {"a8_fused_int8_w2", "a8_fused_fp8_w2", "a8_fused_bf8_w2"}},
+                                               {{"a8_fused_int8_q", "a8_fused_fp8_q", "a8_fused_bf8_q"},
+                                                {"a8_fused_int8_w2_q", "a8_fused_fp8_w2_q", "a8_fused_bf8_w2_q"}}};
+    set_last_kernel(names[codes][bits == 2][a_dtype == QUANTO_HIP_I8 ? 0 : a_dtype == QUANTO_HIP_F8_E4M3FN ? 1 : 2]);
   }
   return r;
+}
+
+int quanto_hip_qbits_mm_a8(const void* a, const void* a_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y,
+                           int64_t M, int64_t N, int64_t K, int bits, int group_size, int a_dtype, int dtype, int shift_dtype, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  return qbits_mm_a8_entry(false, a, a_scale, packed, scale, shift, bias, nullptr, y, M, N, K, bits, group_size, a_dtype, dtype, shift_dtype, workspace,
+                           workspace_bytes, stream);
+}
+
+int quanto_hip_qbits_mm_a8_q(const void* a, const void* a_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
+                             const void* out_scale, void* yq, int64_t M, int64_t N, int64_t K, int bits, int group_size, int a_dtype, int dtype,
+                             int shift_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  return qbits_mm_a8_entry(true, a, a_scale, packed, scale, shift, bias, out_scale, yq, M, N, K, bits, group_size, a_dtype, dtype, shift_dtype, workspace,
+                           workspace_bytes, stream);
 }
 
 // one streaming-MFMA launch for the whole group pays when the members are small enough to be dominated by per-call costs
@@ -665,7 +661,7 @@ int quanto_hip_qbytes_mm_ws(const void* a, const void* b, const void* scales, co
       name = "mfma_large";
       break;
     case QUANTO_HIP_KERNEL_NATIVE8:
-      r = qbytes_mm_native8(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
+      r = qbytes_mm_native8(a, b, scales, bias, nullptr, y, M, N, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
       name = "mfma_native8";
       break;
   }
@@ -759,8 +755,8 @@ int quanto_hip_qbytes_mm_q_ws(const void* a, const void* b, const void* scales, 
   if (st != QUANTO_HIP_OK) return st;
   if (M == 0) return QUANTO_HIP_OK;
   if (!a || !b || !scales || !out_scale || !yq) return QUANTO_HIP_EINVAL;
-  const int r = qbytes_mm_native8_q(a, b, scales, bias, out_scale, yq, M, N, K, a_dtype, b_dtype, mid_dtype, workspace, workspace_bytes,
-                                    reinterpret_cast<hipStream_t>(stream_));
+  const int r = qbytes_mm_native8(a, b, scales, bias, out_scale, yq, M, N, K, a_dtype, b_dtype, mid_dtype, workspace, workspace_bytes,
+                                  reinterpret_cast<hipStream_t>(stream_));
   if (r == QUANTO_HIP_OK) set_last_kernel("mfma_native8_q");
   return r;
 }
@@ -884,42 +880,42 @@ int64_t quanto_hip_qbytes_conv2d_a8_workspace_size(int64_t B, int64_t cin, int64
   return (int64_t)conv2d_a8_workspace(g.M(), OC, g.K());
 }
 
-int quanto_hip_qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, int64_t B, int64_t cin,
-                                int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
-                                int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes,
-                                void* stream) {
+// Both forms of qbytes_conv2d_a8: `codes` = the entry with the layer's output quantization in the epilogue (out_scale, y = a_dtype codes).  The two
+// entries differ in one place, kept: the code form refuses a geometry beyond conv_geometry_ok ahead of any look at the data pointers; the float form
+// leaves that refusal to the launcher, behind the null checks.  Same plan and workspace.
+static int qbytes_conv2d_a8_entry(bool codes, const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, const void* out_scale,
+                                  void* y, int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW,
+                                  int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
   ConvGeom g;
   const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, &g);
   if (geo != QUANTO_HIP_OK) return geo;
   if (qbytes_conv2d_a8_kind(a_dtype, b_dtype, out_dtype) < 0) return QUANTO_HIP_ENOTSUP;
   if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
-  if (!x || !a_scale || !w || !w_scale || !y) return QUANTO_HIP_EINVAL;
+  if (codes && !conv_geometry_ok(g)) return QUANTO_HIP_ENOTSUP;
+  if (!x || !a_scale || !w || !w_scale || !y || (codes && !out_scale)) return QUANTO_HIP_EINVAL;
   int kind = -1;
-  const int r = qbytes_conv2d_a8(x, a_scale, w, w_scale, bias, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), &kind);
-  static const char* const names[3] = {"conv2d_a8_int8", "conv2d_a8_fp8", "conv2d_a8_fp8_w8"};
-  if (r == QUANTO_HIP_OK) set_last_kernel(names[kind]);
+  const int r = qbytes_conv2d_a8(x, a_scale, w, w_scale, bias, codes ? out_scale : nullptr, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes,
+                                 reinterpret_cast<hipStream_t>(stream), &kind);
+  static const char* const names[2][3] = {{"conv2d_a8_int8", "conv2d_a8_fp8", "conv2d_a8_fp8_w8"}, {"conv2d_a8_int8_q", "conv2d_a8_fp8_q", "conv2d_a8_fp8_w8_q"}};
+  if (r == QUANTO_HIP_OK) set_last_kernel(names[codes][kind]);
   return r;
 }
 
-// the same convolution with the layer's output quantization in the epilogue: the checks of the entry above in its order - format and geometry are
-// refused ahead of any look at the data pointers - then the same plan and workspace
+int quanto_hip_qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, int64_t B, int64_t cin,
+                                int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h, int stride_w, int pad_h,
+                                int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  return qbytes_conv2d_a8_entry(false, x, a_scale, w, w_scale, bias, nullptr, y, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h,
+                                dil_w, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
+}
+
 int quanto_hip_qbytes_conv2d_a8_q(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, const void* out_scale, void* yq,
                                   int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h,
                                   int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int a_dtype, int b_dtype, int mid_dtype, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  ConvGeom g;
-  const int geo = check_conv2d_args(B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, &g);
-  if (geo != QUANTO_HIP_OK) return geo;
-  if (qbytes_conv2d_a8_kind(a_dtype, b_dtype, mid_dtype) < 0) return QUANTO_HIP_ENOTSUP;
-  if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
-  if (!conv_geometry_ok(g)) return QUANTO_HIP_ENOTSUP;
-  if (!x || !a_scale || !w || !w_scale || !out_scale || !yq) return QUANTO_HIP_EINVAL;
-  int kind = -1;
-  const int r = qbytes_conv2d_a8_q(x, a_scale, w, w_scale, bias, out_scale, yq, g, a_dtype, b_dtype, mid_dtype, workspace, workspace_bytes,
-                                   reinterpret_cast<hipStream_t>(stream), &kind);
-  static const char* const names[3] = {"conv2d_a8_int8_q", "conv2d_a8_fp8_q", "conv2d_a8_fp8_w8_q"};
-  if (r == QUANTO_HIP_OK) set_last_kernel(names[kind]);
-  return r;
+  return qbytes_conv2d_a8_entry(true, x, a_scale, w, w_scale, bias, out_scale, yq, B, cin, H, W, OC, KH, KW, OH, OW, stride_h, stride_w, pad_h, pad_w, dil_h,
+                                dil_w, a_dtype, b_dtype, mid_dtype, workspace, workspace_bytes, stream);
 }
 
 int quanto_hip_qbytes_conv2d_depthwise(const void* x, const void* w, const void* scales, const void* bias, void* y, int64_t B, int64_t cin, int64_t H,

@@ -349,17 +349,14 @@ static int mm_a8(const void* act, const void* act_scale, const uint8_t* packed, 
                                   : a8::launch_bits<QUANTO_HIP_F16, QOUT>(a, g.bits, a_dtype, p.bm, int_shift, stream);
 }
 
-int qbits_mm_a8(const void* act, const void* act_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  return mm_a8<false>(act, act_scale, packed, scale, shift, bias, nullptr, y, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes, stream);
-}
-
-// The same product with the output quantization of the layer in its epilogue (gf::epilogue_codes): yq[M, N] = codes in a_dtype of the dtype-rounded
-// product at the per-tensor scale out_scale[0] - bit-identical to quantize_symmetric(qbits_mm_a8(...)).  Same gate, same plan, same workspace.
-int qbits_mm_a8_q(const void* act, const void* act_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
-                  const void* out_scale, void* yq, int64_t M, const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace,
-                  size_t workspace_bytes, hipStream_t stream) {
-  return mm_a8<true>(act, act_scale, packed, scale, shift, bias, out_scale, yq, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes, stream);
+// y = dtype[M, N]; or, with an out_scale, the product with the output quantization of the layer in its epilogue (gf::epilogue_codes): y = a_dtype[M, N]
+// codes of the dtype-rounded product at the per-tensor scale out_scale[0] - bit-identical to quantize_symmetric of the float form.  Same gate, same
+// plan, same workspace.
+int qbits_mm_a8(const void* act, const void* act_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
+                const void* out_scale, void* y, int64_t M, const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace,
+                size_t workspace_bytes, hipStream_t stream) {
+  if (!out_scale) return mm_a8<false>(act, act_scale, packed, scale, shift, bias, nullptr, y, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes, stream);
+  return mm_a8<true>(act, act_scale, packed, scale, shift, bias, out_scale, y, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes, stream);
 }
 
 }  // namespace qh

@@ -121,13 +121,7 @@ __device__ __forceinline__ void store_codes_dt(const Args& a, const AV (&acc)[4]
       if (m >= M) continue;
       float q[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = (float)acc[i][j][r] * sc;
-        asm volatile("" : "+v"(v));  // product rounded to fp32 first, with and without bias (no single-rounding v_fma_mixlo_f16)
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv;  // the reference's order: rounded convolution output + bias, rounded again
-        const T t = E::from_f32(v);  // the element conv_store_tile stores
-        q[r] = clamp_target<ODT>(quotient_in<DT>(E::to_f32(t), os));
-      }
+      for (int r = 0; r < 4; ++r) q[r] = epilogue_code<DT, ODT>((float)acc[i][j][r], sc, has_bias, bv, os);  // of the element conv_store_tile stores
       const uint32_t codes = pack4<ODT>(q);
       if (vec && m + 3 < M) {  // (L % 4 == 0 and m % 4 == 0: the four pixels are in one image, aligned)
         *reinterpret_cast<uint32_t*>(yq + ((size_t)bq[i] * N + n) * L + lq[i]) = codes;
@@ -426,14 +420,12 @@ static int conv2d_a8_run(const void* x, const void* a_scale, const void* w, cons
   return launch_status();
 }
 
-int qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, void* y, const ConvGeom& g, int a_dtype,
-                     int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
-  return conv2d_a8_run<false>(x, a_scale, w, w_scale, bias, nullptr, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream, kind);
-}
-// the same convolution with the layer's output quantization in its epilogue: yq = a_dtype codes of the mid_dtype-rounded output at *out_scale
-int qbytes_conv2d_a8_q(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, const void* out_scale, void* yq,
-                       const ConvGeom& g, int a_dtype, int b_dtype, int mid_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
-  return conv2d_a8_run<true>(x, a_scale, w, w_scale, bias, out_scale, yq, g, a_dtype, b_dtype, mid_dtype, workspace, workspace_bytes, stream, kind);
+// out_scale == nullptr: y = out_dtype[B, OC, OH, OW]; otherwise the same convolution with the layer's output quantization in its epilogue: y = a_dtype
+// codes of the out_dtype-rounded output at *out_scale
+int qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, const void* out_scale, void* y,
+                     const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
+  if (!out_scale) return conv2d_a8_run<false>(x, a_scale, w, w_scale, bias, nullptr, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream, kind);
+  return conv2d_a8_run<true>(x, a_scale, w, w_scale, bias, out_scale, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream, kind);
 }
 
 }  // namespace qh

@@ -182,14 +182,7 @@ __device__ __forceinline__ void epilogue_codes(const f32x4 (&acc)[MI], void* yq,
     if (m < M) {
       float q[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[i][r];
-        v = v * sx;
-        asm volatile("" : "+v"(v));
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[r];
-        const T t = E::from_f32(v);  // the element QH_GF_EPILOGUE stores
-        q[r] = clamp_target<ODT>(quotient_in<DT>(E::to_f32(t), os));
-      }
+      for (int r = 0; r < 4; ++r) q[r] = epilogue_code<DT, ODT>(acc[i][r], sx, has_bias, bv[r], os);  // of the element QH_GF_EPILOGUE stores
       const uint32_t codes = pack4<ODT>(q);
       if (pl + 3 < P) {
         *reinterpret_cast<uint32_t*>(y + (size_t)m * N + n0) = codes;

@@ -1,5 +1,5 @@
-// The per-element rule of quanto::quantize_symmetric (library/quantize.py:26-55), one copy for quantize.hip and for the GEMM epilogue that stores
-// output codes (qmm_native8.hip, n8::epilogue_codes): code = cast(clamp(round?(T(x / scale)))).
+// The per-element rule of quanto::quantize_symmetric (library/quantize.py:26-55), one copy for quantize.hip and for the product epilogues that store
+// output codes (epilogue_code below: qh_group_fused.h, qconv_a8.hip; qmm_native8.hip keeps its statements inline, for its listing): code = cast(clamp(round?(T(x / scale)))).
 //
 // Bit-exactness with the torch sequence: the quotient is an fp32 divide, correctly rounded (no reciprocal multiply), rounded to the tensor dtype T -
 // what aten's div does through its opmath type; integer targets are then rounded half-to-even in T (exact: |q| <= 256 after the clamp matters only)
@@ -40,6 +40,20 @@ template <int IDT>
 __device__ __forceinline__ float quotient_in(float x, float s) {
   using E = Elem<IDT>;
   return E::to_f32(E::from_f32(x / s));
+}
+
+// The output code of a product epilogue, before pack4: the element t the float epilogue would store - accumulator x scale rounded to fp32 in front of
+// anything else (the asm volatile: no single-rounding fused form), rounded to T, the bias added to that, rounded again - then the rule above on t at the
+// output scale os.  DT: the tensor dtype T of the product; ODT: the code type.  The QOUT epilogues are pinned bit for bit against the two-kernel sequence: a
+// rounding fix belongs here and in n8::epilogue_codes (qmm_native8.hip), which holds the same statements inline.
+template <int DT, int ODT>
+__device__ __forceinline__ float epilogue_code(float acc, float scale, bool has_bias, float bias, float os) {
+  using E = Elem<DT>;
+  float v = acc * scale;
+  asm volatile("" : "+v"(v));
+  if (has_bias) v = E::to_f32(E::from_f32(v)) + bias;
+  const typename E::T t = E::from_f32(v);  // the element the float epilogue stores
+  return clamp_target<ODT>(quotient_in<DT>(E::to_f32(t), os));
 }
 
 }  // namespace qh

@@ -115,6 +115,8 @@ __device__ __forceinline__ void epilogue_codes(const Args& a, typename Acc<KIND>
         float q[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
+          // the statements of qh::epilogue_code (qh_quantize.h), inline: as a call this unit's QOUT kernels came out with other registers.  A rounding
+          // fix made there belongs here too.
           float v = (float)acc[j][i][r] * sc[j][r];  // the statements of the epilogue below: fp32 product, rounded to fp32 ...
           asm volatile("" : "+v"(v));                // ... and only then to T
           if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[j][r];
@@ -1049,35 +1051,27 @@ size_t qbytes_native8_workspace(int64_t M, int64_t N, int64_t K, int a_dtype, in
   }
 }
 
-int qbytes_mm_native8(const void* a, const void* b, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
-                      int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!qbytes_native8_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) % 16) return QUANTO_HIP_EALIGN;
-  n8::Args args{{a, reinterpret_cast<const uint8_t*>(b), s, bias, y, (int)M, (int)N, (int)K, n8::raster_group(), 1, nullptr, nullptr}, 0};
-#define QH_KIND(ODT)                                                                  \
-  if (a_dtype == QUANTO_HIP_I8) return n8::launch<ODT, n8::K_I8>(args, workspace, workspace_bytes, stream);       \
-  if (a_dtype == QUANTO_HIP_F8_E4M3FN) return n8::launch<ODT, n8::K_F8E4M3>(args, workspace, workspace_bytes, stream); \
-  return n8::launch<ODT, n8::K_F8E5M2>(args, workspace, workspace_bytes, stream)
-  if (out_dtype == QUANTO_HIP_BF16) { QH_KIND(QUANTO_HIP_BF16); }
-  if (out_dtype == QUANTO_HIP_F16) { QH_KIND(QUANTO_HIP_F16); }
-  QH_KIND(QUANTO_HIP_F32);
-#undef QH_KIND
-}
-
-// The same product with the output quantization of the layer in its epilogue (n8::epilogue_codes): yq[M, N] = codes in a_dtype of the mid_dtype-rounded
-// product at the per-tensor scale out_scale[0] - bit-identical to quantize_symmetric(qbytes_mm_native8(...)).  Serves what qbytes_native8_supported serves with
-// a 16-bit mid_dtype; plan, split and workspace are those of qbytes_mm_native8 (the planner does not look at the output).
-int qbytes_mm_native8_q(const void* a, const void* b, const void* s, const void* bias, const void* out_scale, void* yq, int64_t M, int64_t N, int64_t K,
-                        int a_dtype, int b_dtype, int mid_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!qbytes_native8_supported(M, N, K, a_dtype, b_dtype, mid_dtype) || mid_dtype == QUANTO_HIP_F32) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(yq)) % 16) return QUANTO_HIP_EALIGN;
-  n8::Args args{{a, reinterpret_cast<const uint8_t*>(b), s, bias, yq, (int)M, (int)N, (int)K, n8::raster_group(), 1, nullptr, nullptr}, 0, out_scale};
-#define QH_KIND(ODT)                                                                                                          \
-  if (a_dtype == QUANTO_HIP_I8) return n8::launch<ODT, n8::K_I8, true>(args, workspace, workspace_bytes, stream);             \
-  if (a_dtype == QUANTO_HIP_F8_E4M3FN) return n8::launch<ODT, n8::K_F8E4M3, true>(args, workspace, workspace_bytes, stream);  \
-  return n8::launch<ODT, n8::K_F8E5M2, true>(args, workspace, workspace_bytes, stream)
-  if (mid_dtype == QUANTO_HIP_BF16) { QH_KIND(QUANTO_HIP_BF16); }
-  QH_KIND(QUANTO_HIP_F16);
+// out_scale == nullptr: y = out_dtype[M, N].  Otherwise the same product with the output quantization of the layer in its epilogue (n8::epilogue_codes):
+// y[M, N] = codes in a_dtype of the out_dtype-rounded product at the per-tensor scale out_scale[0], 16-byte aligned - bit-identical to quantize_symmetric
+// of the float form.  Serves what qbytes_native8_supported serves with a 16-bit out_dtype; plan, split and workspace are those of the float form (the
+// planner does not look at the output).
+int qbytes_mm_native8(const void* a, const void* b, const void* s, const void* bias, const void* out_scale, void* y, int64_t M, int64_t N, int64_t K,
+                      int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const bool codes = out_scale != nullptr;
+  if (!qbytes_native8_supported(M, N, K, a_dtype, b_dtype, out_dtype) || (codes && out_dtype == QUANTO_HIP_F32)) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | (codes ? reinterpret_cast<uintptr_t>(y) : 0)) % 16) return QUANTO_HIP_EALIGN;
+  n8::Args args{{a, reinterpret_cast<const uint8_t*>(b), s, bias, y, (int)M, (int)N, (int)K, n8::raster_group(), 1, nullptr, nullptr}, 0, out_scale};
+#define QH_KIND(ODT, QOUT)                                                                                                    \
+  if (a_dtype == QUANTO_HIP_I8) return n8::launch<ODT, n8::K_I8, QOUT>(args, workspace, workspace_bytes, stream);             \
+  if (a_dtype == QUANTO_HIP_F8_E4M3FN) return n8::launch<ODT, n8::K_F8E4M3, QOUT>(args, workspace, workspace_bytes, stream);  \
+  return n8::launch<ODT, n8::K_F8E5M2, QOUT>(args, workspace, workspace_bytes, stream)
+  if (!codes) {
+    if (out_dtype == QUANTO_HIP_BF16) { QH_KIND(QUANTO_HIP_BF16, false); }
+    if (out_dtype == QUANTO_HIP_F16) { QH_KIND(QUANTO_HIP_F16, false); }
+    QH_KIND(QUANTO_HIP_F32, false);
+  }
+  if (out_dtype == QUANTO_HIP_BF16) { QH_KIND(QUANTO_HIP_BF16, true); }
+  QH_KIND(QUANTO_HIP_F16, true);
 #undef QH_KIND
 }
 

@@ -593,64 +593,53 @@ class _Bindings:
     def qbits_mm_a8(self, a, a_scale, packed, scale, shift, bias, bits: int, group_size, out_features: int, in_features: int):
         """F.linear(quantized activation, int4 / int2 weight) on the 8-bit matrix instructions: ``a`` int8 / float8_e4m3fn / float8_e5m2 [..., K], ``a_scale`` its
         per-tensor scale (one element).  Raises QuantoHipError(ENOTSUP) for formats the kernel does not take."""
-        if not (a.is_cuda and a_scale.is_cuda and packed.is_cuda and scale.is_cuda and shift.is_cuda and (bias is None or bias.is_cuda)):
-            raise QuantoHipError("quanto_hip kernels only accept tensors on a ROCm device")
-        if a.dim() == 0 or a.shape[-1] != in_features:
-            raise QuantoHipError(f"qbits_mm_a8: input of shape {tuple(a.shape)} does not end in in_features = {in_features}")
-        if a_scale.numel() != 1:
-            raise QuantoHipError("qbits_mm_a8 expects a per-tensor activation scale")
-        sdt = scale.dtype
-        a2 = a if a.dim() == 2 and a.is_contiguous() else a.reshape(-1, in_features).contiguous()
-        a_scale = a_scale.reshape(1).to(sdt).contiguous()
-        packed, scale, shift = packed.contiguous(), scale.contiguous(), shift.contiguous()
-        if bias is not None:
-            bias = bias.to(sdt).contiguous()
-        M = a2.shape[0]
-        ws_bytes = self.qbits_mm_a8_workspace(M, out_features, in_features, bits, group_size, a2.dtype, sdt)
-        if ws_bytes < 0:
-            self._check(int(ws_bytes), "qbits_mm_a8")
-        y = torch.empty((M, out_features), dtype=sdt, device=a.device)
-        with _DeviceGuard(a.device) as stream:
-            wp = self._zeroed_workspace(a.device, ws_bytes, stream).data_ptr() if ws_bytes > 0 else 0
-            st = self._c.quanto_hip_qbits_mm_a8(a2.data_ptr(), a_scale.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                0 if bias is None else bias.data_ptr(), y.data_ptr(), M, out_features, in_features, bits,
-                                                group_size or 0, _DTYPES[a2.dtype], _DTYPES[sdt], _dt(shift), wp, ws_bytes, stream)
-        if st != 0:
-            self._check(st, "qbits_mm_a8")
-        return y if a.dim() == 2 else y.reshape(*a.shape[:-1], out_features)
+        return self._qbits_mm_a8("qbits_mm_a8", a, a_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features)
 
-    # -- quanto::qbits_mm_a8_q ----------------------------------------------------------------------
     def qbits_mm_a8_q(self, a, a_scale, packed, scale, shift, bias, out_scale, bits: int, group_size, out_features: int, in_features: int, _out=None):
         """``quantize_symmetric(qbits_mm_a8(a, ...), a.dtype, None, out_scale)`` in one launch (csrc/qbits_a8_fused.hip, the epilogue that stores codes):
         the same plan cache, zeroed workspace and device guard as ``qbits_mm_a8``.  Raises QuantoHipError for what the library does not serve
         (QUANTO_HIP_ENOTSUP) or a misaligned view (QUANTO_HIP_EALIGN): ``ops.qbits_mm_a8_q_hip`` asks first and runs the two ops then.
         ``_out`` (tests): a contiguous [M, out_features] buffer of ``a.dtype`` to store into."""
-        if not (a.is_cuda and a_scale.is_cuda and packed.is_cuda and scale.is_cuda and shift.is_cuda and out_scale.is_cuda and (bias is None or bias.is_cuda)):
+        return self._qbits_mm_a8("qbits_mm_a8_q", a, a_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features, out_scale, _out)
+
+    def _qbits_mm_a8(self, what, a, a_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features, out_scale=None, _out=None):
+        """The one host path of both entries: ``out_scale`` None -> the float output in the scales' dtype, else the codes in ``a.dtype``."""
+        if not (a.is_cuda and a_scale.is_cuda and packed.is_cuda and scale.is_cuda and shift.is_cuda and (bias is None or bias.is_cuda)
+                and (out_scale is None or out_scale.is_cuda)):
             raise QuantoHipError("quanto_hip kernels only accept tensors on a ROCm device")
         if a.dim() == 0 or a.shape[-1] != in_features:
-            raise QuantoHipError(f"qbits_mm_a8_q: input of shape {tuple(a.shape)} does not end in in_features = {in_features}")
-        if a_scale.numel() != 1 or out_scale.numel() != 1:
-            raise QuantoHipError("qbits_mm_a8_q expects per-tensor activation and output scales")
+            raise QuantoHipError(f"{what}: input of shape {tuple(a.shape)} does not end in in_features = {in_features}")
+        if a_scale.numel() != 1 or (out_scale is not None and out_scale.numel() != 1):
+            raise QuantoHipError(f"{what} expects a per-tensor activation scale" + ("" if out_scale is None else " and a per-tensor output scale"))
         sdt = scale.dtype
         a2 = a if a.dim() == 2 and a.is_contiguous() else a.reshape(-1, in_features).contiguous()
         a_scale = a_scale.reshape(1).to(sdt).contiguous()
-        out_scale = out_scale.reshape(1).to(sdt).contiguous()  # what quantize_symmetric does with a scale of another dtype
         packed, scale, shift = packed.contiguous(), scale.contiguous(), shift.contiguous()
         if bias is not None:
             bias = bias.to(sdt).contiguous()
         M = a2.shape[0]
         ws_bytes = self.qbits_mm_a8_workspace(M, out_features, in_features, bits, group_size, a2.dtype, sdt)
         if ws_bytes < 0:
-            self._check(int(ws_bytes), "qbits_mm_a8_q")
-        yq = torch.empty((M, out_features), dtype=a2.dtype, device=a.device) if _out is None else _out
+            self._check(int(ws_bytes), what)
+        if out_scale is None:
+            y = torch.empty((M, out_features), dtype=sdt, device=a.device)
+        else:
+            out_scale = out_scale.reshape(1).to(sdt).contiguous()  # what quantize_symmetric does with a scale of another dtype
+            y = torch.empty((M, out_features), dtype=a2.dtype, device=a.device) if _out is None else _out
+        bp = 0 if bias is None else bias.data_ptr()
         with _DeviceGuard(a.device) as stream:
             wp = self._zeroed_workspace(a.device, ws_bytes, stream).data_ptr() if ws_bytes > 0 else 0
-            st = self._c.quanto_hip_qbits_mm_a8_q(a2.data_ptr(), a_scale.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                  0 if bias is None else bias.data_ptr(), out_scale.data_ptr(), yq.data_ptr(), M, out_features,
-                                                  in_features, bits, group_size or 0, _DTYPES[a2.dtype], _DTYPES[sdt], _dt(shift), wp, ws_bytes, stream)
+            if out_scale is None:
+                st = self._c.quanto_hip_qbits_mm_a8(a2.data_ptr(), a_scale.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), bp, y.data_ptr(),
+                                                    M, out_features, in_features, bits, group_size or 0, _DTYPES[a2.dtype], _DTYPES[sdt], _dt(shift), wp,
+                                                    ws_bytes, stream)
+            else:
+                st = self._c.quanto_hip_qbits_mm_a8_q(a2.data_ptr(), a_scale.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), bp,
+                                                      out_scale.data_ptr(), y.data_ptr(), M, out_features, in_features, bits, group_size or 0,
+                                                      _DTYPES[a2.dtype], _DTYPES[sdt], _dt(shift), wp, ws_bytes, stream)
         if st != 0:
-            self._check(st, "qbits_mm_a8_q")
-        return yq if a.dim() == 2 else yq.reshape(*a.shape[:-1], out_features)
+            self._check(st, what)
+        return y if a.dim() == 2 else y.reshape(*a.shape[:-1], out_features)
 
     # -- quanto::qbits_mm_multi ---------------------------------------------------------------------
     MAX_MULTI = 4  # QUANTO_HIP_MAX_MULTI
@@ -736,29 +725,35 @@ class _Bindings:
         return self._multi_launch("qbytes_mm_multi", self._c.quanto_hip_qbytes_mm_multi_ws, a2, lead, lists, out_features,
                                   (_dt(a2), _dt(weights[0]), _dt(scales[0])), ws_bytes)
 
-    # -- quanto::qbytes_mm --------------------------------------------------------------------------
-    def qbytes_mm(self, a, b, scales, bias=None, kernel: str = "auto"):
-        if not (a.is_cuda and b.is_cuda and scales.is_cuda and (bias is None or bias.is_cuda)):
+    # -- quanto::qbytes_mm / quanto::qbytes_mm_q ------------------------------------------------------
+    @staticmethod
+    def _qbytes_mm_operands(what, a, b, scales, bias, out_scale=None):
+        """What both products check and normalise: (a2 [M, K], b, scales [N], bias, M, N, K, (a, b, scales) dtype codes) - every tensor on the device, one scale
+        per output feature, ``a`` ending in K, float activations of another 16 / 32-bit dtype cast to the scales' (library/qbytes_mm.py:26)."""
+        if not (a.is_cuda and b.is_cuda and scales.is_cuda and (bias is None or bias.is_cuda) and (out_scale is None or out_scale.is_cuda)):
             raise QuantoHipError("quanto_hip kernels only accept tensors on a ROCm device")
         N, K = b.shape
         if scales.numel() != N:
-            raise QuantoHipError(f"qbytes_mm expects one scale per output feature ({N}), got {tuple(scales.shape)}")
+            raise QuantoHipError(f"{what} expects one scale per output feature ({N}), got {tuple(scales.shape)}")
         if a.dim() == 0 or a.shape[-1] != K:  # torch.matmul's shape error in the reference; here the kernel would read past the buffer
-            raise QuantoHipError(f"qbytes_mm: input of shape {tuple(a.shape)} does not end in in_features = {K}")
+            raise QuantoHipError(f"{what}: input of shape {tuple(a.shape)} does not end in in_features = {K}")
         sdt = scales.dtype
         if a.dtype.is_floating_point and a.dtype.itemsize > 1 and a.dtype != sdt:
-            a = a.to(sdt)  # library/qbytes_mm.py:26
+            a = a.to(sdt)
         a2 = a if a.dim() == 2 and a.is_contiguous() else a.reshape(-1, K).contiguous()
         if not b.is_contiguous():
             b = b.contiguous()
         s = scales if scales.dim() == 1 and scales.is_contiguous() else scales.reshape(-1).contiguous()
         if bias is not None and (bias.dtype != sdt or not bias.is_contiguous()):
             bias = bias.to(sdt).contiguous()
-        M = a2.shape[0]
         adt, bdt, odt = _DTYPES.get(a2.dtype), _DTYPES.get(b.dtype), _DTYPES.get(sdt)
         if adt is None or bdt is None or odt is None:
-            raise QuantoHipError(f"quanto_hip: unsupported dtype in qbytes_mm({a2.dtype}, {b.dtype}, {sdt})")
-        y = torch.empty((M, N), dtype=sdt, device=a.device)
+            raise QuantoHipError(f"quanto_hip: unsupported dtype in {what}({a2.dtype}, {b.dtype}, {sdt})")
+        return a2, b, s, bias, a2.shape[0], N, K, adt, bdt, odt
+
+    def qbytes_mm(self, a, b, scales, bias=None, kernel: str = "auto"):
+        a2, b, s, bias, M, N, K, adt, bdt, odt = self._qbytes_mm_operands("qbytes_mm", a, b, scales, bias)
+        y = torch.empty((M, N), dtype=s.dtype, device=a.device)
         c = self._c
         k, ws_bytes = self._plan("qbytes_mm", (M, N, K, adt, bdt, odt, kernel),
                                  lambda: self._ask(c.quanto_hip_qbytes_mm_plan, M, N, K, adt, bdt, odt, KERNELS[kernel]))
@@ -773,49 +768,39 @@ class _Bindings:
             self._check(st, "qbytes_mm")
         return y if a.dim() == 2 else y.reshape(*a.shape[:-1], N)
 
-    # -- quanto::qbytes_mm_q ------------------------------------------------------------------------
-    def qbytes_mm_q(self, a, b, scales, bias, out_scale):
+    def qbytes_mm_q_workspace(self, M: int, N: int, K: int, a_dtype, b_dtype, dtype) -> int:
+        """Split-K scratch bytes of the code-storing W8A8 kernel for this call shape, or a negative status when the library does not serve it
+        (QUANTO_HIP_ENOTSUP: fp32 scales, mixed operand dtypes, K not a multiple of 64, the size limits): the caller then runs the two ops.  The
+        counterpart of ``qbits_mm_a8_workspace``: the status is kept as the answer, not raised.  The plan entry has one route - its kernel is
+        NATIVE8 by construction (csrc/c_api.hip, quanto_hip_qbytes_mm_q_plan plans with it whatever it is asked) - so the cached plan is
+        (NATIVE8, bytes or status) and the launch names that kernel itself."""
+        def ask():  # (on a miss of the plan cache only: the key holds the torch dtypes)
+            adt, bdt, odt = _DTYPES.get(a_dtype), _DTYPES.get(b_dtype), _DTYPES.get(dtype)
+            if adt is None or bdt is None or odt is None:
+                return 0, KERNEL_NATIVE8, -2
+            st, _, ws = self._ask(self._c.quanto_hip_qbytes_mm_q_plan, M, N, K, adt, bdt, odt, KERNEL_AUTO)
+            return 0, KERNEL_NATIVE8, ws if st == 0 else st
+
+        return self._plan("qbytes_mm_q", (M, N, K, a_dtype, b_dtype, dtype), ask)[1]
+
+    def qbytes_mm_q(self, a, b, scales, bias, out_scale, _ws_bytes=None):
         """``quantize_symmetric(qbytes_mm_bias(a, b, scales, bias), a.dtype, None, out_scale)`` in one launch (csrc/qmm_native8.hip, the epilogue that
-        stores codes), or None when the library does not serve the call (QUANTO_HIP_ENOTSUP: fp32 scales, mixed operand dtypes, K not a multiple of 64,
-        the size limits) or a view is misaligned: the caller then runs the two ops."""
-        if not (a.is_cuda and b.is_cuda and scales.is_cuda and out_scale.is_cuda and (bias is None or bias.is_cuda)):
-            raise QuantoHipError("quanto_hip kernels only accept tensors on a ROCm device")
-        N, K = b.shape
-        if scales.numel() != N:
-            raise QuantoHipError(f"qbytes_mm_q expects one scale per output feature ({N}), got {tuple(scales.shape)}")
-        if a.dim() == 0 or a.shape[-1] != K:
-            raise QuantoHipError(f"qbytes_mm_q: input of shape {tuple(a.shape)} does not end in in_features = {K}")
+        stores codes).  Raises QuantoHipError for what the library does not serve (QUANTO_HIP_ENOTSUP) or a misaligned view (QUANTO_HIP_EALIGN):
+        ``ops.qbytes_mm_q_hip`` asks first and runs the two ops then.  ``_ws_bytes``: the answer of ``qbytes_mm_q_workspace`` for this call when
+        the caller has it already (the op: one plan-cache lookup per call, not two)."""
+        a2, b, s, bias, M, N, K, adt, bdt, odt = self._qbytes_mm_operands("qbytes_mm_q", a, b, scales, bias, out_scale)
         if out_scale.numel() != 1:
             raise QuantoHipError("qbytes_mm_q: the output scale is per-tensor (one element)")
-        sdt = scales.dtype
-        adt, bdt, odt = _DTYPES.get(a.dtype), _DTYPES.get(b.dtype), _DTYPES.get(sdt)
-        if adt is None or bdt is None or odt is None or a.dtype.itemsize != 1:
-            return None
-        a2 = a if a.dim() == 2 and a.is_contiguous() else a.reshape(-1, K).contiguous()
-        if not b.is_contiguous():
-            b = b.contiguous()
-        s = scales if scales.dim() == 1 and scales.is_contiguous() else scales.reshape(-1).contiguous()
-        if bias is not None and (bias.dtype != sdt or not bias.is_contiguous()):
-            bias = bias.to(sdt).contiguous()
-        if out_scale.dtype != sdt:
-            out_scale = out_scale.to(sdt)  # what quantize_symmetric does with a scale of another dtype
-        M = a2.shape[0]
-        c = self._c
-        st, k, ws_bytes = 0, KERNEL_NATIVE8, 0
-        try:
-            k, ws_bytes = self._plan("qbytes_mm_q", (M, N, K, adt, bdt, odt),
-                                     lambda: self._ask(c.quanto_hip_qbytes_mm_q_plan, M, N, K, adt, bdt, odt, KERNEL_AUTO))
-        except QuantoHipError:
-            return None  # not served (the plan entry applies the rule of the launch entry)
-        yq = torch.empty((M, N), dtype=a.dtype, device=a.device)
-        if M == 0:
-            return yq.reshape(*a.shape[:-1], N)
-        if (a2.data_ptr() | b.data_ptr() | yq.data_ptr()) % 16:
-            return None
+        if out_scale.dtype != s.dtype:
+            out_scale = out_scale.to(s.dtype)  # what quantize_symmetric does with a scale of another dtype
+        ws_bytes = self.qbytes_mm_q_workspace(M, N, K, a2.dtype, b.dtype, s.dtype) if _ws_bytes is None else _ws_bytes
+        if ws_bytes < 0:
+            self._check(int(ws_bytes), "qbytes_mm_q")
+        yq = torch.empty((M, N), dtype=a2.dtype, device=a.device)
         with _DeviceGuard(a.device) as stream:
             wp = self._zeroed_workspace(a.device, ws_bytes, stream).data_ptr() if ws_bytes > 0 else 0  # split-K arrival counters: zero on entry, left zero
-            st = c.quanto_hip_qbytes_mm_q_ws(a2.data_ptr(), b.data_ptr(), s.data_ptr(), 0 if bias is None else bias.data_ptr(), out_scale.data_ptr(),
-                                             yq.data_ptr(), M, N, K, adt, bdt, odt, k, wp, max(ws_bytes, 0), stream)
+            st = self._c.quanto_hip_qbytes_mm_q_ws(a2.data_ptr(), b.data_ptr(), s.data_ptr(), 0 if bias is None else bias.data_ptr(), out_scale.data_ptr(),
+                                                   yq.data_ptr(), M, N, K, adt, bdt, odt, KERNEL_NATIVE8, wp, ws_bytes, stream)
         if st != 0:
             self._check(st, "qbytes_mm_q")
         return yq if a.dim() == 2 else yq.reshape(*a.shape[:-1], N)

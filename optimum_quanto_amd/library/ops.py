@@ -147,21 +147,44 @@ _register("qbytes_mm", "(Tensor A, Tensor B, Tensor scales) -> Tensor", qbytes_m
 _register("qbytes_mm_bias", "(Tensor A, Tensor B, Tensor scales, Tensor? bias) -> Tensor", qbytes_mm_bias_hip, default=qbytes_mm_bias_default)
 
 
+def _requantize_output(out, dtype, out_scale):
+    """The second op of every ``*_q`` sequence (nn/qmodule.py:281-299): the float output re-quantized per-tensor to the activations' own 8-bit dtype."""
+    return torch.ops.quanto.quantize_symmetric(out, dtype, None, out_scale.to(out.dtype).reshape(()))
+
+
+# The three ``*_q`` ops below have one shape on a ROCm device: a predicate answers "this call goes to the code-storing kernel" - then the binding is
+# called, which raises for what the library does not serve - otherwise the two-op sequence (``*_q_default``) runs on the existing ops: the caller
+# always gets the sequence's codes.
 def qbytes_mm_q_default(activations, weights, output_scales, bias, out_scale):
-    """The two-op sequence of a quantized-activation layer (tensor/weights/qbytes.py:72-81, then nn/qmodule.py:281-299): the product in the scales' dtype,
-    re-quantized per-tensor to the activations' own 8-bit dtype."""
-    out = torch.ops.quanto.qbytes_mm_bias(activations, weights, output_scales, bias)
-    return torch.ops.quanto.quantize_symmetric(out, activations.dtype, None, out_scale.to(out.dtype).reshape(()))
+    """The two-op sequence of a quantized-activation layer (tensor/weights/qbytes.py:72-81, then the output hook): the product in the scales' dtype."""
+    return _requantize_output(torch.ops.quanto.qbytes_mm_bias(activations, weights, output_scales, bias), activations.dtype, out_scale)
+
+
+def _w8a8_codes_kernel_takes(activations, weights, output_scales, out_scale) -> int:
+    """The predicate of ``qbytes_mm_q_hip``: the split-K workspace bytes (>= 0) when this call goes to the code-storing W8A8 kernel
+    (csrc/qmm_native8.hip), negative otherwise.  Taken: one scale per feature of a 2-D weight, a scalar output scale, 1-byte activations, a served call
+    shape (fp32 scales, mixed operand dtypes, K not a multiple of 64 and the size limits are not), and contiguous views of both operands that start on a
+    16-byte boundary (a non-contiguous operand is copied by the binding and therefore aligned).  An activation that does not end in K also goes to the
+    binding: for its shape error, as in the float product."""
+    if not (weights.ndim == 2 and output_scales.numel() == weights.shape[0] and out_scale.numel() == 1):
+        return -1
+    n, k = weights.shape
+    if activations.ndim == 0 or activations.shape[-1] != k:
+        return 0
+    if activations.dtype.itemsize != 1 or k == 0:
+        return -1
+    if (activations.data_ptr() | weights.data_ptr()) % 16 and (
+            (activations.is_contiguous() and activations.data_ptr() % 16) or (weights.is_contiguous() and weights.data_ptr() % 16)):
+        return -1
+    return quanto_hip.lib.qbytes_mm_q_workspace(activations.numel() // k, n, k, activations.dtype, weights.dtype, output_scales.dtype)
 
 
 def qbytes_mm_q_hip(activations, weights, output_scales, bias, out_scale):
-    """ROCm: the product kernel's epilogue stores the codes (csrc/qmm_native8.hip); what the library does not serve (ENOTSUP) and misaligned views run the
-    two-op sequence on the existing kernels - the caller always gets codes."""
-    n = weights.shape[0]
-    if weights.ndim == 2 and output_scales.numel() == n and out_scale.numel() == 1:
-        out = quanto_hip.lib.qbytes_mm_q(activations, weights, output_scales, bias, out_scale)
-        if out is not None:
-            return out
+    """ROCm: the product kernel's epilogue stores the codes (csrc/qmm_native8.hip) when the predicate says so; every other call runs the two-op sequence
+    on the existing kernels - the caller always gets codes."""
+    ws_bytes = _w8a8_codes_kernel_takes(activations, weights, output_scales, out_scale)
+    if ws_bytes >= 0:
+        return quanto_hip.lib.qbytes_mm_q(activations, weights, output_scales, bias, out_scale, _ws_bytes=ws_bytes)
     return qbytes_mm_q_default(activations, weights, output_scales, bias, out_scale)
 
 
@@ -210,15 +233,14 @@ _register("qbytes_conv2d_a8", "(Tensor input, Tensor input_scale, Tensor weight,
 
 
 def qbytes_conv2d_a8_q_default(input, input_scale, weight, weight_scale, bias, out_scale, stride, padding, dilation):
-    """The two-op sequence of a QConv2d with quantized activations: the convolution in the weight scale's dtype, re-quantized per-tensor to the
-    activations' own 8-bit dtype (nn/qmodule.py:281-299)."""
+    """The two-op sequence of a QConv2d with quantized activations: the convolution in the weight scale's dtype, then the output hook."""
     out = torch.ops.quanto.qbytes_conv2d_a8(input, input_scale, weight, weight_scale, bias, stride, padding, dilation)
-    return torch.ops.quanto.quantize_symmetric(out, input.dtype, None, out_scale.to(out.dtype).reshape(()))
+    return _requantize_output(out, input.dtype, out_scale)
 
 
 def qbytes_conv2d_a8_q_hip(input, input_scale, weight, weight_scale, bias, out_scale, stride, padding, dilation):
-    """ROCm: the convolution kernel's epilogue stores the codes (csrc/qconv_a8.hip) exactly when ``qbytes_conv2d_a8_hip`` takes that kernel; everything
-    else runs the two-op sequence on the existing ops - the caller always gets codes."""
+    """ROCm: the convolution kernel's epilogue stores the codes (csrc/qconv_a8.hip) exactly when ``qbytes_conv2d_a8_hip`` takes that kernel and the
+    output scale is a scalar; every other call runs the two-op sequence on the existing ops - the caller always gets codes."""
     lib = quanto_hip.lib
     stride, padding, dilation = tuple(stride), tuple(padding), tuple(dilation)
     if (input_scale.numel() == 1 and out_scale.numel() == 1
@@ -406,18 +428,18 @@ _register("qbits_mm_a8", "(Tensor input, Tensor input_scale, Tensor packed, Tens
 
 def qbits_mm_a8_q_default(input, input_scale, packed, scale, shift, bias, out_scale, bits: int, group_size: Optional[int], out_features: int,
                           in_features: int):
-    """The two-op sequence of a W4A8 / W2A8 layer (quanto::qbits_mm_a8, then nn/qmodule.py:281-299): the product in the scales' dtype, re-quantized
-    per-tensor to the activation's own 8-bit dtype."""
+    """The two-op sequence of a W4A8 / W2A8 layer: quanto::qbits_mm_a8 in the scales' dtype, then the output hook."""
     out = torch.ops.quanto.qbits_mm_a8(input, input_scale, packed, scale, shift, bias, bits, group_size, out_features, in_features)
-    return torch.ops.quanto.quantize_symmetric(out, input.dtype, None, out_scale.to(out.dtype).reshape(()))
+    return _requantize_output(out, input.dtype, out_scale)
 
 
 def qbits_mm_a8_q_hip(input, input_scale, packed, scale, shift, bias, out_scale, bits: int, group_size: Optional[int], out_features: int,
                       in_features: int):
-    """ROCm: the a8 kernel's epilogue stores the codes exactly when quanto::qbits_mm_a8 runs that kernel for this call (_a8_kernel_takes).  Every other
-    call - up to 64 rows, beyond the tile cap, formats the kernel does not take (QUANTO_HIP_ENOTSUP), a misaligned view of the codes - runs the two-op
-    sequence on the existing ops: the caller always gets the sequence's codes.  (A contiguous view of the codes that does not start on a 16-byte boundary is
-    copied for the sequence: the a8 kernel of quanto::qbits_mm_a8 answers QUANTO_HIP_EALIGN to it; non-contiguous views are copied by the bindings anyway.)"""
+    """ROCm: the a8 kernel's epilogue stores the codes exactly when quanto::qbits_mm_a8 runs that kernel for this call (_a8_kernel_takes: not up to 64
+    rows, beyond the tile cap, or formats the kernel does not take), the output scale is a scalar and the view of the codes is aligned; every other call
+    runs the two-op sequence on the existing ops - the caller always gets codes.  (A contiguous view of the codes that does not start on a 16-byte
+    boundary is copied for the sequence: the a8 kernel of quanto::qbits_mm_a8 answers QUANTO_HIP_EALIGN to it; non-contiguous views are copied by the
+    bindings anyway.)"""
     misaligned = input.is_contiguous() and input.data_ptr() % 16 != 0
     if out_scale.numel() == 1 and not misaligned and _a8_kernel_takes(input, input_scale, scale, bits, group_size, out_features, in_features):
         return quanto_hip.lib.qbits_mm_a8_q(input, input_scale, packed, scale, shift, bias, out_scale, bits, group_size, out_features, in_features)

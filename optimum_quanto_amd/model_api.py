@@ -6,7 +6,7 @@ import torch
 
 from .nn import QConv2d, QLinear, QModuleMixin, quantize_module
 from .tensor import Optimizer, QTensor, WeightQBitsTensor, WeightQBytesTensor, qint2, qint4, qtype
-from .tensor.weights import _fusable
+from .tensor.weights import _fusable, conv2d_a8_scales_underflow
 
 __all__ = ["quantize", "freeze", "requantize", "quantization_map", "fuse_output_quantization"]
 
@@ -175,14 +175,14 @@ def _a8_gate_admits(m: QLinear) -> bool:
 def _conv_a8_gate_admits(m: QConv2d) -> bool:
     """The layers ``quanto::qbytes_conv2d_a8_q`` serves (csrc/qconv_a8.hip): dense, zero padding given as numbers, an 8-bit weight, and a served
     (activation, weight) pair - qint8 x qint8, or qfloat8_e4m3fn / qfloat8_e5m2 activations x qfloat8_e4m3fn / qfloat8_e5m2 / qint8 weights, except
-    e5m2 activations with fp16 scales (their scale product underflows fp16: tensor/weights.py, conv2d_a8_eligible)."""
+    e5m2 activations with fp16 scales (tensor/weights.py, conv2d_a8_scales_underflow)."""
     wq, aq = m.weight_qtype, m.activation_qtype
     if wq.bits != 8 or m.groups != 1 or m.padding_mode != "zeros" or isinstance(m.padding, str) or not isinstance(m.weight, WeightQBytesTensor):
         return False
     fp8 = (torch.float8_e4m3fn, torch.float8_e5m2)
     if aq.dtype == torch.int8:
         return wq.dtype == torch.int8
-    if aq.dtype == torch.float8_e5m2 and m.weight._scale.dtype == torch.float16:
+    if conv2d_a8_scales_underflow(aq.dtype, m.weight._scale.dtype):
         return False
     return aq.dtype in fp8 and (wq.dtype in fp8 or wq.dtype == torch.int8)
 

@@ -23,7 +23,7 @@ from typing import Optional
 
 import torch
 
-from ..tensor import ActivationQBytesTensor, Optimizer, WeightQBytesTensor, qtype
+from ..tensor import Optimizer, WeightQBytesTensor, qtype
 from ..tensor.weights import conv2d_a8_eligible
 from .module import QModuleMixin, register_qmodule
 
@@ -50,17 +50,15 @@ class QConv2d(QModuleMixin, torch.nn.Conv2d):
             w = self.weight
             codes = torch.ops.quanto.qbytes_conv2d_a8_q(input._data, input._scale, w._data, w._scale, self.bias, self.output_scale,
                                                         list(self.stride), list(self.padding), list(self.dilation))
-            return ActivationQBytesTensor(self.activation_qtype, codes.size(), codes.stride(), codes, self.output_scale)
+            return self._output_from_codes(codes)
         # F.conv2d is intercepted by the weight's __torch_function__ (im2col + fused GEMM on a ROCm device)
         return self._conv_forward(input, self.qweight, self.bias)
 
     def _codes_from_epilogue(self, input) -> bool:
-        """Whether this call is the one the fused op computes: stored codes of the module's own activation qtype against a frozen 8-bit weight, zero
-        padding, the output hook still in place, and a call ``quanto::qbytes_conv2d_a8`` serves (conv2d_a8_eligible: ROCm device, scalar input scale,
-        dense, a served format pair, no gradient wanted - the op has no backward)."""
+        """Whether this call is the one the fused op computes (QModuleMixin._takes_stored_codes), and what is the convolution's own: an 8-bit
+        weight, zero padding, and a call ``quanto::qbytes_conv2d_a8`` serves (conv2d_a8_eligible: ROCm device, scalar input scale, dense, a served
+        format pair, no gradient wanted - the op has no backward)."""
         w = self.weight
-        if not (isinstance(input, ActivationQBytesTensor) and input.qtype == self.activation_qtype and type(w) is WeightQBytesTensor):
-            return False
-        if self.padding_mode != "zeros" or "output" not in self._quantize_hooks:
+        if not (self._takes_stored_codes(input) and type(w) is WeightQBytesTensor and self.padding_mode == "zeros"):
             return False
         return conv2d_a8_eligible(input, w, self.bias, self.stride, self.padding, self.dilation, self.groups)

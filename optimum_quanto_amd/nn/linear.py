@@ -3,7 +3,7 @@ from typing import Optional
 
 import torch
 
-from ..tensor import ActivationQBytesTensor, Optimizer, QTensor, WeightQBitsTensor, WeightQBytesTensor, qtype
+from ..tensor import Optimizer, QTensor, WeightQBitsTensor, WeightQBytesTensor, qtype
 from .module import QModuleMixin, register_qmodule
 
 __all__ = ["QLinear"]
@@ -32,18 +32,18 @@ class QLinear(QModuleMixin, torch.nn.Linear):
                                                        w._data.bits, w._group_size, n, k)
             else:
                 codes = torch.ops.quanto.qbytes_mm_q(input._data, w._data, input._scale * w._scale, self.bias, self.output_scale)
-            return ActivationQBytesTensor(self.activation_qtype, codes.size(), codes.stride(), codes, self.output_scale)
+            return self._output_from_codes(codes)
         if type(input) is torch.Tensor and isinstance(w, QTensor):
             return type(w).__torch_function__(torch.nn.functional.linear, (type(w),), (input, w, self.bias))
         return torch.nn.functional.linear(input, w, bias=self.bias)
 
     def _codes_from_epilogue(self, input, w) -> bool:
-        """Whether this call is the one the fused op computes: stored codes of the module's own activation qtype with a scalar scale against a frozen
-        8-bit weight of the same dtype or a frozen int4 / int2 weight (the marking checked its format), the output hook still in place, no gradient
-        wanted (the op has no backward)."""
+        """Whether this call is the one the fused op computes (QModuleMixin._takes_stored_codes), and what is the Linear's own: a scalar input scale
+        against an 8-bit weight of the same dtype or an int4 / int2 weight (the marking checked its format), no gradient wanted (the op has no
+        backward)."""
         sub_byte = isinstance(w, WeightQBitsTensor)
-        if not (isinstance(input, ActivationQBytesTensor) and (sub_byte or type(w) is WeightQBytesTensor) and self.frozen and "output" in self._quantize_hooks):
+        if not (self._takes_stored_codes(input) and (sub_byte or type(w) is WeightQBytesTensor)):
             return False
-        if input.qtype != self.activation_qtype or input._scale.numel() != 1 or not (sub_byte or input._data.dtype == w._data.dtype):
+        if input._scale.numel() != 1 or not (sub_byte or input._data.dtype == w._data.dtype):
             return False
         return not (torch.is_grad_enabled() and (input.requires_grad or w.requires_grad or (self.bias is not None and self.bias.requires_grad)))

@@ -165,6 +165,17 @@ class QModuleMixin(ABC):
             return output  # the forward already stored codes at output_scale (fused output quantization)
         return quantize_activation(output, qtype=self.activation_qtype, scale=self.output_scale)
 
+    # -- fused output quantization (model_api.fuse_output_quantization): what QLinear and QConv2d share ------------------------
+    def _takes_stored_codes(self, input) -> bool:
+        """The part of "this call is the one the fused op computes" that does not depend on the layer: stored codes of the module's own activation
+        qtype reach a frozen module whose output hook is still in place."""
+        return (isinstance(input, ActivationQBytesTensor) and input.qtype == self.activation_qtype and self.frozen
+                and "output" in self._quantize_hooks)
+
+    def _output_from_codes(self, codes: torch.Tensor) -> ActivationQBytesTensor:
+        """The codes a product kernel stored at ``output_scale`` as the module's output: the output hook passes it through."""
+        return ActivationQBytesTensor(self.activation_qtype, codes.size(), codes.stride(), codes, self.output_scale)
+
     # -- serialisation: a frozen weight travels as its inner tensors (weight._data, weight._scale, ...) -----------------------
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         def put(key, tensor):

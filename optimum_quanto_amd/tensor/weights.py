@@ -102,6 +102,13 @@ def _implicit_conv2d(input, weight, scale, bias, stride, padding, dilation, grou
     return torch.ops.quanto.qbytes_conv2d(input, weight._data, scale, bias, pair(stride), pair(padding), pair(dilation))
 
 
+def conv2d_a8_scales_underflow(a_dtype: torch.dtype, scale_dtype: torch.dtype) -> bool:
+    """The one pair of (activation dtype, scale dtype) the quantized-activation convolution leaves to the dequantizing route.  The op's scale is the
+    product of both scales rounded to the output dtype (the W8A8 QLinear contract); an e5m2 activation scale (absmax / 57344) times a weight scale lies
+    below fp16's normal range (~5e-8 against 6.1e-5) and would lose all or most of its bits."""
+    return a_dtype == torch.float8_e5m2 and scale_dtype == torch.float16
+
+
 def conv2d_a8_eligible(input, weight, bias, stride, padding, dilation, groups) -> bool:
     """Whether ``F.conv2d(input, weight, bias, ...)`` is a call the quantized-activation convolution kernel takes (csrc/qconv_a8.hip) - one predicate
     for ``quanto::qbytes_conv2d_a8`` (_implicit_conv2d_a8) and ``quanto::qbytes_conv2d_a8_q`` (a marked QConv2d): a per-tensor quantized 4-D input
@@ -113,9 +120,7 @@ def conv2d_a8_eligible(input, weight, bias, stride, padding, dilation, groups) -
         return False
     if input.axis is not None or input._scale.numel() != 1 or weight.dim() != 4:
         return False
-    # the op's scale is the product of both scales rounded to the output dtype (the W8A8 QLinear contract); an e5m2 activation scale (absmax / 57344)
-    # times a weight scale lies below fp16's normal range (~5e-8 against 6.1e-5) and would lose all or most of its bits: that pair keeps dequantizing
-    if input._data.dtype == torch.float8_e5m2 and weight._scale.dtype == torch.float16:
+    if conv2d_a8_scales_underflow(input._data.dtype, weight._scale.dtype):
         return False
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, weight, bias)):
         return False

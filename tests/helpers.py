@@ -321,3 +321,42 @@ def dequantize_scales(dt: str) -> torch.Tensor:
     """Every scale of the 16-bit lists that ``dt`` can hold (fp32: all ten), rounded to it."""
     values = SCALES_16[dt] if dt in SCALES_16 else tuple(dict.fromkeys(SCALES_16["fp16"] + SCALES_16["bf16"]))
     return scale_tensor(values, dt)
+
+
+# ---- fused output quantization (tests/test_*output_fusion_*.py): what the files of the three products share ---------------------------------------------
+OK, EINVAL, ENOTSUP, EALIGN = 0, -1, -2, -4  # QUANTO_HIP_* statuses (include/quanto_hip.h)
+F32, F16, BF16, I8, U8, E4M3, E5M2, E4M3FNUZ = range(8)  # quanto_hip_dtype
+CODE_DTYPES = {"int8": torch.int8, "e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
+CODE_QMAX = {torch.int8: 127.0, torch.float8_e4m3fn: 448.0, torch.float8_e5m2: 57344.0}
+SENTINEL = 0xA5
+
+
+def full_range_codes(dtype, shape, gen):
+    """Codes over the full range of ``dtype`` (float8: every finite bit pattern, the non-finite ones replaced by zero)."""
+    if dtype == torch.int8:
+        return torch.randint(-128, 128, shape, dtype=torch.int8, generator=gen)
+    bits = torch.randint(0, 256, shape, dtype=torch.int16, generator=gen).to(torch.uint8)
+    finite = torch.isfinite(bits.view(dtype).to(torch.float32))
+    return torch.where(finite, bits, torch.zeros_like(bits)).view(dtype)
+
+
+def quantile_out_scale(y, dtype):
+    """The 0.9-quantile of |y| over the largest code of ``dtype``, in y's dtype: an output scale at which the sequence itself clamps."""
+    return (torch.quantile(y.abs().to(torch.float32).reshape(-1), 0.9) / CODE_QMAX[dtype]).to(y.dtype)
+
+
+def clamped_share(y, out_scale, dtype):
+    """Share of the elements of ``y`` the sequence clamps at ``out_scale``."""
+    return ((y / out_scale).to(torch.float32).abs() > CODE_QMAX[dtype]).to(torch.float32).mean().item()
+
+
+def sentinel_buffer(nbytes, offset, device):
+    """(buffer, lead): ``nbytes`` of output at byte ``lead`` = 256 + offset of a 256-byte aligned buffer filled with SENTINEL, 4096 bytes behind it."""
+    lead = 256 + offset
+    buf = torch.full((lead + nbytes + 4096,), SENTINEL, dtype=torch.uint8, device=device)
+    assert buf.data_ptr() % 256 == 0
+    return buf, lead
+
+
+def assert_nothing_outside(buf, lead, nbytes, what):
+    assert bool((buf[:lead] == SENTINEL).all()) and bool((buf[lead + nbytes:] == SENTINEL).all()), f"bytes outside {what} were written"

@@ -12,10 +12,10 @@ from optimum_quanto_amd import (ActivationQBytesTensor, QLinear, freeze, fuse_ou
 from optimum_quanto_amd.library import hip as hip_mod
 from optimum_quanto_amd.library.hip import quanto_hip
 
-from helpers import make_qbits_problem, to_torch
+from helpers import BF16, E4M3, E4M3FNUZ, E5M2, EALIGN, EINVAL, ENOTSUP, F16, F32, I8, OK, U8
+from helpers import full_range_codes as _codes
+from helpers import make_qbits_problem, quantile_out_scale, to_torch
 
-OK, EINVAL, ENOTSUP, EALIGN = 0, -1, -2, -4
-F32, F16, BF16, I8, U8, E4M3, E5M2, E4M3FNUZ = range(8)
 TDT = {"bf16": torch.bfloat16, "fp16": torch.float16}
 
 
@@ -23,15 +23,6 @@ def test_status_codes_are_the_header_s():
     header = open(os.path.join(os.path.dirname(os.path.dirname(optimum_quanto_amd.__file__)), "include", "quanto_hip.h")).read()
     for name, value in (("QUANTO_HIP_EINVAL", EINVAL), ("QUANTO_HIP_ENOTSUP", ENOTSUP), ("QUANTO_HIP_EALIGN", EALIGN)):
         assert f"{name} = {value}" in header
-
-
-def _codes(dtype, shape, gen):
-    """Codes over the full range of ``dtype`` (float8: every finite bit pattern)."""
-    if dtype == torch.int8:
-        return torch.randint(-128, 128, shape, dtype=torch.int8, generator=gen)
-    bits = torch.randint(0, 256, shape, dtype=torch.int16, generator=gen).to(torch.uint8)
-    finite = torch.isfinite(bits.view(dtype).to(torch.float32))
-    return torch.where(finite, bits, torch.zeros_like(bits)).view(dtype)
 
 
 @pytest.mark.parametrize("with_bias", [False, True])
@@ -46,8 +37,7 @@ def test_op_default_is_the_two_op_sequence(dtype, a_scale, dt, with_bias):
             torch.randn(N, generator=gen).to(TDT[dt]) if with_bias else None)
     y = torch.ops.quanto.qbits_mm_a8(a, *args, 4, 128, N, K)
     assert y.dtype == TDT[dt] and bool(torch.isfinite(y).all())
-    qmax = 127 if dtype == torch.int8 else torch.finfo(dtype).max
-    out_scale = (torch.quantile(y.abs().to(torch.float32).reshape(-1), 0.9) / qmax).to(TDT[dt])
+    out_scale = quantile_out_scale(y, dtype)
     want = torch.ops.quanto.quantize_symmetric(y, dtype, None, out_scale)
     got = torch.ops.quanto.qbits_mm_a8_q(a, *args, out_scale, 4, 128, N, K)
     assert got.dtype == dtype and got.shape == (M, N)

@@ -17,12 +17,12 @@ import torch
 from optimum_quanto_amd import QLinear, freeze, fuse_output_quantization, qfloat8_e5m2, qint2, qint4, qint8, quantize
 from optimum_quanto_amd.library.hip import quanto_hip
 
-from helpers import make_qbits_problem, to_torch
+from helpers import CODE_DTYPES as KINDS
+from helpers import CODE_QMAX as QMAX
+from helpers import assert_nothing_outside, clamped_share, full_range_codes, make_qbits_problem, quantile_out_scale, sentinel_buffer, to_torch
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-QMAX = {torch.int8: 127.0, torch.float8_e4m3fn: 448.0, torch.float8_e5m2: 57344.0}
-KINDS = {"int8": torch.int8, "e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
 A_SCALE = {"int8": 0.02, "e4m3": 0.01, "e5m2": 1e-4}  # |codes| reach 128 / 448 / 57344: outputs of a few units whatever the kind
 ROUTE = {"int8": "a8_fused_int8", "e4m3": "a8_fused_fp8", "e5m2": "a8_fused_bf8"}
 TDT = {"bf16": torch.bfloat16, "fp16": torch.float16}
@@ -33,19 +33,10 @@ def route(kind, bits, fused):
     return ROUTE[kind] + ("_w2" if bits == 2 else "") + ("_q" if fused else "")
 
 
-def codes(kind, shape, gen):
-    """Codes over the full range of the activation type (float8: every finite bit pattern, the non-finite ones replaced by zero)."""
-    if kind == "int8":
-        return torch.randint(-128, 128, shape, dtype=torch.int8, generator=gen)
-    bits = torch.randint(0, 256, shape, dtype=torch.int16, generator=gen).to(torch.uint8)
-    finite = torch.isfinite(bits.view(KINDS[kind]).to(torch.float32))
-    return torch.where(finite, bits, torch.zeros_like(bits)).view(KINDS[kind])
-
-
 def problem(M, N, K, kind, dt, bits, with_bias, zp, seed=0, group_size=128):
     p = make_qbits_problem(1, N, K, dt, bits=bits, group_size=group_size, zeropoint=zp, seed=seed + M + N + K)
     gen = torch.Generator().manual_seed(1000 * seed + 7 * M + 3 * N + K)
-    a = codes(kind, (M, K), gen)
+    a = full_range_codes(KINDS[kind], (M, K), gen)
     shift = torch.from_numpy(p["shift"]) if p["shift"].dtype == np.uint8 else to_torch(p["shift"], dt)
     bias = (torch.randn(N, generator=gen) * 0.5).to(TDT[dt]) if with_bias else None
     return dict(a=a.to(DEV), a_scale=torch.tensor([A_SCALE[kind]], dtype=TDT[dt], device=DEV), packed=torch.from_numpy(p["packed"]).to(DEV),
@@ -57,21 +48,14 @@ def weight_args(p):
     return p["packed"], p["scale"], p["shift"], p["bias"]
 
 
-def out_scale_of(y, dtype):
-    """The 0.9-quantile of |y| over qmax, in y's dtype; and the share of elements the sequence clamps at that scale."""
-    qmax = QMAX[dtype]
-    s = (torch.quantile(y.abs().to(torch.float32).reshape(-1), 0.9) / qmax).to(y.dtype)
-    share = ((y / s).to(torch.float32).abs() > qmax).to(torch.float32).mean().item()
-    return s, share
-
-
 def sequence(p):
     """(codes of the existing quantizer on the existing kernel's output, out_scale) - with the route and the clamped share asserted."""
     lib = quanto_hip.lib
     y = lib.qbits_mm_a8(p["a"], p["a_scale"], *weight_args(p), p["bits"], p["group_size"], p["N"], p["K"])
     assert lib.last_kernel() == route(p["kind"], p["bits"], False)
     assert bool(torch.isfinite(y).all())
-    out_scale, share = out_scale_of(y, p["a"].dtype)
+    out_scale = quantile_out_scale(y, p["a"].dtype)
+    share = clamped_share(y, out_scale, p["a"].dtype)
     want = torch.ops.quanto.quantize_symmetric(y, p["a"].dtype, None, out_scale)
     print(f"{tuple(y.shape)} {p['kind']} {y.dtype} int{p['bits']}: out_scale {out_scale.item():.6g}, clamped share {share:.4f}")
     assert 0.02 <= share <= 0.25, f"the sequence clamps {share:.4f} of the elements at this output scale"
@@ -164,14 +148,12 @@ def test_no_byte_outside_the_output(monkeypatch, bm, offset, M, N, K, bits, kind
     monkeypatch.setenv("QUANTO_HIP_A8_BM", str(bm))
     p = problem(M, N, K, kind, "bf16", bits, True, False, seed=4)
     want, out_scale = sequence(p)
-    lead, tail = 256 + offset, 4096
-    buf = torch.full((lead + M * N + tail,), 0xA5, dtype=torch.uint8, device=DEV)
-    assert buf.data_ptr() % 256 == 0
+    buf, lead = sentinel_buffer(M * N, offset, DEV)
     yq = buf[lead:lead + M * N].view(p["a"].dtype).reshape(M, N)
     fused(p, out_scale, out=yq)
     torch.cuda.synchronize()
     assert torch.equal(buf[lead:lead + M * N], want.view(torch.uint8).reshape(-1))
-    assert bool((buf[:lead] == 0xA5).all()) and bool((buf[lead + M * N:] == 0xA5).all()), "bytes outside [M, N] were written"
+    assert_nothing_outside(buf, lead, M * N, "[M, N]")
 
 
 def test_int8_codes_reach_both_ends(monkeypatch):
@@ -189,8 +171,8 @@ def check_op(p, expect_fused, a=None):
     args = (p["a_scale"], *weight_args(p))
     y = torch.ops.quanto.qbits_mm_a8(p["a"], *args, p["bits"], p["group_size"], p["N"], p["K"])
     unfused_route = lib.last_kernel()
-    out_scale, share = out_scale_of(y, a.dtype)
-    assert 0.02 <= share <= 0.25
+    out_scale = quantile_out_scale(y, a.dtype)
+    assert 0.02 <= clamped_share(y, out_scale, a.dtype) <= 0.25
     want = torch.ops.quanto.quantize_symmetric(y, a.dtype, None, out_scale)
     got = torch.ops.quanto.qbits_mm_a8_q(a, *args, out_scale, p["bits"], p["group_size"], p["N"], p["K"])
     fused_route = lib.last_kernel()
@@ -206,7 +188,7 @@ def test_op_takes_the_fused_kernel_above_64_rows():
     p = problem(300, 136, 256, "int8", "bf16", 4, True, False, seed=5)
     got = check_op(p, True)
     p3 = dict(p, a=p["a"].reshape(3, 100, 256))  # leading batch dimensions are carried through
-    out_scale, _ = out_scale_of(quanto_hip.lib.qbits_mm_a8(p["a"], p["a_scale"], *weight_args(p), 4, 128, 136, 256), torch.int8)
+    out_scale = quantile_out_scale(quanto_hip.lib.qbits_mm_a8(p["a"], p["a_scale"], *weight_args(p), 4, 128, 136, 256), torch.int8)
     got3 = torch.ops.quanto.qbits_mm_a8_q(p3["a"], p["a_scale"], *weight_args(p), out_scale, 4, 128, 136, 256)
     assert got3.shape == (3, 100, 136) and torch.equal(got3.reshape(300, 136), got)
 

@@ -14,9 +14,8 @@ from optimum_quanto_amd import (ActivationQBytesTensor, QConv2d, freeze, fuse_ou
 from optimum_quanto_amd.library import hip as hip_mod
 from optimum_quanto_amd.library.hip import quanto_hip
 
-OK, EINVAL, ENOTSUP = 0, -1, -2
-F32, F16, BF16, I8, U8, E4M3, E5M2, E4M3FNUZ = range(8)
-QMAX = {torch.int8: 127.0, torch.float8_e4m3fn: 448.0}
+from helpers import BF16, E4M3, E4M3FNUZ, E5M2, EINVAL, ENOTSUP, F16, F32, I8, OK, U8, quantile_out_scale
+
 HEADER = os.path.join(os.path.dirname(os.path.dirname(optimum_quanto_amd.__file__)), "include", "quanto_hip.h")
 
 
@@ -59,7 +58,7 @@ def test_op_default_is_the_two_op_sequence(dtype, dt, with_bias):
     geometry = ([2, 1], [1, 0], [1, 2])
     y = torch.ops.quanto.qbytes_conv2d_a8(x, xs, w, ws, b, *geometry)
     assert y.dtype == dt and y.shape == (2, 7, 5, 7)
-    out_scale = (torch.quantile(y.abs().to(torch.float32).reshape(-1), 0.9) / QMAX[dtype]).to(dt)
+    out_scale = quantile_out_scale(y, dtype)
     want = torch.ops.quanto.quantize_symmetric(y, dtype, None, out_scale)
     got = torch.ops.quanto.qbytes_conv2d_a8_q(x, xs, w, ws, b, out_scale, *geometry)
     assert got.dtype == dtype and got.shape == (2, 7, 5, 7)

@@ -14,10 +14,12 @@ import torch
 import optimum_quanto_amd as Q
 from optimum_quanto_amd.library.hip import _DTYPES, quanto_hip
 
+from helpers import CODE_QMAX as QMAX
+from helpers import assert_nothing_outside, quantile_out_scale, sentinel_buffer
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 TDT = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
-QMAX = {torch.int8: 127.0, torch.float8_e4m3fn: 448.0, torch.float8_e5m2: 57344.0}
 E4M3, E5M2 = torch.float8_e4m3fn, torch.float8_e5m2
 
 
@@ -75,7 +77,7 @@ def sequence(p):
     assert lib.last_kernel() == _kernel_name(p["x"].dtype, p["w"].dtype)
     assert bool(torch.isfinite(y).all())
     dtype = p["x"].dtype
-    out_scale = (torch.quantile(y.abs().to(torch.float32).reshape(-1), 0.9) / QMAX[dtype]).to(y.dtype)
+    out_scale = quantile_out_scale(y, dtype)
     want = torch.ops.quanto.quantize_symmetric(y, dtype, None, out_scale)
     share = extreme_share(want)
     print(f"{tuple(y.shape)} {dtype} {y.dtype}: out_scale {out_scale.item():.6g}, extreme codes {share:.4f}")
@@ -210,14 +212,12 @@ def test_no_byte_outside_a_misaligned_output(xdt, geo, offset):
     p = problem(geo, xdt, xdt, "bf16", True, seed=13)
     want, out_scale = sequence(p)
     n = want.numel()
-    lead, tail = 256 + offset, 4096
-    buf = torch.full((lead + n + tail,), 0xA5, dtype=torch.uint8, device=DEV)
-    assert buf.data_ptr() % 256 == 0
+    buf, lead = sentinel_buffer(n, offset, DEV)
     yq = buf[lead:lead + n].view(xdt).reshape(want.shape)
     assert yq.data_ptr() % 256 == offset
     fused(p, out_scale, yq=yq)
     assert torch.equal(buf[lead:lead + n], want.view(torch.uint8).reshape(-1)), "codes differ from the two-op sequence"
-    assert bool((buf[:lead] == 0xA5).all()) and bool((buf[lead + n:] == 0xA5).all()), "bytes outside the output were written"
+    assert_nothing_outside(buf, lead, n, "the output")
 
 
 # ---- forced split: the reduce kernel runs the code epilogue on the summed accumulators ------------------------------------------------------------------
@@ -258,7 +258,7 @@ def check_op(p, expect_fused, xs=None):
     xs = xs0 if xs is None else xs
     geo = [list(v) for v in geometry(p)]
     y = torch.ops.quanto.qbytes_conv2d_a8(x, xs, w, ws, b, *geo)
-    out_scale = (torch.quantile(y.abs().to(torch.float32).reshape(-1), 0.9) / QMAX[x.dtype]).to(y.dtype)
+    out_scale = quantile_out_scale(y, x.dtype)
     want = torch.ops.quanto.quantize_symmetric(y, x.dtype, None, out_scale)
     assert 0.02 <= extreme_share(want) <= 0.25
     from optimum_quanto_amd.library.ops import qbytes_conv2d_a8_q_default

@@ -10,19 +10,10 @@ from optimum_quanto_amd import (ActivationQBytesTensor, QLinear, freeze, fuse_ou
                                 quantize)
 from optimum_quanto_amd.library.hip import quanto_hip
 
-OK, EINVAL, ENOTSUP = 0, -1, -2
-F32, F16, BF16, I8, U8, E4M3, E5M2, E4M3FNUZ = range(8)
+from helpers import BF16, E4M3, E4M3FNUZ, E5M2, EINVAL, ENOTSUP, F16, F32, I8, OK
+from helpers import full_range_codes as _codes
+
 AUTO, NAIVE, GEMV, MFMA, MFMA_LARGE, SKINNY, NATIVE8 = range(7)
-
-
-def _codes(dtype, shape, gen):
-    """Codes over the full range of ``dtype`` (float8: every finite bit pattern)."""
-    if dtype == torch.int8:
-        return torch.randint(-128, 128, shape, dtype=torch.int8, generator=gen)
-    bits = torch.randint(0, 256, shape, dtype=torch.int16, generator=gen).to(torch.uint8)
-    t = bits.view(dtype)
-    finite = torch.isfinite(t.to(torch.float32))
-    return torch.where(finite, bits, torch.zeros_like(bits)).view(dtype)
 
 
 @pytest.mark.parametrize("with_bias", [False, True])

@@ -17,11 +17,13 @@ import torch
 from optimum_quanto_amd import QLinear, freeze, fuse_output_quantization, qfloat8_e4m3fn, qint8, quantize
 from optimum_quanto_amd.library.hip import quanto_hip
 
+from helpers import CODE_DTYPES as KINDS
+from helpers import CODE_QMAX as QMAX
+from helpers import assert_nothing_outside, sentinel_buffer
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 FUSED = "mfma_native8_q"
-QMAX = {torch.int8: 127.0, torch.float8_e4m3fn: 448.0, torch.float8_e5m2: 57344.0}
-KINDS = {"int8": torch.int8, "e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
 MIDS = {"bf16": torch.bfloat16, "fp16": torch.float16}
 DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.int8: 3, torch.float8_e4m3fn: 5, torch.float8_e5m2: 6}
 
@@ -161,9 +163,7 @@ def test_no_byte_outside_the_output(monkeypatch, small, offset, M, N, K, kind):
     monkeypatch.setenv("QUANTO_HIP_NATIVE8_SMALL", str(small))
     a, b, scales, bias = problem(M, N, K, kind, "bf16", True, seed=4)
     _, out_scale, want, _ = sequence(a, b, scales, bias)
-    lead, tail = 256 + offset, 4096
-    buf = torch.full((lead + M * N + tail,), 0xA5, dtype=torch.uint8, device=DEV)
-    assert buf.data_ptr() % 256 == 0
+    buf, lead = sentinel_buffer(M * N, offset, DEV)
     yq = buf[lead:lead + M * N]
     s = scales.reshape(-1).contiguous()
     st = quanto_hip.lib._c.quanto_hip_qbytes_mm_q_ws(a.data_ptr(), b.data_ptr(), s.data_ptr(), bias.data_ptr(), out_scale.data_ptr(), yq.data_ptr(), M, N, K,
@@ -171,7 +171,7 @@ def test_no_byte_outside_the_output(monkeypatch, small, offset, M, N, K, kind):
     assert st == 0 and quanto_hip.lib.last_kernel() == FUSED
     torch.cuda.synchronize()
     assert torch.equal(yq, want.view(torch.uint8).reshape(-1))
-    assert bool((buf[:lead] == 0xA5).all()) and bool((buf[lead + M * N:] == 0xA5).all()), "bytes outside [M, N] were written"
+    assert_nothing_outside(buf, lead, M * N, "[M, N]")
 
 
 # ---- what the library does not serve still returns the sequence's codes ----------------------------------------------------------------------------
