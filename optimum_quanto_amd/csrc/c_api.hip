@@ -55,7 +55,7 @@ size_t qbytes_skinny_multi_workspace(int, const int64_t*, int64_t, int64_t);
 int qbytes_mm_skinny_multi(const void*, int, const void* const*, const void* const*, const void* const*, void* const*, const int64_t*, int64_t,
                            int64_t, int, int, int, void*, size_t, hipStream_t);
 bool qbytes_skinny_supported(int64_t, int64_t, int64_t, int, int, int);
-size_t qbytes_skinny_workspace(int64_t, int64_t, int64_t);
+size_t qbytes_skinny_workspace(int64_t, int64_t, int64_t, int, int, int);
 int qbytes_mm_skinny(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, void*, size_t, hipStream_t);
 bool dense_mm_large_supported(int64_t, int64_t, int64_t, int);
 int dense_mm_large(const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, hipStream_t);
@@ -72,7 +72,7 @@ int qbits_mm_skinny_multi(const void*, int, const uint8_t* const*, const void* c
 bool qbits_mmv_supported(int64_t, const PackedGeom&, int);
 int qbits_mm_mmv(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool, hipStream_t);
 bool qbits_skinny_supported(int64_t, const PackedGeom&, int);
-size_t qbits_skinny_workspace(int64_t, const PackedGeom&);
+size_t qbits_skinny_workspace(int64_t, const PackedGeom&, int);
 int qbits_mm_skinny(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool, void*,
                     size_t, hipStream_t);
 bool qbits_mfma_supported(int64_t, const PackedGeom&, int);
@@ -213,7 +213,7 @@ struct Plan {
 
 static int64_t qbits_kernel_workspace(int kernel, int64_t M, const PackedGeom& g, int dtype) {
   switch (kernel) {
-    case QUANTO_HIP_KERNEL_SKINNY: return qbits_skinny_supported(M, g, dtype) ? (int64_t)qbits_skinny_workspace(M, g) : 0;
+    case QUANTO_HIP_KERNEL_SKINNY: return (int64_t)qbits_skinny_workspace(M, g, dtype);  // one plan: 0 when not served
     case QUANTO_HIP_KERNEL_MFMA: return qbits_mfma_supported(M, g, dtype) ? (int64_t)qbits_mfma_workspace(M, g) : 0;
     case QUANTO_HIP_KERNEL_DEQUANT_MFMA: return dequant_mfma_supported(M, g, dtype) ? (int64_t)dequant_mfma_workspace(g) : 0;
     case QUANTO_HIP_KERNEL_MFMA_FUSED4: return qbits_mfma_fused_supported(M, g, dtype) ? (int64_t)qbits_mfma_fused_workspace(M, g) : 0;
@@ -587,8 +587,8 @@ static int qbytes_kernel_serves(int kernel, int64_t M, int64_t N, int64_t K, int
 static Plan plan_qbytes(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel) {
   if (kernel == QUANTO_HIP_KERNEL_AUTO) kernel = pick_qbytes_kernel(M, N, K, a_dtype, b_dtype, out_dtype);
   int64_t ws = 0;
-  if (kernel == QUANTO_HIP_KERNEL_SKINNY && qbytes_skinny_supported(M, N, K, a_dtype, b_dtype, out_dtype))
-    ws = (int64_t)qbytes_skinny_workspace(M, N, K);
+  if (kernel == QUANTO_HIP_KERNEL_SKINNY)
+    ws = (int64_t)qbytes_skinny_workspace(M, N, K, a_dtype, b_dtype, out_dtype);  // one plan: 0 when not served
   else if (kernel == QUANTO_HIP_KERNEL_MFMA_LARGE && qbytes_mfma_large_supported(M, N, K, a_dtype, b_dtype, out_dtype))
     ws = (int64_t)qbytes_mfma_large_workspace(M, N, K);
   else if (kernel == QUANTO_HIP_KERNEL_NATIVE8)

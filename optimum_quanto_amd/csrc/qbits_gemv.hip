@@ -407,18 +407,31 @@ __global__ void __launch_bounds__(256)
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side: `nseg` Linears sharing x (nseg = 1 for the plain op)
+// host side: `l.nseg` Linears sharing x (nseg = 1 for the plain op; qh_common.h)
 struct GemvProblem {
-  int nseg;
-  const uint8_t* packed[MAX_SEGS];
-  const void* scale[MAX_SEGS];
-  const void* shift[MAX_SEGS];
-  const void* bias[MAX_SEGS];
-  void* y[MAX_SEGS];
-  int N[MAX_SEGS];
+  Linears l;
   int gs;    // group size: 128 (quad-shared scale fetch), 32 / 64 / 96, or 0 = per-channel
   int bits;  // 4, or 2 (always on the per-lane scale fetch)
 };
+
+// How K is dealt over the waves and M over the passes; worked out once per call (qbytes_gemv.hip: the same slab rule, two rows per pass).
+struct GemvShape {
+  int wpr, wpr_log2;  // 1, 2 or 4 waves per row group: a wave owns K-slabs of 1024
+  int iters;          // slabs per wave; more than 4 are not instantiated
+  int mt_max;         // rows of x per pass
+};
+static GemvShape gemv_shape(const GemvProblem& pb, int K) {
+  GemvShape s;
+  const int nslab = (K + 1023) / 1024;
+  s.wpr = nslab >= 3 ? 4 : nslab;
+  s.wpr_log2 = s.wpr == 4 ? 2 : s.wpr - 1;
+  s.iters = (nslab + s.wpr - 1) / s.wpr;
+  // Rows of x are processed in passes of at most 8 (x lives in registers: 8 VGPRs per slab and row); the weights of
+  // later passes come from the Infinity Cache (a Linear's packed weight is 8-30 MB).  8 rows per pass need
+  // iters <= 2 slabs per wave (K <= 8192) to stay inside the register file; the per-lane scale fetch variants exist for <= 4 rows
+  s.mt_max = (pb.gs != 128 || pb.bits != 4 || pb.l.nseg > 1) ? 4 : (s.iters <= 2 ? 8 : 4);
+  return s;
+}
 
 static int gemv_variant() {
   // experiments: QUANTO_HIP_GEMV_VARIANT = bit 0 (x / scales requested first) | bit 1 (non-temporal weight loads) |
@@ -428,11 +441,8 @@ static int gemv_variant() {
 }
 
 template <int DT, int MT, bool INT_SHIFT>
-static int gemv_launch_iters(const void* x, const GemvProblem& pb, int m0, int K, hipStream_t stream) {
-  const int nslab = (K + 1023) / 1024;
-  const int wpr = nslab >= 3 ? 4 : nslab;  // 1, 2 or 4 waves per row group
-  const int wpr_log2 = wpr == 4 ? 2 : wpr - 1;
-  const int iters = (nslab + wpr - 1) / wpr;
+static int gemv_launch_iters(const void* x, const GemvProblem& pb, const GemvShape& sh, int m0, int K, hipStream_t stream) {
+  const int wpr = sh.wpr, wpr_log2 = sh.wpr_log2, iters = sh.iters;
   if (iters > 4) return QUANTO_HIP_ENOTSUP;
   // packed rows per wave pass.  8 rows cut the instructions per weight byte by a quarter (612 per 8 KiB wave against 387 per 4 KiB:
   // x slice, addresses and reduction tail are per wave) but halve the waves, and a wave is one batch of loads followed by its
@@ -441,19 +451,19 @@ static int gemv_launch_iters(const void* x, const GemvProblem& pb, int m0, int K
   const bool rr8_ok = pb.gs == 128 && pb.bits == 4 && MT <= 2 && iters == 1;
   const int rr = rr8_ok && env_int("QUANTO_HIP_GEMV_RR", 0) == 8 ? 8 : RR;
   const int rows_per_block = rr * (4 / wpr);
+  const Linears& l = pb.l;
   GemvSegs segs;
-  int grid = 0;
-  for (int i = 0; i < MAX_SEGS; ++i) {
-    const int j = i < pb.nseg ? i : 0;  // unused slots repeat segment 0 and are never selected
-    segs.packed[i] = pb.packed[j];
-    segs.scale[i] = reinterpret_cast<const uint16_t*>(pb.scale[j]);
-    segs.shift[i] = pb.shift[j];
-    segs.bias[i] = reinterpret_cast<const uint16_t*>(pb.bias[j]);
-    segs.y[i] = reinterpret_cast<uint16_t*>(pb.y[j]) + (size_t)m0 * pb.N[j];
-    segs.N[i] = pb.N[j];
-    segs.first_block[i] = i < pb.nseg ? grid : 0x7FFFFFFF;
-    if (i < pb.nseg) grid += (pb.N[i] / (8 / pb.bits) + rows_per_block - 1) / rows_per_block;
-  }
+  const int grid = fill_segments(
+      l.nseg, segs.first_block,
+      [&](int i, int j) {
+        segs.packed[i] = reinterpret_cast<const uint8_t*>(l.w[j]);
+        segs.scale[i] = reinterpret_cast<const uint16_t*>(l.scale[j]);
+        segs.shift[i] = l.shift[j];
+        segs.bias[i] = reinterpret_cast<const uint16_t*>(l.bias[j]);
+        segs.y[i] = reinterpret_cast<uint16_t*>(l.y[j]) + (size_t)m0 * l.N[j];
+        segs.N[i] = l.N[j];
+      },
+      [&](int i) { return (l.N[i] / (8 / pb.bits) + rows_per_block - 1) / rows_per_block; });
   auto xs = reinterpret_cast<const uint16_t*>(x) + (size_t)m0 * K;
   // group -> shift: 32 -> 5, 64 -> 6, 128 -> 7, per-channel -> 30 (always group 0), 96 -> -1 ((k >> 5) / 3)
   const int gshift = pb.gs == 0 ? 30 : pb.gs == 96 ? -1 : pb.gs == 32 ? 5 : pb.gs == 64 ? 6 : 7;
@@ -472,7 +482,7 @@ static int gemv_launch_iters(const void* x, const GemvProblem& pb, int m0, int K
 #define QH_LAUNCH_V(IT, V)                    \
   do {                                        \
     if constexpr (MT <= 4) {                  \
-      if (pb.nseg > 1)                        \
+      if (pb.l.nseg > 1)                      \
         QH_LAUNCH_VM(IT, V, true);            \
       else                                    \
         QH_LAUNCH_VM(IT, V, false);           \
@@ -520,31 +530,26 @@ static int gemv_launch_iters(const void* x, const GemvProblem& pb, int m0, int K
 #undef QH_LAUNCH
 #undef QH_LAUNCH_V
 #undef QH_LAUNCH_VM
-  if ((pb.nseg > 1 || pb.gs != 128 || pb.bits != 4) && MT > 4) return QUANTO_HIP_ENOTSUP;  // not reachable: those calls are limited to M <= 4
+  if ((pb.l.nseg > 1 || pb.gs != 128 || pb.bits != 4) && MT > 4) return QUANTO_HIP_ENOTSUP;  // not reachable: those calls are limited to M <= 4
   return launch_status();
 }
 
 template <int DT, bool INT_SHIFT>
 static int gemv_launch_m(const void* x, const GemvProblem& pb, int M, int K, hipStream_t stream) {
-  // Rows of x are processed in passes of at most 8 (x lives in registers: 8 VGPRs per slab and row); the weights of
-  // later passes come from the Infinity Cache (a Linear's packed weight is 8-30 MB).  8 rows per pass need
-  // iters <= 2 slabs per wave (K <= 8192) to stay inside the register file.
-  const int nslab = (K + 1023) / 1024;
-  const int iters = (nslab + (nslab >= 3 ? 4 : nslab) - 1) / (nslab >= 3 ? 4 : nslab);
-  const int mt_max = (pb.gs != 128 || pb.bits != 4 || pb.nseg > 1) ? 4 : (iters <= 2 ? 8 : 4);  // the per-lane scale fetch variants exist for <= 4 rows
+  const GemvShape sh = gemv_shape(pb, K);
   int m0 = 0;
   while (m0 < M) {
     const int left = M - m0;
-    const int mt = (left >= 8 && mt_max >= 8) ? 8 : (left >= 4 ? 4 : (left >= 2 ? 2 : 1));
+    const int mt = (left >= 8 && sh.mt_max >= 8) ? 8 : (left >= 4 ? 4 : (left >= 2 ? 2 : 1));
     int st;
     if (mt == 8)
-      st = gemv_launch_iters<DT, 8, INT_SHIFT>(x, pb, m0, K, stream);
+      st = gemv_launch_iters<DT, 8, INT_SHIFT>(x, pb, sh, m0, K, stream);
     else if (mt == 4)
-      st = gemv_launch_iters<DT, 4, INT_SHIFT>(x, pb, m0, K, stream);
+      st = gemv_launch_iters<DT, 4, INT_SHIFT>(x, pb, sh, m0, K, stream);
     else if (mt == 2)
-      st = gemv_launch_iters<DT, 2, INT_SHIFT>(x, pb, m0, K, stream);
+      st = gemv_launch_iters<DT, 2, INT_SHIFT>(x, pb, sh, m0, K, stream);
     else
-      st = gemv_launch_iters<DT, 1, INT_SHIFT>(x, pb, m0, K, stream);
+      st = gemv_launch_iters<DT, 1, INT_SHIFT>(x, pb, sh, m0, K, stream);
     if (st != QUANTO_HIP_OK) return st;
     m0 += mt;
   }
@@ -570,17 +575,9 @@ static int gemv_dispatch(const void* x, const GemvProblem& pb, int M, int K, int
 int qbits_mm_gemv(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
                   const PackedGeom& g, int dtype, bool int_shift, hipStream_t stream) {
   if (!qbits_gemv_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
-  GemvProblem pb{};
-  pb.nseg = 1;
-  pb.packed[0] = packed;
-  pb.scale[0] = scale;
-  pb.shift[0] = shift;
-  pb.bias[0] = bias;
-  pb.y[0] = y;
-  pb.N[0] = (int)g.N;
-  pb.gs = g.C == g.K && g.C != 128 ? 0 : (int)g.C;
-  pb.bits = g.bits;
+  const void* w = packed;
+  const GemvProblem pb{gather_linears(x, 1, &w, &scale, &shift, &bias, &y, &g.N), g.C == g.K && g.C != 128 ? 0 : (int)g.C, g.bits};
+  if (pb.l.align % 16) return QUANTO_HIP_EALIGN;
   return gemv_dispatch(x, pb, (int)M, (int)g.K, dtype, int_shift, stream);
 }
 
@@ -590,21 +587,8 @@ int qbits_mm_gemv_multi(const void* x, int nseg, const uint8_t* const* packed, c
                         const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, int dtype, bool int_shift,
                         hipStream_t stream) {
   if (nseg < 1 || nseg > MAX_SEGS) return QUANTO_HIP_EINVAL;
-  GemvProblem pb{};
-  pb.nseg = nseg;
-  pb.gs = 128;
-  pb.bits = 4;
-  uintptr_t align = reinterpret_cast<uintptr_t>(x);
-  for (int i = 0; i < nseg; ++i) {
-    pb.packed[i] = packed[i];
-    pb.scale[i] = scale[i];
-    pb.shift[i] = shift[i];
-    pb.bias[i] = bias ? bias[i] : nullptr;
-    pb.y[i] = y[i];
-    pb.N[i] = (int)N[i];
-    align |= reinterpret_cast<uintptr_t>(packed[i]);
-  }
-  if (align % 16) return QUANTO_HIP_EALIGN;
+  const GemvProblem pb{gather_linears(x, nseg, reinterpret_cast<const void* const*>(packed), scale, shift, bias, y, N), 128, 4};
+  if (pb.l.align % 16) return QUANTO_HIP_EALIGN;
   return gemv_dispatch(x, pb, (int)M, (int)K, dtype, int_shift, stream);
 }
 

@@ -448,52 +448,13 @@ __global__ void __launch_bounds__(WAVES * SETS * 64) qbits_skinny_kernel(Args a,
 constexpr int lds_bytes(int tf, int stages, int G, int waves, int planes = 2) {
   return stages * (waves * (16 / planes) * BK + tf * 16 * BK * 2) + G * 2 * (16 * waves + 4) * 2;
 }
-
-// `segs` (with the total number of feature blocks) selects the multi-Linear launch; 64-feature blocks only, like the two-set form
-template <int DT, int TF, int STAGES, bool INT_SHIFT, int WAVES, bool MULTI, int SETS, int GPT = 1, int PLANES = 2, int TK = 128>
-static int launch_k(const Args& a, hipStream_t stream, const Segs& segs, int grid, int lds) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbits_skinny_kernel<DT, TF, STAGES, INT_SHIFT, WAVES, MULTI, SETS, GPT, PLANES, TK>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((qbits_skinny_kernel<DT, TF, STAGES, INT_SHIFT, WAVES, MULTI, SETS, GPT, PLANES, TK>), dim3(grid), dim3(WAVES * SETS * 64), lds, stream, a, segs);
-  return launch_status();
-}
-
-template <int DT, int TF, int STAGES, bool INT_SHIFT, int WAVES>
-static int launch_s(const Args& a, hipStream_t stream, const Segs* segs = nullptr, int total_fb = 0) {
-  const int lds = lds_bytes(TF, STAGES, a.K / BK / a.S, WAVES);
-  if constexpr (WAVES == 4) {
-    // eight waves per block from two token fragments on (us, four -> eight waves: (32,4096,4096) 10.74 -> 10.21, (64,4096,4096)
-    // 17.6 -> 15.7, (32,14336,4096) 18.5 -> 17.7, gate+up M = 32 in one launch 29.5 -> 26.6; but one fragment, q/k/v M = 8:
-    // 9.87 -> 10.52: too little work per tile to share; the 8-bit kernel of qbytes_skinny.hip gains nothing: int8 (32,4096,4096)
-    // 10.95 -> 10.96, gate+up in one launch 26.5 -> 26.7 - four times the weight bytes per tile, no group fold)
-    // r6: the choice is a compile-time one (the other wave-set count of each TF was reachable through QUANTO_HIP_SKINNY_SETS only and doubled
-    // the 64-feature-block instantiations of this file)
-    constexpr int SETS = TF >= 2 ? 2 : 1;
-    if (segs) return launch_k<DT, TF, STAGES, INT_SHIFT, 4, true, SETS>(a, stream, *segs, total_fb * a.S, lds);
-    if constexpr (SETS == 2) return launch_k<DT, TF, STAGES, INT_SHIFT, 4, false, 2>(a, stream, Segs{}, a.N / 64 * a.S, lds);
-  }
-  return launch_k<DT, TF, STAGES, INT_SHIFT, WAVES, false, 1>(a, stream, Segs{}, a.N / (16 * WAVES) * a.S, lds);
-}
-
-// Deepest DMA pipeline that fits: the kernel is latency-bound per block (bytes in flight = stages x tile bytes).  Narrow
-// blocks budget for two (or three) blocks per CU.
-template <int DT, int TF, bool INT_SHIFT, int WAVES>
-static int launch(const Args& a, hipStream_t stream, const Segs* segs = nullptr, int total_fb = 0) {
-  // LDS budget per block: 50 KiB = three blocks per CU.  A deeper ring with the CU to itself is slower: (32,4096,4096) 11.5 us
-  // at 150 KiB, 11.0 at 76, 10.6 at 50; (32,4096,14336) split 2: 28.3 / 17.8 / 17.3 us
-  const int budget = env_int("QUANTO_HIP_SKINNY_LDS_KB", 50) * 1024;
-  constexpr int per_tile = 1 + TF * 4 / WAVES;  // DMA instructions per wave and tile; vmcnt counts at most 63 of them
-  if constexpr ((8 - 4) * per_tile <= 60)
-    if (lds_bytes(TF, 8, a.K / BK / a.S, WAVES) <= budget) return launch_s<DT, TF, 8, INT_SHIFT, WAVES>(a, stream, segs, total_fb);
-  if constexpr ((6 - 4) * per_tile <= 60)
-    if (lds_bytes(TF, 6, a.K / BK / a.S, WAVES) <= budget) return launch_s<DT, TF, 6, INT_SHIFT, WAVES>(a, stream, segs, total_fb);
-  return launch_s<DT, TF, 4, INT_SHIFT, WAVES>(a, stream, segs, total_fb);
-}
+// a ring of `stages` keeps (stages - 4) tiles' DMA instructions of a wave outstanding; vmcnt counts at most 63 of them
+constexpr bool ring_countable(int stages, int tf, int waves) { return (stages - 4) * (1 + tf * 4 / waves) <= 60; }
 
 // waves per block: the widest that divides N.  Narrower blocks do not help small N (measured, N = 4096, M = 32: 4 waves
 // 21.9 us, 2 waves 21.8 us, 1 wave 26.1 us): the kernel is bound by the instruction stream of the single wave each SIMD gets,
 // not by the number of occupied CUs - what it lacks for N <= 4096 is K-parallelism.
-inline int pick_waves(int N, int tf = 1) {
+inline int pick_waves(int N) {
   const int forced = env_int("QUANTO_HIP_SKINNY_WAVES", 0);  // experiments
   // (r5 experiment, withdrawn in r6: forced == 8 -> 128 features per block - half the activation traffic per weight byte, twice the partial
   //  sums: (32,4096,4096) 11.0 vs 9.5 us, profiles/r05_batched_decode_128_feature_blocks_ab.jsonl; patch: scripts/archive/experiments_r6/)
@@ -501,198 +462,256 @@ inline int pick_waves(int N, int tf = 1) {
   return N % 64 == 0 ? 4 : (N % 32 == 0 ? 2 : 1);
 }
 
-template <int DT, bool INT_SHIFT, int TF>
-static int launch_waves(const Args& a, hipStream_t stream, const Segs* segs = nullptr, int total_fb = 0) {
-  if (segs) return launch<DT, TF, INT_SHIFT, 4>(a, stream, segs, total_fb);
-  const int w = pick_waves(a.N, TF);
-  if (w == 4) return launch<DT, TF, INT_SHIFT, 4>(a, stream);
-  if (w == 2) return launch<DT, TF, INT_SHIFT, 2>(a, stream);
-  return launch<DT, TF, INT_SHIFT, 1>(a, stream);
+// Everything the host decides about a call, in one place: qbits_skinny_supported / _workspace, their _multi forms and the launch read this and
+// nothing else, as the prefill units read n8::make_plan / gf::make_plan.  Made per call (the experiment knobs are read per call), never kept.
+struct Plan {
+  // the call (make_plan): what the supported / workspace entries answer
+  bool served;
+  int waves, split_waves;   // a block is 16 * waves features wide; the width the split counts blocks of (see plan_format)
+  int gpt, per_channel, planes, tk;  // Args: groups per tile, one scale per feature, values per byte, k per tile
+  bool one_form;            // a format instantiated for the 4-stage ring only
+  int tiles;                // K / tk
+  int S, grid;              // K split, workgroups = feature blocks * S
+  size_t workspace;         // bytes the split this shape asks for needs (0: unsplit), whatever the caller then brought
+  // one pass of up to 64 rows (plan_pass): what only the launch needs
+  int rows, tf;             // rows of x and their token fragments of 16: 1, 2 or 4
+  int sets, stages;         // block = waves * sets * 64 threads; DMA ring depth
+  int lds;                  // dynamic LDS bytes
+};
+
+// `g` is the geometry of the launch (multi: the Linears' N added up, int4, group size 128); `workspace_bytes`: what the caller's split may use
+// (the queries plan with SIZE_MAX; without enough of it the call runs with one block per feature block).
+// It is made in three steps, each a function of the one before, so that an entry pays for what it answers: plan_format (format, block width,
+// "served": the supported entries), make_plan (+ split, grid, workspace: the workspace entries and the launch), plan_pass (+ one pass's ring).
+constexpr int fragments(int64_t rows) { return rows <= 16 ? 1 : (rows <= 32 ? 2 : 4); }
+static Plan plan_format(int64_t M, const PackedGeom& g, int dtype, bool multi) {
+  Plan p{};
+  const int call_tf = fragments(M > 64 ? 64 : M);  // of a full pass: M > 64 runs in passes of 64
+  // group sizes 128, 64, 32 (1, 2, 4 groups per 128-k tile) and per-channel scales (r3: the formats nn/qmodule.py:121-129 selects
+  // when in_features is not a multiple of 128 or the caller asks for them no longer leave the streaming kernel)
+  p.per_channel = g.C == g.K && g.C != 128;
+  const bool g96 = g.bits == 4 && g.C == 96 && !p.per_channel;  // group size 96 (r4): tiles of 96 k
+  const bool int2 = g.bits == 2;                                // qint2 (r4): 16 packed rows x 4 planes
+  const bool small = !p.per_channel && (g.C == 64 || g.C == 32);
+  p.planes = int2 ? 4 : 2;
+  p.tk = g96 ? 96 : 128;
+  p.gpt = small ? (int)(128 / g.C) : 1;
+  // group sizes 96 / 64 / 32 and int2 are instantiated for 64-feature blocks and the 4-stage ring only, the multi launch for 64-feature blocks; from
+  // two token fragments on such a block is two wave sets (us, four -> eight waves: (32,4096,4096) 10.74 -> 10.21, (64,4096,4096) 17.6 -> 15.7,
+  // (32,14336,4096) 18.5 -> 17.7, gate+up M = 32 in one launch 29.5 -> 26.6; but one fragment, q/k/v M = 8: 9.87 -> 10.52: too little work
+  // per tile to share; the 8-bit kernel of qbytes_skinny.hip gains nothing: four times the weight bytes per tile, no group fold)
+  p.one_form = g96 || int2 || small;
+  const int knob_waves = pick_waves((int)g.N);
+  p.waves = p.one_form || multi ? 4 : knob_waves;
+  // Kept as found, and visible under QUANTO_HIP_SKINNY_WAVES (experiments) only: the LDS rule of group sizes 64 / 32 and of the multi launch, and the
+  // multi launch's split, count blocks of the knob's width, not of the four waves that are launched.
+  const int fit_waves = small || multi ? knob_waves : p.waves;
+  p.split_waves = multi ? knob_waves : p.waves;
+  const int tiles = p.tiles = (int)(g96 ? g.K / 96 : g.K / 128);
+  bool shape;
+  if (g96)
+    shape = g.N % 64 == 0 && g.K % 96 == 0 && g.K >= 192;
+  else if (int2)
+    shape = g.C == 128 && g.N % 64 == 0 && g.K % 128 == 0;
+  else
+    shape = g.bits == 4 && (g.C == 128 || (small && g.N % 64 == 0) || p.per_channel) && g.N % 16 == 0 && g.K % 128 == 0;
+  p.served = shape && M >= 1 && M <= QUANTO_HIP_SKINNY_MAX_M && (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && g.N < (1 << 30) &&
+             g.K < (1 << 30) && lds_bytes(call_tf, 4, tiles * p.gpt, fit_waves, p.planes) <= kMaxLdsBytes;  // the unsplit 4-stage ring fits
+  return p;
 }
 
-// group sizes 64 / 32: 64-feature blocks, 4-stage ring, two wave sets from two token fragments on (as the group-size-128 form)
-template <int DT, bool INT_SHIFT, int TF, int GPT>
-static int launch_small_groups(const Args& a, hipStream_t stream) {
-  const int lds = lds_bytes(TF, 4, a.K / BK / a.S * GPT, 4);
-  return launch_k<DT, TF, 4, INT_SHIFT, 4, false, (TF >= 2 ? 2 : 1), GPT>(a, stream, Segs{}, a.N / 64 * a.S, lds);
-}
-template <int DT, bool INT_SHIFT, int GPT>
-static int launch_small_groups_tf(const Args& a, hipStream_t stream) {
-  if (a.M <= 16) return launch_small_groups<DT, INT_SHIFT, 1, GPT>(a, stream);
-  if (a.M <= 32) return launch_small_groups<DT, INT_SHIFT, 2, GPT>(a, stream);
-  return launch_small_groups<DT, INT_SHIFT, 4, GPT>(a, stream);
-}
-
-// qint2 (four planes per byte): 64-feature blocks, 4-stage ring, two wave sets from two token fragments on
-template <int DT, bool INT_SHIFT, int TF>
-static int launch_int2(const Args& a, hipStream_t stream) {
-  const int lds = lds_bytes(TF, 4, a.K / BK / a.S, 4, 4);
-  return launch_k<DT, TF, 4, INT_SHIFT, 4, false, (TF >= 2 ? 2 : 1), 1, 4>(a, stream, Segs{}, a.N / 64 * a.S, lds);
-}
-
-// group size 96 (r4): tiles of 96 k, 64-feature blocks, 4-stage ring, two wave sets from two token fragments on
-template <int DT, bool INT_SHIFT, int TF>
-static int launch_g96(const Args& a, hipStream_t stream) {
-  const int lds = lds_bytes(TF, 4, a.K / 96 / a.S, 4);
-  return launch_k<DT, TF, 4, INT_SHIFT, 4, false, (TF >= 2 ? 2 : 1), 1, 2, 96>(a, stream, Segs{}, a.N / 64 * a.S, lds);
-}
-
-template <int DT, bool INT_SHIFT>
-static int launch_tf(const Args& a, hipStream_t stream, const Segs* segs = nullptr, int total_fb = 0) {
-  if (a.tk == 96) {
-    if (a.M <= 16) return launch_g96<DT, INT_SHIFT, 1>(a, stream);
-    if (a.M <= 32) return launch_g96<DT, INT_SHIFT, 2>(a, stream);
-    return launch_g96<DT, INT_SHIFT, 4>(a, stream);
-  }
-  if (a.planes == 4) {
-    if (a.M <= 16) return launch_int2<DT, INT_SHIFT, 1>(a, stream);
-    if (a.M <= 32) return launch_int2<DT, INT_SHIFT, 2>(a, stream);
-    return launch_int2<DT, INT_SHIFT, 4>(a, stream);
-  }
-  if (a.gpt == 2) return launch_small_groups_tf<DT, INT_SHIFT, 2>(a, stream);
-  if (a.gpt == 4) return launch_small_groups_tf<DT, INT_SHIFT, 4>(a, stream);
-  if (a.M <= 16) return launch_waves<DT, INT_SHIFT, 1>(a, stream, segs, total_fb);
-  if (a.M <= 32) return launch_waves<DT, INT_SHIFT, 2>(a, stream, segs, total_fb);
-  return launch_waves<DT, INT_SHIFT, 4>(a, stream, segs, total_fb);
-}
-
-}  // namespace skinny
-
-// Split factor.  r2 measurements (M = 32, K = 4096, us per launch, S = 1 / 2 / 4 / 8 with three blocks per CU): N = 4096
-// - / 13.6 / 10.6 / 12.3, N = 14336 22.4 (one block per CU) / 17.3 / 21.4 / 28.1: the best split gives the chip 250-500 blocks of
-// four waves (two to three co-resident blocks per CU hide each other's barrier and reduction stalls), never leaves a block
-// fewer than 8 groups (its DMA ring would barely fill) and must divide the group count.
-static int skinny_split(const PackedGeom& g, int64_t M) {
-  const int forced = env_int("QUANTO_HIP_SKINNY_SPLIT", 0);  // experiments
-  const int tf = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-  // group sizes 64 / 32 always launch 64-feature blocks (launch_small_groups), whatever the wave knob says
-  const bool g96 = g.C == 96 && g.K != 96;
-  const int blocks = (g.C == 64 || g.C == 32 || g96 || g.bits == 2) ? (int)(g.N / 64) : (int)(g.N / (16 * skinny::pick_waves((int)g.N, tf)));
+static Plan make_plan(int64_t M, const PackedGeom& g, int dtype, bool multi, size_t workspace_bytes) {
+  Plan p = plan_format(M, g, dtype, multi);
+  if (!p.served) return p;
+  const int call_tf = fragments(M > 64 ? 64 : M), tiles = p.tiles;
+  const bool g96 = p.tk == 96;
+  // Split factor.  r2 measurements (M = 32, K = 4096, us per launch, S = 1 / 2 / 4 / 8 with three blocks per CU): N = 4096
+  // - / 13.6 / 10.6 / 12.3, N = 14336 22.4 (one block per CU) / 17.3 / 21.4 / 28.1: the best split gives the chip 250-500 blocks of
+  // four waves (two to three co-resident blocks per CU hide each other's barrier and reduction stalls), never leaves a block
+  // fewer than 8 groups (its DMA ring would barely fill) and must divide the tile count.
+  const int blocks = (int)(g.N / 16) / p.split_waves;
   int s = 1;
-  const int tiles = (int)(g.K / (g96 ? 96 : 128));  // 128-k tiles (= groups of 128), or groups of 96
   while (s < 8 && blocks * s * 2 <= 512 && tiles % (s * 2) == 0 && tiles / (s * 2) >= 8) s *= 2;
   // K = 96 j with j not a multiple of 4: the largest divisor of the tile count under the same bounds, not only powers of two, while the partial
   // sums are small (us, bf16, N = 4096, K = 4800 = 50 tiles, split 2 -> 5: M = 32 17.0 -> 13.5, but M = 64 20.3 -> 22.1, M = 128 39.3 -> 41.8)
-  if (g96 && tf <= 2)
+  if (g96 && call_tf <= 2)
     for (int d = 8; d > s; --d)
       if (tiles % d == 0 && blocks * d <= 512 && tiles / d >= 8) {
         s = d;
         break;
       }
+  const int forced = env_int("QUANTO_HIP_SKINNY_SPLIT", 0);  // experiments
   if (forced > 0 && tiles % forced == 0) s = forced;
   if (!ws_counters_fit(blocks)) s = 1;  // one counter per feature block
-  return s;
+  // [counters (zero on entry, zero on exit) | fp32 partial sums, fragment-major]; the passes of M > 64 reuse it
+  p.workspace = s == 1 ? 0 : QUANTO_HIP_WS_COUNTER_BYTES + (size_t)(g.N / 16) * s * 64 * call_tf * 16;
+  p.S = workspace_bytes >= p.workspace ? s : 1;
+  p.grid = (int)(g.N / 16) / p.waves * p.S;
+  return p;
 }
 
-bool qbits_skinny_supported(int64_t M, const PackedGeom& g, int dtype) {
-  const int64_t Mp = M > 64 ? 64 : M;  // rows per pass
-  const int tf = Mp <= 16 ? 1 : (Mp <= 32 ? 2 : 4);
-  // group sizes 128, 64, 32 (1, 2, 4 groups per 128-k tile) and per-channel scales (r3: the formats nn/qmodule.py:121-129 selects
-  // when in_features is not a multiple of 128 or the caller asks for them no longer leave the streaming kernel)
-  const bool per_channel = g.C == g.K && g.C != 128;
-  const bool grouped = g.C == 128 || ((g.C == 64 || g.C == 32) && g.N % 64 == 0);
-  const int groups = per_channel ? (int)(g.K / 128) : (int)g.G;
-  if (g.bits == 4 && g.C == 96 && !per_channel)  // group size 96 (r4): tiles of 96 k, 64-feature blocks
-    return g.N % 64 == 0 && g.K % 96 == 0 && g.K >= 192 && M >= 1 && M <= QUANTO_HIP_SKINNY_MAX_M &&
-           (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && g.N < (1 << 30) && g.K < (1 << 30) &&
-           skinny::lds_bytes(tf, 4, (int)g.G, 4) <= kMaxLdsBytes;
-  if (g.bits == 2)  // qint2 (r4): group size 128, 64-feature blocks (16 packed rows x 4 planes)
-    return g.C == 128 && g.N % 64 == 0 && g.K % 128 == 0 && M >= 1 && M <= QUANTO_HIP_SKINNY_MAX_M &&
-           (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && g.N < (1 << 30) && g.K < (1 << 30) &&
-           skinny::lds_bytes(tf, 4, (int)g.G, 4, 4) <= kMaxLdsBytes;
-  return g.bits == 4 && (grouped || per_channel) && (g.N % 16 == 0) && (g.K % 128 == 0) && M >= 1 && M <= QUANTO_HIP_SKINNY_MAX_M &&
-         (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && g.N < (1 << 30) && g.K < (1 << 30) &&
-         skinny::lds_bytes(tf, 4, groups, skinny::pick_waves((int)g.N)) <= kMaxLdsBytes;
+// The block and ring of one pass of `rows` rows (the short last pass of M > 64 has fewer fragments than the others).  Deepest DMA pipeline that fits
+// the LDS budget per block: the kernel is latency-bound per block (bytes in flight = stages x tile bytes).  50 KiB = three blocks per CU; a deeper
+// ring with the CU to itself is slower: (32,4096,4096) 11.5 us at 150 KiB, 11.0 at 76, 10.6 at 50; (32,4096,14336) split 2: 28.3 / 17.8 / 17.3 us
+static void plan_pass(Plan& p, int rows) {
+  p.rows = rows;
+  p.tf = fragments(rows);
+  p.sets = p.waves == 4 && p.tf >= 2 ? 2 : 1;
+  const int G = p.tiles / p.S * p.gpt;  // groups in a block's LDS tables
+  p.stages = 4;
+  if (!p.one_form) {
+    const int budget = env_int("QUANTO_HIP_SKINNY_LDS_KB", 50) * 1024;
+    for (int st = 8; st > 4 && p.stages == 4; st -= 2)
+      if (ring_countable(st, p.tf, p.waves) && lds_bytes(p.tf, st, G, p.waves) <= budget) p.stages = st;
+  }
+  p.lds = lds_bytes(p.tf, p.stages, G, p.waves, p.planes);
 }
 
-// [counters (zero on entry, zero on exit) | fp32 partial sums]; 0 when the problem is not split
-size_t qbits_skinny_workspace(int64_t M, const PackedGeom& g) {
-  const int S = skinny_split(g, M);
-  if (S == 1) return 0;
-  const int tf = M <= 16 ? 1 : (M <= 32 ? 2 : 4);  // M > 64 runs in passes of 64 rows, which reuse the workspace
-  return QUANTO_HIP_WS_COUNTER_BYTES + (size_t)(g.N / 16) * S * 64 * tf * 16;
+template <int DT, int TF, int STAGES, bool INT_SHIFT, int WAVES, bool MULTI, int SETS, int GPT = 1, int PLANES = 2, int TK = 128>
+static int launch_k(const Plan& p, const Args& a, const Segs& segs, hipStream_t stream) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbits_skinny_kernel<DT, TF, STAGES, INT_SHIFT, WAVES, MULTI, SETS, GPT, PLANES, TK>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+  hipLaunchKernelGGL((qbits_skinny_kernel<DT, TF, STAGES, INT_SHIFT, WAVES, MULTI, SETS, GPT, PLANES, TK>), dim3(p.grid), dim3(WAVES * SETS * 64), p.lds, stream,
+                     a, segs);
+  return launch_status();
 }
 
-int qbits_mm_skinny(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                    const PackedGeom& g, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!qbits_skinny_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
+// ---- plan -> instantiation: the only place that names them ----------------------------------------------------------------------------------------
+// group sizes 96 / 64 / 32 and int2: 64-feature blocks, the 4-stage ring, one Linear
+template <int DT, bool INT_SHIFT, int GPT, int PLANES, int TK>
+static int launch_one_form(const Plan& p, const Args& a, const Segs& segs, hipStream_t stream) {
+  if (p.tf == 1) return launch_k<DT, 1, 4, INT_SHIFT, 4, false, 1, GPT, PLANES, TK>(p, a, segs, stream);
+  if (p.tf == 2) return launch_k<DT, 2, 4, INT_SHIFT, 4, false, 2, GPT, PLANES, TK>(p, a, segs, stream);
+  return launch_k<DT, 4, 4, INT_SHIFT, 4, false, 2, GPT, PLANES, TK>(p, a, segs, stream);
+}
+
+// group size 128 and per-channel scales: 4 / 2 / 1 waves x every ring depth vmcnt can count; on 4 waves also the multi launch, and two wave sets
+template <int DT, int TF, int STAGES, bool INT_SHIFT, int WAVES>
+static int launch_sets(const Plan& p, const Args& a, const Segs& segs, bool multi, hipStream_t stream) {
+  if constexpr (WAVES == 4) {
+    constexpr int SETS = TF >= 2 ? 2 : 1;  // make_plan's rule
+    if (multi) return launch_k<DT, TF, STAGES, INT_SHIFT, 4, true, SETS>(p, a, segs, stream);
+    if constexpr (SETS == 2)
+      if (p.sets == 2) return launch_k<DT, TF, STAGES, INT_SHIFT, 4, false, 2>(p, a, segs, stream);
+  }
+  // (on 4 waves from two fragments on, this one-set form is one no plan asks for: it was instantiated before, and still is)
+  return launch_k<DT, TF, STAGES, INT_SHIFT, WAVES, false, 1>(p, a, segs, stream);
+}
+
+template <int DT, bool INT_SHIFT, int TF, int WAVES>
+static int launch_ring(const Plan& p, const Args& a, const Segs& segs, bool multi, hipStream_t stream) {
+  if constexpr (ring_countable(8, TF, WAVES))
+    if (p.stages == 8) return launch_sets<DT, TF, 8, INT_SHIFT, WAVES>(p, a, segs, multi, stream);
+  if constexpr (ring_countable(6, TF, WAVES))
+    if (p.stages == 6) return launch_sets<DT, TF, 6, INT_SHIFT, WAVES>(p, a, segs, multi, stream);
+  return launch_sets<DT, TF, 4, INT_SHIFT, WAVES>(p, a, segs, multi, stream);
+}
+
+template <int DT, bool INT_SHIFT, int TF>
+static int launch_waves(const Plan& p, const Args& a, const Segs& segs, bool multi, hipStream_t stream) {
+  if (p.waves == 4) return launch_ring<DT, INT_SHIFT, TF, 4>(p, a, segs, multi, stream);
+  if (p.waves == 2) return launch_ring<DT, INT_SHIFT, TF, 2>(p, a, segs, multi, stream);
+  return launch_ring<DT, INT_SHIFT, TF, 1>(p, a, segs, multi, stream);
+}
+
+template <int DT, bool INT_SHIFT>
+static int launch(const Plan& p, const Args& a, const Segs& segs, bool multi, hipStream_t stream) {
+  if (p.tk == 96) return launch_one_form<DT, INT_SHIFT, 1, 2, 96>(p, a, segs, stream);
+  if (p.planes == 4) return launch_one_form<DT, INT_SHIFT, 1, 4, 128>(p, a, segs, stream);
+  if (p.gpt == 2) return launch_one_form<DT, INT_SHIFT, 2, 2, 128>(p, a, segs, stream);
+  if (p.gpt == 4) return launch_one_form<DT, INT_SHIFT, 4, 2, 128>(p, a, segs, stream);
+  if (p.tf == 1) return launch_waves<DT, INT_SHIFT, 1>(p, a, segs, multi, stream);
+  if (p.tf == 2) return launch_waves<DT, INT_SHIFT, 2>(p, a, segs, multi, stream);
+  return launch_waves<DT, INT_SHIFT, 4>(p, a, segs, multi, stream);
+}
+
+// One host path: `l.nseg` Linears sharing x (the plain op is nseg = 1, the kernel without the segment lookup), `g` the geometry of the launch.
+static int run(const void* x, const Linears& l, int64_t M, const PackedGeom& g, int dtype, bool int_shift, void* workspace, size_t workspace_bytes,
+               hipStream_t stream) {
+  const bool multi = l.nseg > 1;
   // split-K only with a workspace (whose counter words the caller guarantees to be zero); without one: one block per feature block
-  int S = skinny_split(g, M > 64 ? 64 : M);
-  if (S > 1 && !ws_holds(workspace, workspace_bytes, qbits_skinny_workspace(M, g))) S = 1;
-  const bool per_channel = g.C == g.K && g.C != 128;
+  const size_t ws_bytes = ws_holds(workspace, workspace_bytes, 0) ? workspace_bytes : 0;
+  Plan p = make_plan(M, g, dtype, multi, ws_bytes);
+  if (!p.served) return QUANTO_HIP_ENOTSUP;
+  if (l.align % 16) return QUANTO_HIP_EALIGN;
+  Segs segs;
+  fill_segments(
+      l.nseg, segs.first_fb,
+      [&](int i, int j) {
+        segs.w[i] = reinterpret_cast<const uint8_t*>(l.w[j]);
+        segs.scale[i] = l.scale[j];
+        segs.shift[i] = l.shift[j];
+        segs.bias[i] = l.bias[j];
+        segs.y[i] = l.y[j];
+        segs.N[i] = l.N[j];
+      },
+      [&](int i) { return l.N[i] / 64; });
   const size_t esize = 2;  // bf16 / fp16
-  for (int64_t m0 = 0; m0 < M; m0 += 64) {  // passes of up to 64 rows (stream-ordered: each pass leaves the counters zero)
-    const int64_t rows = M - m0 < 64 ? M - m0 : 64;
-    skinny::Args a{reinterpret_cast<const uint8_t*>(x) + (size_t)m0 * g.K * esize, packed, scale, shift, bias,
-                   reinterpret_cast<uint8_t*>(y) + (size_t)m0 * g.N * esize, (int)rows, (int)g.N, (int)g.K, (int)g.G, S,
-                   reinterpret_cast<int*>(workspace),
-                   S > 1 ? ws_partials(workspace) : nullptr,
-                   per_channel ? 1 : (int)(128 / g.C), per_channel ? 1 : 0, g.bits == 2 ? 4 : 2, (g.C == 96 && !per_channel) ? 96 : 128,
-                   // later passes of a multi-pass call re-read the weights from the Infinity Cache: keep them cacheable there
-                   env_int("QUANTO_HIP_SKINNY_NT", M <= 64 ? 1 : 0), env_int("QUANTO_HIP_SKINNY_ABLATE", 0),
-                   reinterpret_cast<unsigned long long*>(env_ptr("QUANTO_HIP_SKINNY_TIMELINE"))};
+  for (int64_t m0 = 0; m0 < M; m0 += 64) {  // passes of up to 64 rows (stream-ordered: each pass leaves the counters zero); multi: M <= 64
+    const int rows = (int)(M - m0 < 64 ? M - m0 : 64);
+    if (rows != p.rows) plan_pass(p, rows);
+    const Args a{reinterpret_cast<const uint8_t*>(x) + (size_t)m0 * g.K * esize, segs.w[0], segs.scale[0], segs.shift[0], segs.bias[0],
+                 reinterpret_cast<uint8_t*>(segs.y[0]) + (size_t)m0 * g.N * esize, rows, segs.N[0], (int)g.K, (int)g.G, p.S,
+                 reinterpret_cast<int*>(workspace), p.S > 1 ? ws_partials(workspace) : nullptr, p.gpt, p.per_channel, p.planes, p.tk,
+                 // later passes of a multi-pass call re-read the weights from the Infinity Cache: keep them cacheable there
+                 env_int("QUANTO_HIP_SKINNY_NT", M <= 64 ? 1 : 0),
+                 // the timing experiments of the plain op (bench.py --ablate, scripts/skinny_timeline.py)
+                 multi ? 0 : env_int("QUANTO_HIP_SKINNY_ABLATE", 0),
+                 multi ? nullptr : reinterpret_cast<unsigned long long*>(env_ptr("QUANTO_HIP_SKINNY_TIMELINE"))};
     int r;
     if (dtype == QUANTO_HIP_BF16)
-      r = int_shift ? skinny::launch_tf<QUANTO_HIP_BF16, true>(a, stream) : skinny::launch_tf<QUANTO_HIP_BF16, false>(a, stream);
+      r = int_shift ? launch<QUANTO_HIP_BF16, true>(p, a, segs, multi, stream) : launch<QUANTO_HIP_BF16, false>(p, a, segs, multi, stream);
     else
-      r = int_shift ? skinny::launch_tf<QUANTO_HIP_F16, true>(a, stream) : skinny::launch_tf<QUANTO_HIP_F16, false>(a, stream);
+      r = int_shift ? launch<QUANTO_HIP_F16, true>(p, a, segs, multi, stream) : launch<QUANTO_HIP_F16, false>(p, a, segs, multi, stream);
     if (r != QUANTO_HIP_OK) return r;
   }
   return QUANTO_HIP_OK;
 }
 
+}  // namespace skinny
+
+bool qbits_skinny_supported(int64_t M, const PackedGeom& g, int dtype) { return skinny::plan_format(M, g, dtype, false).served; }
+// 0 as well when the shape is not served
+size_t qbits_skinny_workspace(int64_t M, const PackedGeom& g, int dtype) { return skinny::make_plan(M, g, dtype, false, SIZE_MAX).workspace; }
+
+int qbits_mm_skinny(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
+                    const PackedGeom& g, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const void* w = packed;
+  return skinny::run(x, gather_linears(x, 1, &w, &scale, &shift, &bias, &y, &g.N), M, g, dtype, int_shift, workspace, workspace_bytes, stream);
+}
+
 // ---- several Linears with a shared input in one launch (5 <= M <= 64) --------------------------------------------------------
 // Per-call fixed costs of the streaming kernel (launch, first-byte latency, split-K tail: ~7.7 of the 10.6 us of a
 // (32,4096,4096) call) are paid once for q/k/v or gate/up, and the wider grid needs a smaller split (gate+up of
-// Llama-3-8B: 448 feature blocks -> no split at all).
-static PackedGeom multi_geom(int nseg, const int64_t* N, int64_t K) {
+// Llama-3-8B: 448 feature blocks -> no split at all).  The launch's geometry: all features, int4, group size 128.
+static bool multi_geom(int nseg, const int64_t* N, int64_t M, int64_t K, PackedGeom* g) {
+  if (nseg < 1 || nseg > skinny::MAX_SEGS || M < 1 || M > 64) return false;
   int64_t total = 0;
-  for (int i = 0; i < nseg; ++i) total += N[i];
-  return make_geom(total, K, 4, 128);
+  for (int i = 0; i < nseg; ++i) {
+    if (N[i] <= 0 || N[i] % 64) return false;  // 4-wave blocks only
+    total += N[i];
+  }
+  *g = make_geom(total, K, 4, 128);
+  return true;
 }
 
 bool qbits_skinny_multi_supported(int nseg, const int64_t* N, int64_t M, int64_t K, int dtype) {
-  if (nseg < 1 || nseg > skinny::MAX_SEGS || M < 1 || M > 64) return false;
-  for (int i = 0; i < nseg; ++i)
-    if (N[i] <= 0 || N[i] % 64) return false;  // 4-wave blocks only
-  return qbits_skinny_supported(M, multi_geom(nseg, N, K), dtype);
+  PackedGeom g;
+  return multi_geom(nseg, N, M, K, &g) && skinny::plan_format(M, g, dtype, true).served;
 }
 
-size_t qbits_skinny_multi_workspace(int nseg, const int64_t* N, int64_t M, int64_t K) { return qbits_skinny_workspace(M, multi_geom(nseg, N, K)); }
+size_t qbits_skinny_multi_workspace(int nseg, const int64_t* N, int64_t M, int64_t K) {
+  PackedGeom g;
+  return multi_geom(nseg, N, M, K, &g) ? skinny::make_plan(M, g, QUANTO_HIP_BF16, true, SIZE_MAX).workspace : 0;
+}
 
 int qbits_mm_skinny_multi(const void* x, int nseg, const uint8_t* const* packed, const void* const* scale, const void* const* shift,
                           const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, int dtype, bool int_shift,
                           void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!qbits_skinny_multi_supported(nseg, N, M, K, dtype)) return QUANTO_HIP_ENOTSUP;
-  const PackedGeom g = multi_geom(nseg, N, K);
-  uintptr_t align = reinterpret_cast<uintptr_t>(x);
-  skinny::Segs segs;
-  int fb = 0;
-  for (int i = 0; i < skinny::MAX_SEGS; ++i) {
-    const int j = i < nseg ? i : 0;  // unused slots repeat segment 0 and are never selected
-    segs.w[i] = packed[j];
-    segs.scale[i] = scale[j];
-    segs.shift[i] = shift[j];
-    segs.bias[i] = bias ? bias[j] : nullptr;
-    segs.y[i] = y[j];
-    segs.N[i] = (int)N[j];
-    segs.first_fb[i] = i < nseg ? fb : 0x7FFFFFFF;
-    if (i < nseg) {
-      fb += (int)(N[i] / 64);
-      align |= reinterpret_cast<uintptr_t>(packed[i]);
-    }
-  }
-  if (align % 16) return QUANTO_HIP_EALIGN;
-  int S = skinny_split(g, M);
-  if (S > 1 && !ws_holds(workspace, workspace_bytes, qbits_skinny_workspace(M, g))) S = 1;
-  skinny::Args a{x, packed[0], scale[0], shift[0], bias ? bias[0] : nullptr, y[0], (int)M, (int)N[0], (int)K, (int)g.G, S,
-                 reinterpret_cast<int*>(workspace),
-                 S > 1 ? ws_partials(workspace) : nullptr, 1, 0, 2, 128,
-                 env_int("QUANTO_HIP_SKINNY_NT", 1), 0, nullptr};
-  if (dtype == QUANTO_HIP_BF16)
-    return int_shift ? skinny::launch_tf<QUANTO_HIP_BF16, true>(a, stream, &segs, fb) : skinny::launch_tf<QUANTO_HIP_BF16, false>(a, stream, &segs, fb);
-  return int_shift ? skinny::launch_tf<QUANTO_HIP_F16, true>(a, stream, &segs, fb) : skinny::launch_tf<QUANTO_HIP_F16, false>(a, stream, &segs, fb);
+  PackedGeom g;
+  if (!multi_geom(nseg, N, M, K, &g)) return QUANTO_HIP_ENOTSUP;
+  return skinny::run(x, gather_linears(x, nseg, reinterpret_cast<const void* const*>(packed), scale, shift, bias, y, N), M, g, dtype, int_shift, workspace,
+                     workspace_bytes, stream);
 }
 
 }  // namespace qh

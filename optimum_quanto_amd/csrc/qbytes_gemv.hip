@@ -176,37 +176,27 @@ __global__ void __launch_bounds__(256) qbytes_gemv_kernel(const uint16_t* __rest
   }
 }
 
-struct GemvProblem8 {
-  int nseg;
-  const void* w[MAX_SEGS8];
-  const void* s[MAX_SEGS8];
-  const void* bias[MAX_SEGS8];
-  void* y[MAX_SEGS8];
-  int N[MAX_SEGS8];
-};
-
 template <int DT, int BDT, int MT>
-static int launch_iters(const void* x, const GemvProblem8& pb, int m0, int K, hipStream_t stream) {
+static int launch_iters(const void* x, const Linears& l, int m0, int K, hipStream_t stream) {
   const int nslab = (K + 1023) / 1024;
   const int wpr = nslab >= 3 ? 4 : nslab;  // 1, 2 or 4 waves per row group
   const int iters = (nslab + wpr - 1) / wpr;
   if (iters > 4) return QUANTO_HIP_ENOTSUP;
   const int rows_per_block = RR8 * (4 / wpr);
-  GemvSegs8 segs;
-  int grid = 0;
-  for (int i = 0; i < MAX_SEGS8; ++i) {
-    const int j = i < pb.nseg ? i : 0;  // unused slots repeat segment 0 and are never selected
-    segs.w[i] = reinterpret_cast<const uint8_t*>(pb.w[j]);
-    segs.scales[i] = reinterpret_cast<const uint16_t*>(pb.s[j]);
-    segs.bias[i] = reinterpret_cast<const uint16_t*>(pb.bias[j]);
-    segs.y[i] = reinterpret_cast<uint16_t*>(pb.y[j]) + (size_t)m0 * pb.N[j];
-    segs.N[i] = pb.N[j];
-    segs.first_block[i] = i < pb.nseg ? grid : 0x7FFFFFFF;
-    if (i < pb.nseg) grid += (pb.N[i] + rows_per_block - 1) / rows_per_block;
-  }
+  GemvSegs8 segs;  // `l.nseg` Linears sharing x (nseg = 1 for the plain op; qh_common.h)
+  const int grid = fill_segments(
+      l.nseg, segs.first_block,
+      [&](int i, int j) {
+        segs.w[i] = reinterpret_cast<const uint8_t*>(l.w[j]);
+        segs.scales[i] = reinterpret_cast<const uint16_t*>(l.scale[j]);
+        segs.bias[i] = reinterpret_cast<const uint16_t*>(l.bias[j]);
+        segs.y[i] = reinterpret_cast<uint16_t*>(l.y[j]) + (size_t)m0 * l.N[j];
+        segs.N[i] = l.N[j];
+      },
+      [&](int i) { return (l.N[i] + rows_per_block - 1) / rows_per_block; });
   auto xs = reinterpret_cast<const uint16_t*>(x) + (size_t)m0 * K;
 #define QH_LAUNCH(IT)                                                                                                           \
-  if (pb.nseg > 1)                                                                                                              \
+  if (l.nseg > 1)                                                                                                               \
     hipLaunchKernelGGL((qbytes_gemv_kernel<DT, BDT, MT, IT, true>), dim3(grid), dim3(256), 0, stream, xs, segs, K, wpr);         \
   else                                                                                                                          \
     hipLaunchKernelGGL((qbytes_gemv_kernel<DT, BDT, MT, IT, false>), dim3(grid), dim3(256), 0, stream, xs, segs, K, wpr)
@@ -221,19 +211,19 @@ static int launch_iters(const void* x, const GemvProblem8& pb, int m0, int K, hi
 }
 
 template <int DT, int BDT>
-static int launch_m(const void* x, const GemvProblem8& pb, int M, int K, hipStream_t stream) {
+static int launch_m(const void* x, const Linears& l, int M, int K, hipStream_t stream) {
   int m0 = 0;
   while (m0 < M) {  // x lives in registers as fp32 (16 VGPRs per slab and row): two rows per pass, later passes hit the MALL
     const int mt = (M - m0) >= 2 ? 2 : 1;
-    const int st = mt == 2 ? launch_iters<DT, BDT, 2>(x, pb, m0, K, stream) : launch_iters<DT, BDT, 1>(x, pb, m0, K, stream);
+    const int st = mt == 2 ? launch_iters<DT, BDT, 2>(x, l, m0, K, stream) : launch_iters<DT, BDT, 1>(x, l, m0, K, stream);
     if (st != QUANTO_HIP_OK) return st;
     m0 += mt;
   }
   return QUANTO_HIP_OK;
 }
 
-static int gemv8_dispatch(const void* a, const GemvProblem8& pb, int M, int K, int b_dtype, int out_dtype, hipStream_t stream) {
-#define QH_CASE(DT, BDT) return launch_m<DT, BDT>(a, pb, M, K, stream)
+static int gemv8_dispatch(const void* a, const Linears& l, int M, int K, int b_dtype, int out_dtype, hipStream_t stream) {
+#define QH_CASE(DT, BDT) return launch_m<DT, BDT>(a, l, M, K, stream)
   if (out_dtype == QUANTO_HIP_BF16) {
     if (b_dtype == QUANTO_HIP_I8) QH_CASE(QUANTO_HIP_BF16, QUANTO_HIP_I8);
     if (b_dtype == QUANTO_HIP_F8_E4M3FN) QH_CASE(QUANTO_HIP_BF16, QUANTO_HIP_F8_E4M3FN);
@@ -256,34 +246,18 @@ bool qbytes_gemv_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_d
 int qbytes_mm_gemv(const void* a, const void* b, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
                    int b_dtype, int out_dtype, hipStream_t stream) {
   if (!qbytes_gemv_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) % 16) return QUANTO_HIP_EALIGN;
-  GemvProblem8 pb{};
-  pb.nseg = 1;
-  pb.w[0] = b;
-  pb.s[0] = s;
-  pb.bias[0] = bias;
-  pb.y[0] = y;
-  pb.N[0] = (int)N;
-  return gemv8_dispatch(a, pb, (int)M, (int)K, b_dtype, out_dtype, stream);
+  const Linears l = gather_linears(a, 1, &b, &s, nullptr, &bias, &y, &N);
+  if (l.align % 16) return QUANTO_HIP_EALIGN;
+  return gemv8_dispatch(a, l, (int)M, (int)K, b_dtype, out_dtype, stream);
 }
 
 // up to QUANTO_HIP_MAX_MULTI weights that share the activation, ONE launch (every member must pass qbytes_gemv_supported)
 int qbytes_mm_gemv_multi(const void* a, int nseg, const void* const* b, const void* const* s, const void* const* bias, void* const* y,
                          const int64_t* N, int64_t M, int64_t K, int b_dtype, int out_dtype, hipStream_t stream) {
   if (nseg < 1 || nseg > MAX_SEGS8) return QUANTO_HIP_EINVAL;
-  GemvProblem8 pb{};
-  pb.nseg = nseg;
-  uintptr_t align = reinterpret_cast<uintptr_t>(a);
-  for (int i = 0; i < nseg; ++i) {
-    pb.w[i] = b[i];
-    pb.s[i] = s[i];
-    pb.bias[i] = bias ? bias[i] : nullptr;
-    pb.y[i] = y[i];
-    pb.N[i] = (int)N[i];
-    align |= reinterpret_cast<uintptr_t>(b[i]);
-  }
-  if (align % 16) return QUANTO_HIP_EALIGN;
-  return gemv8_dispatch(a, pb, (int)M, (int)K, b_dtype, out_dtype, stream);
+  const Linears l = gather_linears(a, nseg, b, s, nullptr, bias, y, N);
+  if (l.align % 16) return QUANTO_HIP_EALIGN;
+  return gemv8_dispatch(a, l, (int)M, (int)K, b_dtype, out_dtype, stream);
 }
 
 }  // namespace qh

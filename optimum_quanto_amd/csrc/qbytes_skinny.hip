@@ -247,82 +247,120 @@ __global__ void __launch_bounds__(256) qbytes_skinny_kernel(Args a, const Segs s
   }
 }
 
+
 constexpr int lds_bytes(int tf, int stages) { return stages * (64 * BK + tf * 16 * BK * 2); }
 
-template <int DT, int FMT, int TF, int STAGES>
-static int launch_s(const Args& a, hipStream_t stream, const Segs* segs = nullptr, int total_fb = 0) {
-  constexpr int lds = lds_bytes(TF, STAGES);
-  if (segs) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_skinny_kernel<DT, FMT, TF, STAGES, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL((qbytes_skinny_kernel<DT, FMT, TF, STAGES, true>), dim3(total_fb * a.S), dim3(256), lds, stream, a, *segs);
-    return launch_status();
-  }
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_skinny_kernel<DT, FMT, TF, STAGES>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((qbytes_skinny_kernel<DT, FMT, TF, STAGES>), dim3((a.N + 63) / 64 * a.S), dim3(256), lds, stream, a, Segs{});
+// Everything the host decides about a call (see skinny::Plan in qbits_skinny.hip, which this follows): qbytes_skinny_supported / _workspace, their
+// _multi forms and the launch read it and nothing else.  Made per call, never kept.
+struct Plan {
+  // the call (make_plan): what the supported / workspace entries answer
+  bool served, multi;
+  int S, grid;         // K split, workgroups = feature blocks of 64 * S
+  size_t workspace;    // bytes the split this shape asks for needs (0: unsplit), whatever the caller then brought
+  // one pass of up to 64 rows (plan_pass): what only the launch needs
+  int rows, tf;        // rows of x and their token fragments of 16: 1, 2 or 4
+  int stages;          // DMA ring depth
+  int lds;             // dynamic LDS bytes
+};
+
+// `N`: all features of the launch (multi: the Linears' N added up); `workspace_bytes`: what the caller's split may use (queries: SIZE_MAX)
+// Three steps, as in qbits_skinny.hip: plan_format ("served": the supported entries), make_plan (+ split, grid, workspace), plan_pass (+ ring).
+constexpr int fragments(int64_t rows) { return rows <= 16 ? 1 : (rows <= 32 ? 2 : 4); }
+static Plan plan_format(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, bool multi) {
+  Plan p{};
+  p.multi = multi;
+  const bool bd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2 || b_dtype == QUANTO_HIP_F8_E4M3FNUZ;
+  p.served = bd && a_dtype == out_dtype && (out_dtype == QUANTO_HIP_BF16 || out_dtype == QUANTO_HIP_F16) && K % BK == 0 && M >= 1 &&
+             M <= QUANTO_HIP_SKINNY_MAX_M && N >= 1 && N < (1 << 30) && K < (1 << 30);
+  return p;
+}
+
+static Plan make_plan(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, bool multi, size_t workspace_bytes) {
+  Plan p = plan_format(M, N, K, a_dtype, b_dtype, out_dtype, multi);
+  if (!p.served) return p;
+  // split: same rule as qbits_skinny.hip - 250-500 blocks, at least 8 tiles per block; one counter per feature block of 64
+  const int blocks = (int)((N + 63) / 64), tiles = (int)(K / BK);
+  int s = 1;
+  while (s < 8 && blocks * s * 2 <= 512 && tiles % (s * 2) == 0 && tiles / (s * 2) >= 8) s *= 2;
+  const int forced = env_int("QUANTO_HIP_SKINNY_SPLIT", 0);  // experiments
+  if (forced > 0 && tiles % forced == 0) s = forced;
+  if (!ws_counters_fit(blocks)) s = 1;
+  // [counters (zero on entry, zero on exit) | fp32 partial sums]; the passes of M > 64 reuse it
+  p.workspace = s == 1 ? 0 : QUANTO_HIP_WS_COUNTER_BYTES + (size_t)blocks * s * 256 * fragments(M > 64 ? 64 : M) * 16;
+  p.S = workspace_bytes >= p.workspace ? s : 1;
+  p.grid = blocks * p.S;
+  return p;
+}
+
+// The ring of one pass of `rows` rows (the short last pass of M > 64 has fewer fragments than the others): 4 stages (48 / 64 KiB: two to three
+// blocks per CU, which hide each other's barrier and reduction stalls - see the measurements in qbits_skinny.hip) unless the experiment knob asks
+// for the deep ring (8 stages, 6 with four fragments: one block per CU); the multi-Linear launch keeps the default ring
+static void plan_pass(Plan& p, int rows) {
+  p.rows = rows;
+  p.tf = fragments(rows);
+  const bool deep = !p.multi && env_int("QUANTO_HIP_SKINNY_LDS_KB", 50) >= 100;
+  p.stages = deep ? (p.tf == 4 ? 6 : 8) : 4;
+  p.lds = lds_bytes(p.tf, p.stages);
+}
+
+// ---- plan -> instantiation: the only place that names them ----------------------------------------------------------------------------------------
+template <int DT, int FMT, int TF, int STAGES, bool MULTI>
+static int launch_k(const Plan& p, const Args& a, const Segs& segs, hipStream_t stream) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_skinny_kernel<DT, FMT, TF, STAGES, MULTI>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            p.lds);
+  hipLaunchKernelGGL((qbytes_skinny_kernel<DT, FMT, TF, STAGES, MULTI>), dim3(p.grid), dim3(256), p.lds, stream, a, segs);
   return launch_status();
+}
+// (the multi form of the deep rings is one no plan asks for: it was instantiated before, and still is)
+template <int DT, int FMT, int TF, int STAGES>
+static int launch_m(const Plan& p, const Args& a, const Segs& segs, bool multi, hipStream_t stream) {
+  return multi ? launch_k<DT, FMT, TF, STAGES, true>(p, a, segs, stream) : launch_k<DT, FMT, TF, STAGES, false>(p, a, segs, stream);
 }
 
 template <int DT, int FMT>
-static int launch_tf(const Args& a, hipStream_t stream, const Segs* segs = nullptr, int total_fb = 0) {
-  if (segs) {  // the multi-Linear launch keeps the default ring
-    if (a.M <= 16) return launch_s<DT, FMT, 1, 4>(a, stream, segs, total_fb);
-    if (a.M <= 32) return launch_s<DT, FMT, 2, 4>(a, stream, segs, total_fb);
-    return launch_s<DT, FMT, 4, 4>(a, stream, segs, total_fb);
+static int launch(const Plan& p, const Args& a, const Segs& segs, bool multi, hipStream_t stream) {
+  if (p.stages == 4) {
+    if (p.tf == 1) return launch_m<DT, FMT, 1, 4>(p, a, segs, multi, stream);
+    if (p.tf == 2) return launch_m<DT, FMT, 2, 4>(p, a, segs, multi, stream);
+    return launch_m<DT, FMT, 4, 4>(p, a, segs, multi, stream);
   }
-  // ring depth: 4 stages (48 / 64 KiB: two to three blocks per CU, which hide each other's barrier and reduction stalls - see the
-  // measurements in qbits_skinny.hip) unless the experiment knob asks for the deep ring (8 stages, one block per CU)
-  const bool deep = env_int("QUANTO_HIP_SKINNY_LDS_KB", 50) >= 100;
-  if (a.M <= 16) return deep ? launch_s<DT, FMT, 1, 8>(a, stream) : launch_s<DT, FMT, 1, 4>(a, stream);
-  if (a.M <= 32) return deep ? launch_s<DT, FMT, 2, 8>(a, stream) : launch_s<DT, FMT, 2, 4>(a, stream);
-  return deep ? launch_s<DT, FMT, 4, 6>(a, stream) : launch_s<DT, FMT, 4, 4>(a, stream);
+  if (p.tf == 1) return launch_m<DT, FMT, 1, 8>(p, a, segs, multi, stream);
+  if (p.tf == 2) return launch_m<DT, FMT, 2, 8>(p, a, segs, multi, stream);
+  return launch_m<DT, FMT, 4, 6>(p, a, segs, multi, stream);
 }
 
-}  // namespace skinny8
-
-static int skinny8_split(int64_t N, int64_t K) {
-  const int forced = env_int("QUANTO_HIP_SKINNY_SPLIT", 0);  // experiments
-  const int blocks = (int)((N + 63) / 64), G = (int)(K / skinny8::BK);
-  int s = 1;  // same rule as qbits_skinny.hip: 250-500 blocks, at least 8 tiles per block
-  while (s < 8 && blocks * s * 2 <= 512 && G % (s * 2) == 0 && G / (s * 2) >= 8) s *= 2;
-  if (forced > 0 && G % forced == 0) s = forced;
-  if (!ws_counters_fit((N + 63) / 64)) s = 1;  // one counter per feature block of 64
-  return s;
-}
-
-bool qbytes_skinny_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  const bool bd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2 || b_dtype == QUANTO_HIP_F8_E4M3FNUZ;
-  return bd && a_dtype == out_dtype && (out_dtype == QUANTO_HIP_BF16 || out_dtype == QUANTO_HIP_F16) && K % skinny8::BK == 0 && M >= 1 &&
-         M <= QUANTO_HIP_SKINNY_MAX_M && N >= 1 && N < (1 << 30) && K < (1 << 30);
-}
-
-// [counters (zero on entry, zero on exit) | fp32 partial sums]; 0 when the problem is not split
-size_t qbytes_skinny_workspace(int64_t M, int64_t N, int64_t K) {
-  const int S = skinny8_split(N, K);
-  if (S == 1) return 0;
-  const int tf = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-  return QUANTO_HIP_WS_COUNTER_BYTES + (size_t)((N + 63) / 64) * S * 256 * tf * 16;
-}
-
-int qbytes_mm_skinny(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
-                     int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!qbytes_skinny_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) % 16) return QUANTO_HIP_EALIGN;
-  int S = skinny8_split(N, K);
-  if (S > 1 && !ws_holds(workspace, workspace_bytes, qbytes_skinny_workspace(M, N, K))) S = 1;
-  for (int64_t m0 = 0; m0 < M; m0 += 64) {
-    const int64_t rows = M - m0 < 64 ? M - m0 : 64;
-    skinny8::Args a{reinterpret_cast<const uint8_t*>(x) + (size_t)m0 * K * 2, reinterpret_cast<const uint8_t*>(w), s, bias,
-                    reinterpret_cast<uint8_t*>(y) + (size_t)m0 * N * 2, (int)rows, (int)N, (int)K, S, reinterpret_cast<int*>(workspace),
-                    S > 1 ? ws_partials(workspace) : nullptr,
-                    env_int("QUANTO_HIP_SKINNY_NT", M <= 64 ? 1 : 0)};
+// One host path: `l.nseg` Linears sharing x (the plain op is nseg = 1, the kernel without the segment lookup), `N` all features of the launch.
+static int run(const void* x, const Linears& l, int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, void* workspace,
+               size_t workspace_bytes, hipStream_t stream) {
+  const bool multi = l.nseg > 1;
+  // split-K only with a workspace (whose counter words the caller guarantees to be zero); without one: one block per feature block
+  const size_t ws_bytes = ws_holds(workspace, workspace_bytes, 0) ? workspace_bytes : 0;
+  Plan p = make_plan(M, N, K, a_dtype, b_dtype, out_dtype, multi, ws_bytes);
+  if (!p.served) return QUANTO_HIP_ENOTSUP;
+  if (l.align % 16) return QUANTO_HIP_EALIGN;
+  Segs segs;
+  fill_segments(
+      l.nseg, segs.first_fb,
+      [&](int i, int j) {
+        segs.w[i] = reinterpret_cast<const uint8_t*>(l.w[j]);
+        segs.scale[i] = l.scale[j];
+        segs.bias[i] = l.bias[j];
+        segs.y[i] = l.y[j];
+        segs.N[i] = l.N[j];
+      },
+      [&](int i) { return l.N[i] / 64; });
+  for (int64_t m0 = 0; m0 < M; m0 += 64) {  // passes of up to 64 rows; multi: M <= 64
+    const int rows = (int)(M - m0 < 64 ? M - m0 : 64);
+    if (rows != p.rows) plan_pass(p, rows);
+    const Args a{reinterpret_cast<const uint8_t*>(x) + (size_t)m0 * K * 2, segs.w[0], segs.scale[0], segs.bias[0],
+                 reinterpret_cast<uint8_t*>(segs.y[0]) + (size_t)m0 * N * 2, rows, segs.N[0], (int)K, p.S, reinterpret_cast<int*>(workspace),
+                 p.S > 1 ? ws_partials(workspace) : nullptr, env_int("QUANTO_HIP_SKINNY_NT", M <= 64 ? 1 : 0)};
     int r;
-#define QH_FMT(DT)                                                                              \
-  r = b_dtype == QUANTO_HIP_I8 ? skinny8::launch_tf<DT, skinny8::W_I8>(a, stream)               \
-      : b_dtype == QUANTO_HIP_F8_E4M3FN ? skinny8::launch_tf<DT, skinny8::W_F8E4M3>(a, stream)  \
-      : b_dtype == QUANTO_HIP_F8_E4M3FNUZ ? skinny8::launch_tf<DT, skinny8::W_F8E4M3FNUZ>(a, stream) \
-                                        : skinny8::launch_tf<DT, skinny8::W_F8E5M2>(a, stream)
+#define QH_FMT(DT)                                                                                            \
+  r = b_dtype == QUANTO_HIP_I8 ? launch<DT, W_I8>(p, a, segs, multi, stream)                                  \
+      : b_dtype == QUANTO_HIP_F8_E4M3FN ? launch<DT, W_F8E4M3>(p, a, segs, multi, stream)                     \
+      : b_dtype == QUANTO_HIP_F8_E4M3FNUZ ? launch<DT, W_F8E4M3FNUZ>(p, a, segs, multi, stream)               \
+                                        : launch<DT, W_F8E5M2>(p, a, segs, multi, stream)
     if (out_dtype == QUANTO_HIP_BF16) {
       QH_FMT(QUANTO_HIP_BF16);
     } else {
@@ -334,62 +372,49 @@ int qbytes_mm_skinny(const void* x, const void* w, const void* s, const void* bi
   return QUANTO_HIP_OK;
 }
 
+}  // namespace skinny8
+
+bool qbytes_skinny_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
+  return skinny8::plan_format(M, N, K, a_dtype, b_dtype, out_dtype, false).served;
+}
+// 0 as well when the shape is not served
+size_t qbytes_skinny_workspace(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
+  return skinny8::make_plan(M, N, K, a_dtype, b_dtype, out_dtype, false, SIZE_MAX).workspace;
+}
+
+int qbytes_mm_skinny(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
+                     int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return skinny8::run(x, gather_linears(x, 1, &w, &s, nullptr, &bias, &y, &N), M, N, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
+}
+
 // ---- several Linears with a shared input in one launch (3 <= M <= 64), see qbits_skinny.hip ------------------------------------
-static int64_t multi_total(int nseg, const int64_t* N) {
+// all features of the launch; 0: not a group this launch takes
+static int64_t multi_total(int nseg, const int64_t* N, int64_t M) {
+  if (nseg < 1 || nseg > skinny8::MAX_SEGS || M < 1 || M > 64) return 0;
   int64_t t = 0;
-  for (int i = 0; i < nseg; ++i) t += N[i];
+  for (int i = 0; i < nseg; ++i) {
+    if (N[i] <= 0 || N[i] % 64) return 0;
+    t += N[i];
+  }
   return t;
 }
 
 bool qbytes_skinny_multi_supported(int nseg, const int64_t* N, int64_t M, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  if (nseg < 1 || nseg > skinny8::MAX_SEGS || M < 1 || M > 64) return false;
-  for (int i = 0; i < nseg; ++i)
-    if (N[i] <= 0 || N[i] % 64) return false;
-  return qbytes_skinny_supported(M, multi_total(nseg, N), K, a_dtype, b_dtype, out_dtype);
+  const int64_t total = multi_total(nseg, N, M);
+  return total > 0 && skinny8::plan_format(M, total, K, a_dtype, b_dtype, out_dtype, true).served;
 }
 
-size_t qbytes_skinny_multi_workspace(int nseg, const int64_t* N, int64_t M, int64_t K) { return qbytes_skinny_workspace(M, multi_total(nseg, N), K); }
+size_t qbytes_skinny_multi_workspace(int nseg, const int64_t* N, int64_t M, int64_t K) {
+  const int64_t total = multi_total(nseg, N, M);
+  return total > 0 ? skinny8::make_plan(M, total, K, QUANTO_HIP_BF16, QUANTO_HIP_I8, QUANTO_HIP_BF16, true, SIZE_MAX).workspace : 0;
+}
 
 int qbytes_mm_skinny_multi(const void* x, int nseg, const void* const* w, const void* const* s, const void* const* bias, void* const* y,
                            const int64_t* N, int64_t M, int64_t K, int a_dtype, int b_dtype, int out_dtype, void* workspace,
                            size_t workspace_bytes, hipStream_t stream) {
-  if (!qbytes_skinny_multi_supported(nseg, N, M, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  const int64_t total = multi_total(nseg, N);
-  uintptr_t align = reinterpret_cast<uintptr_t>(x);
-  skinny8::Segs segs;
-  int fb = 0;
-  for (int i = 0; i < skinny8::MAX_SEGS; ++i) {
-    const int j = i < nseg ? i : 0;  // unused slots repeat segment 0 and are never selected
-    segs.w[i] = reinterpret_cast<const uint8_t*>(w[j]);
-    segs.scale[i] = s[j];
-    segs.bias[i] = bias ? bias[j] : nullptr;
-    segs.y[i] = y[j];
-    segs.N[i] = (int)N[j];
-    segs.first_fb[i] = i < nseg ? fb : 0x7FFFFFFF;
-    if (i < nseg) {
-      fb += (int)(N[i] / 64);
-      align |= reinterpret_cast<uintptr_t>(w[i]);
-    }
-  }
-  if (align % 16) return QUANTO_HIP_EALIGN;
-  int S = skinny8_split(total, K);
-  if (S > 1 && !ws_holds(workspace, workspace_bytes, qbytes_skinny_workspace(M, total, K))) S = 1;
-  skinny8::Args a{x, segs.w[0], s[0], segs.bias[0], y[0], (int)M, (int)N[0], (int)K, S, reinterpret_cast<int*>(workspace),
-                  S > 1 ? ws_partials(workspace) : nullptr,
-                  env_int("QUANTO_HIP_SKINNY_NT", 1)};
-  int r;
-#define QH_FMT(DT)                                                                                        \
-  r = b_dtype == QUANTO_HIP_I8 ? skinny8::launch_tf<DT, skinny8::W_I8>(a, stream, &segs, fb)              \
-      : b_dtype == QUANTO_HIP_F8_E4M3FN ? skinny8::launch_tf<DT, skinny8::W_F8E4M3>(a, stream, &segs, fb) \
-      : b_dtype == QUANTO_HIP_F8_E4M3FNUZ ? skinny8::launch_tf<DT, skinny8::W_F8E4M3FNUZ>(a, stream, &segs, fb) \
-                                        : skinny8::launch_tf<DT, skinny8::W_F8E5M2>(a, stream, &segs, fb)
-  if (out_dtype == QUANTO_HIP_BF16) {
-    QH_FMT(QUANTO_HIP_BF16);
-  } else {
-    QH_FMT(QUANTO_HIP_F16);
-  }
-#undef QH_FMT
-  return r;
+  const int64_t total = multi_total(nseg, N, M);
+  if (total <= 0) return QUANTO_HIP_ENOTSUP;
+  return skinny8::run(x, gather_linears(x, nseg, w, s, nullptr, bias, y, N), M, total, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
 }
 
 }  // namespace qh

@@ -179,6 +179,50 @@ inline bool ws_holds(const void* workspace, size_t workspace_bytes, size_t need)
 constexpr int64_t kMaxGridYZ = 65535;
 inline bool grid_yz_fits(int64_t items, int64_t tile) { return (items + tile - 1) / tile <= kMaxGridYZ; }
 
+// ---- several Linears that share their input in one launch (q/k/v, gate/up): host side of the streaming kernels' segment tables ----------------
+// What the caller handed over, per Linear; the plain op is nseg = 1.  `shift` stays null for the 8-bit products.  `align` ors x and every weight
+// pointer: the streaming kernels want all of them 16-byte aligned.
+struct Linears {
+  int nseg;
+  const void* w[QUANTO_HIP_MAX_MULTI];
+  const void* scale[QUANTO_HIP_MAX_MULTI];
+  const void* shift[QUANTO_HIP_MAX_MULTI];
+  const void* bias[QUANTO_HIP_MAX_MULTI];
+  void* y[QUANTO_HIP_MAX_MULTI];
+  int N[QUANTO_HIP_MAX_MULTI];
+  uintptr_t align;
+};
+// 1 <= nseg <= QUANTO_HIP_MAX_MULTI is the caller's check; `shift` / `bias` may be null arrays.  The plain op passes the addresses of its arguments.
+inline Linears gather_linears(const void* x, int nseg, const void* const* w, const void* const* scale, const void* const* shift, const void* const* bias,
+                              void* const* y, const int64_t* N) {
+  Linears l{};
+  l.nseg = nseg;
+  l.align = reinterpret_cast<uintptr_t>(x);
+  for (int i = 0; i < nseg; ++i) {
+    l.w[i] = w[i];
+    l.scale[i] = scale[i];
+    l.shift[i] = shift ? shift[i] : nullptr;
+    l.bias[i] = bias ? bias[i] : nullptr;
+    l.y[i] = y[i];
+    l.N[i] = (int)N[i];
+    l.align |= reinterpret_cast<uintptr_t>(w[i]);
+  }
+  return l;
+}
+// The one fill of the four segment tables (GemvSegs, GemvSegs8, skinny::Segs, skinny8::Segs: kernel arguments whose members differ in name and type,
+// hence `put(slot, linear)`, which copies one Linear's pointers and N).  Slot i < nseg holds Linear i and first[i] its first workgroup, with
+// `blocks(i)` workgroups per Linear; the unused slots repeat Linear 0 and are never selected: first = INT_MAX.  Returns the workgroups of all Linears.
+template <class Put, class Blocks>
+inline int fill_segments(int nseg, int (&first)[QUANTO_HIP_MAX_MULTI], Put put, Blocks blocks) {
+  int total = 0;
+  for (int i = 0; i < QUANTO_HIP_MAX_MULTI; ++i) {
+    put(i, i < nseg ? i : 0);
+    first[i] = i < nseg ? total : 0x7FFFFFFF;
+    if (i < nseg) total += blocks(i);
+  }
+  return total;
+}
+
 int launch_status();  // hipGetLastError() -> quanto_hip_status (defined in c_api.hip)
 void set_last_kernel(const char* name);
 
