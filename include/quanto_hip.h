@@ -424,6 +424,27 @@ int64_t quanto_hip_qbytes_conv2d_a8_workspace_size(int64_t B, int64_t cin, int64
                                                    int out_dtype);
 
 /*
+ * quanto::qbytes_bmm(Tensor a, Tensor b, Tensor scale, ScalarType out_dtype) -> Tensor
+ *   replaces the aten.bmm handler of quantized activations (tensor/activations/qbytes_ops.py:175-186: both int8 operands cast to fp32, an fp32 bmm,
+ *   a multiply by the scale product, a cast) - the q k^T and p v of an eager attention block - by one batched int8 x int8 product on the 8-bit
+ *   matrix instructions (csrc/qbytes_bmm.hip):
+ *     y[b, m, n] = T( float( sum_k a[b, m, k] * w[b, k, n] ) * scale[0] )
+ *   the sum exact in int32, one round-to-nearest-even to fp32, one fp32 multiply, one rounding to T.  Bit-identical to the fp32 sequence for
+ *   K <= 1024 (all its partial sums are exact integers); beyond, the correctly rounded value of the exact sum where the fp32 bmm rounds partial sums.
+ * a: I8 [B, M, K] at byte strides (a_batch_stride, a_row_stride, 1); w: I8 [B, K, N] at byte strides (w_batch_stride, w_k_stride, w_n_stride) with
+ * w_k_stride == 1 (K contiguous: a transposed view) or w_n_stride == 1 (N contiguous); scale: F32[1] on the device; y: out_dtype[B, M, N], dense,
+ * out_dtype in {F32, F16, BF16}.  Any batch stride, 0 included (an expanded operand); no alignment rule - the load width of each operand (16, 4 or 1
+ * bytes) follows the alignment of its pointer and strides, and no load touches a byte outside the row it reads.
+ * Checked in this order, before any HIP call: a negative size or stride QUANTO_HIP_EINVAL; an out_dtype outside the three float types, neither w stride
+ * equal to 1, K > 131071 (the last K for which K * 128 * 128 fits int32), or B * ceil(M / 64) * ceil(N / 64) >= 2^31 (the workgroups of one launch)
+ * QUANTO_HIP_ENOTSUP; B, M or N == 0 QUANTO_HIP_OK, nothing launched; a NULL scale or y, or a NULL a or w with K > 0, QUANTO_HIP_EINVAL.  K == 0
+ * stores float(0) * scale.  No workspace.  quanto_hip_last_kernel() reports "bmm_i8".
+ */
+int quanto_hip_qbytes_bmm(const void* a, const void* w, const void* scale, void* y, int64_t B, int64_t M, int64_t N, int64_t K,
+                          int64_t a_batch_stride, int64_t a_row_stride, int64_t w_batch_stride, int64_t w_k_stride, int64_t w_n_stride,
+                          int out_dtype, void* stream);
+
+/*
  * Scratch bytes the convolution kernels want for their K split (0: the problem is not split): when the 128 x 128 output tiles alone cannot
  * occupy the chip the K-tiles are dealt over up to 64 workgroups per tile, whose fp32 sums a second kernel adds in split order (deterministic,
  * no atomics, nothing to zero).  K = cin * KH * KW.  Both quanto_hip_q*_conv2d entries take the buffer (16-byte aligned); with NULL / too few

@@ -124,6 +124,7 @@ _PROTOTYPES = {
     "quanto_hip_qbytes_mm_pick": (_ci, [_i64] * 3 + [_ci] * 3),
     "quanto_hip_qbytes_mm_q_ws": (_ci, [_vp] * 6 + [_i64] * 3 + [_ci] * 4 + [_vp, _sz, _vp]),
     "quanto_hip_qbytes_mm_q_plan": (_ci, [_i64] * 3 + [_ci] * 4 + [_pci, _pi64]),
+    "quanto_hip_qbytes_bmm": (_ci, [_vp] * 4 + [_i64] * 9 + [_ci, _vp]),
     "quanto_hip_quantize_symmetric": (_ci, [_vp] * 3 + [_i64] * 2 + [_ci] * 3 + [_vp]),
     "quanto_hip_dequantize_symmetric": (_ci, [_vp] * 3 + [_i64] + [_ci] * 2 + [_vp]),
     "quanto_hip_quantize_affine": (_ci, [_vp] * 4 + [_i64] * 2 + [_ci] * 4 + [_vp]),
@@ -805,6 +806,42 @@ class _Bindings:
             self._check(st, "qbytes_mm_q")
         return yq if a.dim() == 2 else yq.reshape(*a.shape[:-1], N)
 
+    # -- quanto::qbytes_bmm (int8 x int8 batched product of two quantized activations) ------------------------
+    BMM_MAX_K = 131071  # the last K for which K * 128 * 128 fits the int32 accumulator (csrc/qbytes_bmm.hip)
+    BMM_OUT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+    def qbytes_bmm(self, a, b, scale, out_dtype):
+        """``(bmm(a.float(), b.float()) * scale).to(out_dtype)`` for int8 ``a`` [B, M, K] and ``b`` [B, K, N] and a one-element ``scale`` on the
+        device (never read on the host), as one launch of csrc/qbytes_bmm.hip.  The operands are passed as the views they are - pointer and strides,
+        an expanded batch (stride 0) included: ``a`` with K contiguous, ``b`` with K contiguous (a transposed view) or N contiguous; a view whose
+        unit-stride dimension is neither is copied first.  Raises QuantoHipError for what the library does not serve: ``ops.qbytes_bmm_hip`` asks
+        its predicate first."""
+        self._require_cuda(a, b, scale)
+        if not (a.dtype == b.dtype == torch.int8 and a.dim() == b.dim() == 3 and a.shape[0] == b.shape[0] and a.shape[2] == b.shape[1]):
+            raise QuantoHipError(f"qbytes_bmm expects int8 [B, M, K] x [B, K, N], got {a.dtype}{tuple(a.shape)} x {b.dtype}{tuple(b.shape)}")
+        if scale.numel() != 1 or out_dtype not in self.BMM_OUT_DTYPES:
+            raise QuantoHipError("qbytes_bmm expects a one-element scale and a float32 / float16 / bfloat16 output")
+        B, M, K = a.shape
+        N = b.shape[2]
+        if K > 1 and a.stride(2) != 1:
+            a = a.contiguous()
+        # (a dimension of one element is contiguous whatever stride torch reports for it)
+        if K == 1 or b.stride(1) == 1:
+            w_k, w_n = 1, b.stride(2)
+        elif N == 1 or b.stride(2) == 1:
+            w_k, w_n = b.stride(1), 1
+        else:
+            b = b.contiguous()
+            w_k, w_n = N, 1
+        scale = scale.reshape(1).to(torch.float32)
+        y = torch.empty((B, M, N), dtype=out_dtype, device=a.device)
+        with _DeviceGuard(a.device) as stream:
+            st = self._c.quanto_hip_qbytes_bmm(a.data_ptr(), b.data_ptr(), scale.data_ptr(), y.data_ptr(), B, M, N, K, a.stride(0), a.stride(1),
+                                               b.stride(0), w_k, w_n, _DTYPES[out_dtype], stream)
+        if st != 0:
+            self._check(st, "qbytes_bmm")
+        return y
+
 
 class QuantoHipExtension(NativeLibrary):
     """The ``quanto_hip`` extension (name expected by the reference's tests/library/test_extensions.py:23-24)."""
@@ -815,7 +852,7 @@ class QuantoHipExtension(NativeLibrary):
             "quanto_hip",
             root_dir=csrc,
             lib_path=os.path.join(_PKG_DIR, "lib", "libquanto_hip.so"),
-            sources=["c_api.hip", "unpack.hip", "naive_mm.hip", "qbits_gemv.hip", "qbytes_gemv.hip", "qmm_mfma.hip", "qconv_mfma.hip", "qconv_a8.hip", "qconv_depthwise.hip", "qmm_mfma_large.hip", "qmm_large_common.h", "qbits_skinny.hip", "qbits_mmv.hip", "qbits_mfma_fused.hip", "qbits_a8_fused.hip", "qbits_mfma_large.hip", "qbytes_skinny.hip", "qmm_native8.hip", "qmm_f32.hip", "quantize.hip",
+            sources=["c_api.hip", "unpack.hip", "naive_mm.hip", "qbits_gemv.hip", "qbytes_gemv.hip", "qmm_mfma.hip", "qconv_mfma.hip", "qconv_a8.hip", "qconv_depthwise.hip", "qmm_mfma_large.hip", "qmm_large_common.h", "qbits_skinny.hip", "qbits_mmv.hip", "qbits_mfma_fused.hip", "qbits_a8_fused.hip", "qbits_mfma_large.hip", "qbytes_skinny.hip", "qmm_native8.hip", "qmm_f32.hip", "quantize.hip", "qbytes_bmm.hip",
                      "qh_common.h", "qh_conv.h", "qh_group_fused.h", "qh_mfma.h", "qh_quantize.h", os.path.join("..", "..", "include", "quanto_hip.h")],
         )
         self._bindings = None

@@ -193,6 +193,43 @@ def qbytes_mm_q_hip(activations, weights, output_scales, bias, out_scale):
 _register("qbytes_mm_q", "(Tensor A, Tensor B, Tensor scales, Tensor? bias, Tensor out_scale) -> Tensor", qbytes_mm_q_hip, default=qbytes_mm_q_default)
 
 
+# ------------------------------------------------------------------------------------------------
+# quanto::qbytes_bmm: torch.bmm / torch.matmul on two int8 quantized activations (the q k^T and p v of an eager attention block)
+# ------------------------------------------------------------------------------------------------
+def qbytes_bmm_default(a, b, scale, out_dtype):
+    """The two statements of the reference's aten.bmm handler (tensor/activations/qbytes_ops.py:175-186): an fp32 bmm of the casts, times the scale
+    product, cast."""
+    out = torch.bmm(a.to(torch.float32), b.to(torch.float32))
+    return (out * scale).to(out_dtype)
+
+
+def _bmm_kernel_takes(a, b, scale, out_dtype) -> bool:
+    """The predicate of ``qbytes_bmm_hip``: int8 x int8, both 3-D with matching sizes, a one-element scale, a float32 / float16 / bfloat16 output,
+    K <= 131071 (the int32 accumulator) and fewer than 2^31 workgroups (64 x 64 output tiles over all batch members).  No shape class is routed
+    back on speed: profiles/qbmm_vs_sequence.jsonl."""
+    lib = quanto_hip.lib
+    if not (a.dtype == torch.int8 and b.dtype == torch.int8 and a.ndim == 3 and b.ndim == 3 and scale.numel() == 1 and out_dtype in lib.BMM_OUT_DTYPES):
+        return False
+    (nb, m, k), n = a.shape, b.shape[2]
+    if b.shape[0] != nb or b.shape[1] != k or k > lib.BMM_MAX_K:
+        return False
+    return nb * (-(-m // 64) * -(-n // 64)) < (1 << 31)
+
+
+def qbytes_bmm_hip(a, b, scale, out_dtype):
+    """ROCm: one launch of csrc/qbytes_bmm.hip when the predicate says so; everything else runs the fp32 sequence on the device."""
+    if _bmm_kernel_takes(a, b, scale, out_dtype):
+        return quanto_hip.lib.qbytes_bmm(a, b, scale, out_dtype)
+    return qbytes_bmm_default(a, b, scale, out_dtype)
+
+
+# new op: the batched product of two int8 quantized activations on the 8-bit matrix instructions - the exact int32 sum, rounded once to fp32,
+# times the scale product, rounded once to out_dtype.  For K <= 1024 every fp32 partial sum of the sequence above is an exact integer, so the kernel
+# is bit-identical to it; for larger K the fp32 bmm rounds partial sums in an unspecified order and the kernel returns the correctly rounded value of
+# the exact sum - the only observable difference.  On the CPU the default runs.
+_register("qbytes_bmm", "(Tensor a, Tensor b, Tensor scale, ScalarType out_dtype) -> Tensor", qbytes_bmm_hip, default=qbytes_bmm_default)
+
+
 def qbytes_conv2d_default(input, weight, scales, bias, stride, padding, dilation):
     """What the reference computes for F.conv2d on a WeightQBytesTensor (nn/qconv2d.py:54-55 -> qfallback): dequantize, float convolution."""
     w = scales.reshape(-1, 1, 1, 1).to(input.dtype) * weight.to(input.dtype)

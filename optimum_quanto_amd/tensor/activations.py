@@ -153,6 +153,9 @@ def _h_bmm(op, a, b):
         return op(a.dequantize(), b)
     if a.qtype != qint8 or b.qtype != qint8 or (b.axis is not None and b.size() != b._data.size()):
         return qfallback(op, a, b)
+    if b.axis is None and a._scale.numel() == 1 and b._scale.numel() == 1:
+        # both per-tensor: on a ROCm device one int8 x int8 launch on the matrix units (csrc/qbytes_bmm.hip); on the CPU the op's default - the two lines below
+        return torch.ops.quanto.qbytes_bmm(a._data, b._data, (a._scale * b._scale).to(torch.float32), a._scale.dtype)
     out = op(a._data.to(torch.float32), b._data.to(torch.float32))
     return (out * (a._scale * b._scale).to(torch.float32)).to(a._scale.dtype)
 
