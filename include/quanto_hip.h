@@ -445,6 +445,28 @@ int quanto_hip_qbytes_bmm(const void* a, const void* w, const void* scale, void*
                           int out_dtype, void* stream);
 
 /*
+ * quanto::layer_norm_q(Tensor input, int[] normalized_shape, Tensor? weight, Tensor? bias, float eps, Tensor out_scale, ScalarType dtype) -> Tensor
+ *   replaces the two launches of a QLayerNorm with quantized activations (nn/qlayernorm.py: a float layer_norm whose output hook quantizes to
+ *   output_scale) by one (csrc/layernorm_q.hip): the float row is read once and the codes are stored, the float output is never written.
+ *     yq[r, :] = Q( T( (x[r, :] - mean_r) * rstd_r * weight + bias ), out_scale[0] )
+ *   mean and variance in fp32 in two passes over the row in registers (the variance is the mean of squared deviations from the mean),
+ *   rstd = 1 / sqrt(var + eps) correctly rounded, the affine step in fp32 rounded once to T, then the rule of quanto::quantize_symmetric on that element.
+ * x: T [rows, n] with n contiguous elements per row and row_stride >= n elements between rows; weight, bias: T[n] or NULL; out_scale: T[1] on the
+ * device; yq: out_dtype [rows, n], dense.  T = dtype in {F32, F16, BF16}; out_dtype in {I8, F8_E4M3FN, F8_E5M2}.  No alignment rule: loads are 16 bytes
+ * wide when x, weight, bias and the row stride in bytes are multiples of 16 and per element otherwise, stores 8, 4 or 1 bytes wide by the alignment of
+ * yq and n; no access touches a byte outside its row.
+ * Checked in this order, before any HIP call: a negative rows, n or row_stride QUANTO_HIP_EINVAL; a dtype or out_dtype outside the sets above,
+ * n > QUANTO_HIP_LAYER_NORM_Q_MAX_N (the row a workgroup holds in registers) or rows >= 2^31 QUANTO_HIP_ENOTSUP; row_stride < n with more than one row
+ * QUANTO_HIP_EINVAL; rows == 0 or n == 0 QUANTO_HIP_OK, nothing launched; a NULL x, out_scale or yq QUANTO_HIP_EINVAL.  No workspace, no atomics.
+ * quanto_hip_last_kernel() reports "layer_norm_q".
+ */
+#define QUANTO_HIP_LAYER_NORM_Q_MAX_N 8192
+int quanto_hip_layer_norm_q(const void* x, const void* weight, const void* bias, const void* out_scale, void* yq, int64_t rows, int64_t n,
+                            int64_t row_stride, float eps, int dtype, int out_dtype, void* stream);
+/* The size and format rule of quanto_hip_layer_norm_q alone: QUANTO_HIP_OK when it serves (rows, n, dtype, out_dtype), else the status above.  Needs no device. */
+int quanto_hip_layer_norm_q_supported(int64_t rows, int64_t n, int dtype, int out_dtype);
+
+/*
  * Scratch bytes the convolution kernels want for their K split (0: the problem is not split): when the 128 x 128 output tiles alone cannot
  * occupy the chip the K-tiles are dealt over up to 64 workgroups per tile, whose fp32 sums a second kernel adds in split order (deterministic,
  * no atomics, nothing to zero).  K = cin * KH * KW.  Both quanto_hip_q*_conv2d entries take the buffer (16-byte aligned); with NULL / too few

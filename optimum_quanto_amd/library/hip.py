@@ -125,6 +125,8 @@ _PROTOTYPES = {
     "quanto_hip_qbytes_mm_q_ws": (_ci, [_vp] * 6 + [_i64] * 3 + [_ci] * 4 + [_vp, _sz, _vp]),
     "quanto_hip_qbytes_mm_q_plan": (_ci, [_i64] * 3 + [_ci] * 4 + [_pci, _pi64]),
     "quanto_hip_qbytes_bmm": (_ci, [_vp] * 4 + [_i64] * 9 + [_ci, _vp]),
+    "quanto_hip_layer_norm_q": (_ci, [_vp] * 5 + [_i64] * 3 + [ctypes.c_float, _ci, _ci, _vp]),
+    "quanto_hip_layer_norm_q_supported": (_ci, [_i64] * 2 + [_ci] * 2),
     "quanto_hip_quantize_symmetric": (_ci, [_vp] * 3 + [_i64] * 2 + [_ci] * 3 + [_vp]),
     "quanto_hip_dequantize_symmetric": (_ci, [_vp] * 3 + [_i64] + [_ci] * 2 + [_vp]),
     "quanto_hip_quantize_affine": (_ci, [_vp] * 4 + [_i64] * 2 + [_ci] * 4 + [_vp]),
@@ -842,6 +844,51 @@ class _Bindings:
             self._check(st, "qbytes_bmm")
         return y
 
+    # -- quanto::layer_norm_q (QLayerNorm with its output quantization in the same launch) ----------------------
+    LAYER_NORM_Q_MAX_N = 8192  # QUANTO_HIP_LAYER_NORM_Q_MAX_N: the row one workgroup holds in registers (csrc/layernorm_q.hip)
+    LAYER_NORM_Q_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+    def layer_norm_q_supported(self, rows: int, n: int, dtype, out_dtype) -> bool:
+        """Python mirror of ``quanto_hip_layer_norm_q_supported``: the sizes and formats csrc/layernorm_q.hip serves."""
+        return (dtype in self.LAYER_NORM_Q_DTYPES and out_dtype in self.QUANTIZE_TARGETS and 0 <= n <= self.LAYER_NORM_Q_MAX_N
+                and 0 <= rows < (1 << 31))
+
+    def layer_norm_q(self, x, normalized_shape, weight, bias, eps: float, out_scale, dtype):
+        """``quantize_symmetric(F.layer_norm(x, normalized_shape, weight, bias, eps), dtype, None, out_scale)`` as one launch of
+        csrc/layernorm_q.hip: codes of ``dtype`` in x's shape, dense.  ``x`` is passed as the [rows, n] view it is when its leading dimensions
+        collapse to one row stride >= n (a slice of a wider buffer, an offset view) and copied otherwise; the normalized dimensions must be
+        contiguous.  ``out_scale``: one element on the device, never read on the host.  Raises QuantoHipError for what the library does not
+        serve: ``ops.layer_norm_q_hip`` asks its predicate first."""
+        self._require_cuda(x, weight, bias, out_scale)
+        normalized_shape = tuple(normalized_shape)
+        nd = len(normalized_shape)
+        if nd == 0 or nd > x.dim() or tuple(x.shape[x.dim() - nd:]) != normalized_shape:
+            raise QuantoHipError(f"layer_norm_q: input of shape {tuple(x.shape)} does not end in normalized_shape = {normalized_shape}")
+        n = 1
+        for d in normalized_shape:
+            n *= d
+        T = x.dtype
+        if any(p is not None and (p.dtype != T or p.numel() != n) for p in (weight, bias)) or out_scale.numel() != 1:
+            raise QuantoHipError("layer_norm_q expects weight and bias of normalized_shape in the input's dtype and a one-element output scale")
+        rows = x.numel() // n if n else 0
+        if not self.layer_norm_q_supported(rows, n, T, dtype):
+            self._check(-2, "layer_norm_q")
+        yq = torch.empty(x.shape, dtype=dtype, device=x.device)
+        if rows == 0:
+            return yq
+        x2 = x.reshape(rows, n)  # a view wherever the leading dimensions collapse, a copy otherwise
+        if (n > 1 and x2.stride(1) != 1) or (rows > 1 and x2.stride(0) < n):
+            x2 = x2.contiguous()
+        weight = None if weight is None else weight.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        out_scale = out_scale.reshape(1).to(T)  # what quantize_symmetric does with a scale of another dtype
+        with _DeviceGuard(x.device) as stream:
+            st = self._c.quanto_hip_layer_norm_q(x2.data_ptr(), _ptr(weight), _ptr(bias), out_scale.data_ptr(), yq.data_ptr(), rows, n,
+                                                 x2.stride(0) if rows > 1 else n, eps, _DTYPES[T], _DTYPES[dtype], stream)
+        if st != 0:
+            self._check(st, "layer_norm_q")
+        return yq
+
 
 class QuantoHipExtension(NativeLibrary):
     """The ``quanto_hip`` extension (name expected by the reference's tests/library/test_extensions.py:23-24)."""
@@ -852,7 +899,7 @@ class QuantoHipExtension(NativeLibrary):
             "quanto_hip",
             root_dir=csrc,
             lib_path=os.path.join(_PKG_DIR, "lib", "libquanto_hip.so"),
-            sources=["c_api.hip", "unpack.hip", "naive_mm.hip", "qbits_gemv.hip", "qbytes_gemv.hip", "qmm_mfma.hip", "qconv_mfma.hip", "qconv_a8.hip", "qconv_depthwise.hip", "qmm_mfma_large.hip", "qmm_large_common.h", "qbits_skinny.hip", "qbits_mmv.hip", "qbits_mfma_fused.hip", "qbits_a8_fused.hip", "qbits_mfma_large.hip", "qbytes_skinny.hip", "qmm_native8.hip", "qmm_f32.hip", "quantize.hip", "qbytes_bmm.hip",
+            sources=["c_api.hip", "unpack.hip", "naive_mm.hip", "qbits_gemv.hip", "qbytes_gemv.hip", "qmm_mfma.hip", "qconv_mfma.hip", "qconv_a8.hip", "qconv_depthwise.hip", "qmm_mfma_large.hip", "qmm_large_common.h", "qbits_skinny.hip", "qbits_mmv.hip", "qbits_mfma_fused.hip", "qbits_a8_fused.hip", "qbits_mfma_large.hip", "qbytes_skinny.hip", "qmm_native8.hip", "qmm_f32.hip", "quantize.hip", "qbytes_bmm.hip", "layernorm_q.hip",
                      "qh_common.h", "qh_conv.h", "qh_group_fused.h", "qh_mfma.h", "qh_quantize.h", os.path.join("..", "..", "include", "quanto_hip.h")],
         )
         self._bindings = None

@@ -375,6 +375,58 @@ _register("quantize_affine", "(Tensor base, int bits, int axis, int? group_size,
 
 
 # ------------------------------------------------------------------------------------------------
+# quanto::layer_norm_q: the LayerNorm of a model with quantized activations and its output quantization in one launch
+# ------------------------------------------------------------------------------------------------
+def layer_norm_q_default(input, normalized_shape, weight, bias, eps: float, out_scale, dtype):
+    """The two-op sequence of the reference's QLayerNorm (nn/qlayernorm.py:52-53, then the output hook of nn/qmodule.py): the float layer norm,
+    quantized per-tensor at ``out_scale``."""
+    y = torch.nn.functional.layer_norm(input, tuple(normalized_shape), weight, bias, eps)
+    return torch.ops.quanto.quantize_symmetric(y, dtype, None, out_scale)
+
+
+def _layer_norm_q_kernel_takes(input, normalized_shape, weight, bias, out_scale, dtype) -> bool:
+    """The predicate of ``layer_norm_q_hip``: a plain float32 / float16 / bfloat16 tensor on the device that ends in ``normalized_shape``, weight and
+    bias (each may be absent) of that shape in the same dtype, a one-element output scale on the device, an int8 / float8_e4m3fn / float8_e5m2 code
+    type, n = prod(normalized_shape) within the row one workgroup holds in registers (``LAYER_NORM_Q_MAX_N``), fewer than 2^31 rows, and the
+    normalized dimensions contiguous inside the input (leading dimensions that do not collapse to one row stride are the binding's business: it
+    copies).  No shape class is routed back on speed: the kernel is 1.35-1.79x the sequence on every measured one (profiles/layernorm_q_vs_sequence.jsonl)."""
+    lib = quanto_hip.lib
+    nd = len(normalized_shape)
+    if not (type(input) is torch.Tensor and input.is_cuda and input.dtype in lib.LAYER_NORM_Q_DTYPES and 0 < nd <= input.dim()
+            and tuple(input.shape[input.dim() - nd:]) == tuple(normalized_shape)):
+        return False
+    n = 1
+    for d in normalized_shape:
+        n *= d
+    for p in (weight, bias):
+        if p is not None and not (type(p) in (torch.Tensor, torch.nn.Parameter) and p.is_cuda and p.dtype == input.dtype and p.numel() == n):
+            return False
+    if not (out_scale.is_cuda and out_scale.numel() == 1 and lib.layer_norm_q_supported(input.numel() // n if n else 0, n, input.dtype, dtype)):
+        return False
+    expect = 1
+    for size, stride in zip(reversed(input.shape[input.dim() - nd:]), reversed(input.stride()[input.dim() - nd:])):
+        if size != 1 and stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+def layer_norm_q_hip(input, normalized_shape, weight, bias, eps: float, out_scale, dtype):
+    """ROCm: one launch of csrc/layernorm_q.hip when the predicate says so; every other call runs the two-op sequence on the device - the caller always
+    gets the sequence's contract."""
+    if _layer_norm_q_kernel_takes(input, normalized_shape, weight, bias, out_scale, dtype):
+        return quanto_hip.lib.layer_norm_q(input, normalized_shape, weight, bias, eps, out_scale, dtype)
+    return layer_norm_q_default(input, normalized_shape, weight, bias, eps, out_scale, dtype)
+
+
+# new op: F.layer_norm and the per-tensor quantization of its output in one launch - the float row is read once and the codes are stored.  Statistics
+# in fp32 (two passes), the affine result rounded once to the input dtype, then the rule of quanto::quantize_symmetric: the codes of the sequence up to
+# the last bits of the statistics (at most one code step, on a few elements in 10^5: tests/test_layernorm_q_gpu.py).  On the CPU the default runs.
+_register("layer_norm_q", "(Tensor input, int[] normalized_shape, Tensor? weight, Tensor? bias, float eps, Tensor out_scale, ScalarType dtype) -> Tensor",
+          layer_norm_q_hip, default=layer_norm_q_default)
+
+
+# ------------------------------------------------------------------------------------------------
 # quanto::dequantize_qbits and quanto::qbits_mm (new ops)
 # ------------------------------------------------------------------------------------------------
 def dequantize_qbits_default(packed, scale, shift, bits: int, group_size: Optional[int], out_features: int, in_features: int):

@@ -4,7 +4,7 @@ from typing import Any, Dict, List, Optional, Union
 
 import torch
 
-from .nn import QConv2d, QLinear, QModuleMixin, quantize_module
+from .nn import QConv2d, QLayerNorm, QLinear, QModuleMixin, quantize_module
 from .tensor import Optimizer, QTensor, WeightQBitsTensor, WeightQBytesTensor, qint2, qint4, qtype
 from .tensor.weights import _fusable, conv2d_a8_scales_underflow
 
@@ -18,8 +18,12 @@ def _set_module_by_name(parent: torch.nn.Module, name: str, child: torch.nn.Modu
     setattr(parent, leaf, child)
 
 
-def _quantize_submodule(model, name, module, weights=None, activations=None, optimizer=None):
-    qmodule = quantize_module(module, weights=weights, activations=activations, optimizer=optimizer)
+def _quantize_submodule(model, name, module, weights=None, activations=None, optimizer=None, layernorm=False):
+    if layernorm and isinstance(module, torch.nn.LayerNorm) and not isinstance(module, QModuleMixin):
+        # opt-in: QLayerNorm is not in the table of counterparts, which decides what the default quantize() does (None without an activation qtype)
+        qmodule = QLayerNorm.from_module(module, weights=weights, activations=activations, optimizer=optimizer)
+    else:
+        qmodule = quantize_module(module, weights=weights, activations=activations, optimizer=optimizer)
     if qmodule is None:
         return False
     _set_module_by_name(model, name, qmodule)
@@ -37,11 +41,15 @@ def _as_patterns(p: Optional[Union[str, List[str]]]):
 
 def quantize(model: torch.nn.Module, weights: Optional[Union[str, qtype]] = None,
              activations: Optional[Union[str, qtype]] = None, optimizer: Optional[Optimizer] = None,
-             include: Optional[Union[str, List[str]]] = None, exclude: Optional[Union[str, List[str]]] = None):
+             include: Optional[Union[str, List[str]]] = None, exclude: Optional[Union[str, List[str]]] = None, layernorm: bool = False):
     """Replace every eligible submodule in place by its quantized counterpart.
 
     ``include`` / ``exclude`` are Unix shell-style patterns on module names (quantize.py:55-98).  Weights stay
     float (dynamically quantized in forward) until ``freeze``.
+
+    ``layernorm=True`` (opt-in) also replaces every ``torch.nn.LayerNorm`` that passes include / exclude by a ``QLayerNorm`` when an
+    activation qtype is given (the reference does so always, nn/qlayernorm.py): its output is then quantized at its ``output_scale``,
+    which lets the Linears it feeds run on the stored codes.  The default leaves LayerNorms as float modules.
     """
     include, exclude = _as_patterns(include), _as_patterns(exclude)
     for name, module in list(model.named_modules()):
@@ -49,12 +57,16 @@ def quantize(model: torch.nn.Module, weights: Optional[Union[str, qtype]] = None
             continue
         if exclude is not None and any(fnmatch(name, pattern) for pattern in exclude):
             continue
-        _quantize_submodule(model, name, module, weights=weights, activations=activations, optimizer=optimizer)
+        _quantize_submodule(model, name, module, weights=weights, activations=activations, optimizer=optimizer, layernorm=layernorm)
 
 
 def requantize(model: torch.nn.Module, state_dict: Dict[str, Any], quantization_map: Dict[str, Dict[str, str]],
-               device: torch.device = None):
+               device: torch.device = None, layernorm: bool = False):
     """Rebuild a frozen model from a flattened state dict + ``quantization_map`` (quantize.py:101-140).
+
+    ``layernorm=True`` (opt-in): a ``torch.nn.LayerNorm`` the map names is rebuilt as a ``QLayerNorm`` and gets its input / output scales back
+    (a checkpoint of ``quantize(..., layernorm=True)``, or one written by the reference); with the default it stays a float module and the
+    warning below says so.
 
     One deliberate divergence from the reference: when the checkpoint's float dtype differs from the dtype ``model`` was built in
     (an fp32 checkpoint opened as a bf16 skeleton), the reference keeps the deserialized scale / shift as they are
@@ -63,9 +75,8 @@ def requantize(model: torch.nn.Module, state_dict: Dict[str, Any], quantization_
     the dequantized weights are then the checkpoint's values re-rounded to the model dtype, not bit-identical to what was saved.
     Build the skeleton in the checkpoint's dtype to get the reference's bits."""
     if device is None:
-        device = next(model.parameters()).device
-        if device.type == "meta":
-            device = torch.device("cpu")
+        first = next(model.parameters(), None)  # (None: a model of LayerNorms without elementwise affine has no parameter)
+        device = torch.device("cpu") if first is None or first.device.type == "meta" else first.device
     not_rebuilt = []
     for name, module in list(model.named_modules()):
         qconfig = quantization_map.get(name)
@@ -73,7 +84,7 @@ def requantize(model: torch.nn.Module, state_dict: Dict[str, Any], quantization_
             continue
         weights = None if qconfig["weights"] == "none" else qconfig["weights"]
         activations = None if qconfig["activations"] == "none" else qconfig["activations"]
-        if not _quantize_submodule(model, name, module, weights=weights, activations=activations):
+        if not _quantize_submodule(model, name, module, weights=weights, activations=activations, layernorm=layernorm):
             not_rebuilt.append(f"{name} ({type(module).__name__})")
     missing = sorted(set(quantization_map) - {n for n, _ in model.named_modules()})
     # Materialise what is still on the meta device, then load.  The float ``weight`` of a module whose quantized weight is in the
@@ -196,15 +207,17 @@ def fuse_output_quantization(model: torch.nn.Module, enable: bool = True) -> Lis
     (``groups == 1``) with ``padding_mode == "zeros"`` and numeric padding, has an 8-bit weight qtype and a pair the quantized-activation convolution
     serves - qint8 x qint8, or qfloat8_e4m3fn / qfloat8_e5m2 activations with a qfloat8_e4m3fn / qfloat8_e5m2 / qint8 weight, but not e5m2 activations
     with fp16 scales (``quanto::qbytes_conv2d_a8_q``).  Its forward then gets the output codes from the product kernel's epilogue instead of writing
-    the float output and quantizing it in a second pass - bit-identical codes, same ``output_scale``.  Returns the names of the marked (unmarked)
-    Linear and Conv modules in ``named_modules()`` order.
+    the float output and quantizing it in a second pass - bit-identical codes, same ``output_scale``.  Also marked: every ``QLayerNorm`` with a
+    qint8 / qfloat8_e4m3fn / qfloat8_e5m2 activation qtype and its output hook still registered (``quanto::layer_norm_q``: one launch reads the float
+    row and stores the codes - those of the two-op sequence up to the last bits of the statistics).  Returns the names of the marked (unmarked)
+    modules in ``named_modules()`` order.
 
     Not automatic: forward hooks registered by the user and calibration passes read a module's float output before its own hook quantizes it; a marked
     module hands them codes.  Calibrate first, then call this.  Sub-byte ``QLinear`` weights outside that format, fp32 ``QLinear`` modules, ``QConv2d``
     with sub-byte weights, groups, string or non-zero-mode padding, and other module classes are never marked; the mark is not saved with the state dict."""
     names = []
     for name, m in model.named_modules():
-        if type(m) is not QLinear and type(m) is not QConv2d:
+        if type(m) is not QLinear and type(m) is not QConv2d and type(m) is not QLayerNorm:
             continue
         if not enable:
             if m._fuse_output_quantization:
@@ -212,6 +225,11 @@ def fuse_output_quantization(model: torch.nn.Module, enable: bool = True) -> Lis
                 names.append(name)
             continue
         wq, aq = m.weight_qtype, m.activation_qtype
+        if type(m) is QLayerNorm:  # no quantized weight, nothing to freeze
+            if aq is not None and aq.dtype in _FUSED_OUTPUT_DTYPES and "output" in m._quantize_hooks:
+                m._fuse_output_quantization = True
+                names.append(name)
+            continue
         if not (m.frozen and wq is not None and aq is not None and aq.dtype in _FUSED_OUTPUT_DTYPES and "output" in m._quantize_hooks):
             continue
         if type(m) is QConv2d:

@@ -183,7 +183,7 @@ class QModuleMixin(ABC):
 
         if self.frozen and self.weight_qtype is not None:
             self.weight.save_to_state_dict(destination, _flat_weight_prefix(prefix), keep_vars)
-        else:
+        elif self.weight is not None:  # (a QLayerNorm without elementwise affine has none)
             put("weight", self.weight)
         if self.bias is not None:
             put("bias", self.bias)
