@@ -76,7 +76,18 @@ typedef enum {
  * the first QUANTO_HIP_WS_COUNTER_BYTES bytes are arrival counters - zero on entry, restored to zero by the kernel - and the
  * partial sums start right behind them, whatever the problem size.  A buffer whose counter region was zeroed once can
  * therefore serve any sequence of calls on one stream; a kernel never splits a problem that needs more counters than the
- * region holds. */
+ * region holds.
+ *
+ * What a call does with less than the bytes its *_plan / *_workspace_size entry reports - established per family by
+ * tests/test_containment_gpu.py with a workspace 16 bytes short of the report and with (NULL, 0); in every case not one byte behind
+ * the bytes that were given is written, and a refused call leaves the output untouched:
+ *   SKINNY and the one-launch *_multi_ws forms, MFMA_LARGE, NATIVE8, MFMA_FUSED4, quanto_hip_qbits_mm_a8: the call runs UNSPLIT
+ *     (QUANTO_HIP_OK, same kernel name, same exact-math gate; int8 x int8 on NATIVE8 the same bits);
+ *   MFMA of quanto_hip_qbits_mm (row sums) and DEQUANT_MFMA (dense weight), forced: QUANTO_HIP_EINVAL - they cannot run without
+ *     their scratch;  AUTO, and the separate calls of quanto_hip_qbits_mm_multi_ws, STEP DOWN instead: DEQUANT_MFMA -> MFMA -> NAIVE;
+ *   quanto_hip_qbytes_conv2d, quanto_hip_qbytes_conv2d_a8, the tap kernel of quanto_hip_qbits_conv2d: UNSPLIT;
+ *   the dequantize-once row route of quanto_hip_qbits_conv2d: with room for the dense weight but not for the split, the row route
+ *     unsplit; with less than the dense weight, the tap kernel (unsplit when the rest does not hold its split either). */
 #define QUANTO_HIP_WS_COUNTER_BYTES 4096
 
 #define QUANTO_HIP_MAX_MULTI 4           /* Linears per quanto_hip_qbits_mm_multi call                        */
