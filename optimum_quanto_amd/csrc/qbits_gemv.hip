@@ -56,20 +56,6 @@ __device__ __forceinline__ float pair_hi(uint32_t p) {
   return Elem<DT>::to_f32(__builtin_bit_cast(typename Elem<DT>::T, (uint16_t)(p >> 16)));
 }
 
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
-}
-// sum over the 64 lanes; only lane 63 holds the total
-__device__ __forceinline__ float wave_sum_lane63(float v) {
-  v += dpp_f<0xB1>(v);        // quad_perm [1,0,3,2]
-  v += dpp_f<0x4E>(v);        // quad_perm [2,3,0,1]
-  v += dpp_f<0x141>(v);       // row_half_mirror
-  v += dpp_f<0x140>(v);       // row_mirror  -> every lane of a 16-lane row holds the row sum
-  v += dpp_f<0x142, 0xA>(v);  // row_bcast15 into rows 1 and 3
-  v += dpp_f<0x143, 0xC>(v);  // row_bcast31 into rows 2 and 3 -> lane 63 holds the total
-  return v;
-}
 template <int R>
 __device__ __forceinline__ float quad_bcast(float v) {
   constexpr int ctrl = R | (R << 2) | (R << 4) | (R << 6);

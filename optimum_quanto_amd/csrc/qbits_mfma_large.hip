@@ -87,22 +87,6 @@ __device__ __forceinline__ float round_to_T(float v) {
     return (float)(_Float16)v;
 }
 
-// two fp32 -> one dword of T, round to nearest even (qh_mfma.h's pack_exact rounds fp16 toward zero: exact only for the 8-bit codes it serves)
-template <int DT>
-__device__ __forceinline__ uint32_t pack_rne(float a, float b) {
-  if constexpr (DT == QUANTO_HIP_BF16) {
-    bf16x2 r;
-    r.x = (__bf16)a;
-    r.y = (__bf16)b;
-    return __builtin_bit_cast(uint32_t, r);
-  } else {
-    f16x2 r;
-    r.x = (_Float16)a;
-    r.y = (_Float16)b;
-    return __builtin_bit_cast(uint32_t, r);
-  }
-}
-
 // Two weights of one feature -> one MFMA operand dword.  `spread`: the lane's nibble plane spread to bytes (plane 0: q, plane 1: 16 q -
 // the factor 16 is folded into s / zp below, exactly: powers of two).  `PAIR`: byte pair 0 / 1 of the dword.
 template <int DT, bool INT_SHIFT, int PAIR>

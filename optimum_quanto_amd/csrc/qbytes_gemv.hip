@@ -8,53 +8,6 @@
 
 namespace qh {
 
-template <int BDT>
-__device__ __forceinline__ void decode_word(uint32_t w, float (&f)[4]);
-template <>
-__device__ __forceinline__ void decode_word<QUANTO_HIP_I8>(uint32_t w, float (&f)[4]) {
-  f[0] = (float)(int8_t)(w & 0xFFu);
-  f[1] = (float)(int8_t)((w >> 8) & 0xFFu);
-  f[2] = (float)(int8_t)((w >> 16) & 0xFFu);
-  f[3] = (float)(int8_t)(w >> 24);
-}
-template <>
-__device__ __forceinline__ void decode_word<QUANTO_HIP_F8_E4M3FN>(uint32_t w, float (&f)[4]) {
-  const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
-  const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
-  f[0] = lo.x; f[1] = lo.y; f[2] = hi.x; f[3] = hi.y;
-}
-template <>
-__device__ __forceinline__ void decode_word<QUANTO_HIP_F8_E5M2>(uint32_t w, float (&f)[4]) {
-  const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, false);
-  const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, true);
-  f[0] = lo.x; f[1] = lo.y; f[2] = hi.x; f[3] = hi.y;
-}
-
-template <>
-__device__ __forceinline__ void decode_word<QUANTO_HIP_F8_E4M3FNUZ>(uint32_t w, float (&f)[4]) {  // qh_common.h: fn value / 2 + three patched patterns
-  const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
-  const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
-  f[0] = fnuz_fix_f32(lo.x * 0.5f, w & 0xFFu);
-  f[1] = fnuz_fix_f32(lo.y * 0.5f, (w >> 8) & 0xFFu);
-  f[2] = fnuz_fix_f32(hi.x * 0.5f, (w >> 16) & 0xFFu);
-  f[3] = fnuz_fix_f32(hi.y * 0.5f, w >> 24);
-}
-
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
-}
-// sum over the 64 lanes; only lane 63 holds the total
-__device__ __forceinline__ float wave_sum_lane63(float v) {
-  v += dpp_f<0xB1>(v);        // quad_perm [1,0,3,2]
-  v += dpp_f<0x4E>(v);        // quad_perm [2,3,0,1]
-  v += dpp_f<0x141>(v);       // row_half_mirror
-  v += dpp_f<0x140>(v);       // row_mirror
-  v += dpp_f<0x142, 0xA>(v);  // row_bcast15 into rows 1 and 3
-  v += dpp_f<0x143, 0xC>(v);  // row_bcast31 into rows 2 and 3 -> lane 63 holds the total
-  return v;
-}
-
 constexpr int RR8 = 4;  // weight rows per wave pass
 
 // Latency-first layout (same as qbits_gemv.hip): a decode call lasts a few microseconds, so every byte a wave needs is
@@ -141,7 +94,7 @@ __global__ void __launch_bounds__(256) qbytes_gemv_kernel(const uint16_t* __rest
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
         float f[4];
-        decode_word<BDT>(w4[d], f);
+        dword_f32<BDT>(w4[d], f);
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll

@@ -9,17 +9,17 @@
 // codes.  acc is exact int32 for int8 x int8 (the result is a pure function of the integers, split or not) and the fp32 matrix-pipe sum of exact
 // products for fp8.
 //
-// GEMM view, tiles and gather: the tap gather of DESIGN.md 4.8, whose shared pieces (LDS layout, tap table, validity test, partial-tile store, split
-// plan and reduce, geometry rule) live in qh_conv.h: M = B*OH*OW pixels, N = OC, K = cin*KH*KW in the weight's (c, i, j) order; one workgroup =
+// GEMM view, tiles and gather: the tap gather of DESIGN.md 4.8, whose shared pieces (tap table, validity test, partial-tile store, split
+// plan and reduce, geometry rule) live in qh_conv.h and whose LDS layout in qh_mfma.h: M = B*OH*OW pixels, N = OC, K = cin*KH*KW in the weight's (c, i, j) order; one workgroup =
 // 128 pixels x 128 channels, eight waves (2 x 4, 64 pixels x 32 channels each), two LDS buffers.  A K-tile is 128 ONE-byte elements - one 128-byte
-// LDS row of conv_lds_off:
+// LDS row of tile_lds_off:
 //   * a thread stages one pixel (tile row tid & 127) and two 16-byte chunks of it per K-tile, kc = (tid >> 7) + 4 j: k is uniform across a wave;
 //   * the k-only part of an address (byte offset of tap (c, i, j) relative to the window's top-left tap, and the tap's number) comes from a
 //     128-entry LDS table per K-tile; the pixel-only part (base offset, one validity bit per tap) lives in registers; an element is one
 //     range-checked BUFFER byte load whose offset is forced to 0xFFFFFFFF for a padding tap or a k behind K: it reads 0 (int8 0, fp8 +0.0), nothing
 //     is masked afterwards;
 //   * fragments: lane (row lane & 15, 16-byte chunk lane >> 4 of each 64-byte half of the row) - the maps of qmm_native8.hip (one K = 64 int8
-//     MFMA per half: v_mfma_i32_16x16x64_i8) and of its paired fp8 form (both halves as ONE K = 128 v_mfma_scale_f32_16x16x128_f8f6f4, the same k
+//     MFMA per half: v_mfma_i32_16x16x64_i8) and of its fp8 loop (both halves as ONE K = 128 v_mfma_scale_f32_16x16x128_f8f6f4, the same k
 //     assignment in both operands, A and B formats independent, block scales 2^0).
 // fp8 activations x int8 weights: q = 16 hi + lo with hi = q >> 4 in [-8, 7] and lo = q & 15 in [0, 15], both exact e4m3 codes, built from the
 // LDS fragment by v_perm over 16-entry code tables (qbits_a8_fused.hip's nibble scheme).  Two MX-format MFMAs per fragment into the SAME fp32
@@ -49,7 +49,7 @@ enum { F_E4M3 = 0, F_E5M2 = 1 };              // cbsz / blgp codes of the MX-for
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-static_assert(BK == kConvRowBytes, "a K-tile of one-byte elements is one LDS row of conv_lds_off");
+static_assert(BK == kTileRowBytes, "a K-tile of one-byte elements is one LDS row of tile_lds_off");
 
 struct Args {
   const uint8_t* x;       // [B, cin, H, W] int8 / fp8 codes
@@ -247,12 +247,12 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
     uint8_t* sb = sa + TILE_BYTES;
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-      *reinterpret_cast<uint4*>(sa + conv_lds_off(tid & 127, (tid >> 7) + 4 * j)) =
+      *reinterpret_cast<uint4*>(sa + tile_lds_off(tid & 127, (tid >> 7) + 4 * j)) =
           make_uint4(pack4(g[j][0], g[j][1], g[j][2], g[j][3]), pack4(g[j][4], g[j][5], g[j][6], g[j][7]),
                      pack4(g[j][8], g[j][9], g[j][10], g[j][11]), pack4(g[j][12], g[j][13], g[j][14], g[j][15]));
     const int row = tid >> 2, part = tid & 3;
-    *reinterpret_cast<uint4*>(sb + conv_lds_off(row, 2 * part)) = rw[0];
-    *reinterpret_cast<uint4*>(sb + conv_lds_off(row, 2 * part + 1)) = rw[1];
+    *reinterpret_cast<uint4*>(sb + tile_lds_off(row, 2 * part)) = rw[0];
+    *reinterpret_cast<uint4*>(sb + tile_lds_off(row, 2 * part + 1)) = rw[1];
   };
 
   AV acc[4][2];
@@ -268,9 +268,9 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_a8_kernel(const Args a) {
     for (int h = 0; h < 2; ++h) {
       const int kc = h * 4 + (lane >> 4);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) fa[h][i] = *reinterpret_cast<const uint4*>(sa + conv_lds_off(wm * 64 + i * 16 + (lane & 15), kc));
+      for (int i = 0; i < 4; ++i) fa[h][i] = *reinterpret_cast<const uint4*>(sa + tile_lds_off(wm * 64 + i * 16 + (lane & 15), kc));
 #pragma unroll
-      for (int j = 0; j < 2; ++j) fb[h][j] = *reinterpret_cast<const uint4*>(sb + conv_lds_off(wn * 32 + j * 16 + (lane & 15), kc));
+      for (int j = 0; j < 2; ++j) fb[h][j] = *reinterpret_cast<const uint4*>(sb + tile_lds_off(wn * 32 + j * 16 + (lane & 15), kc));
     }
     auto cat = [](const uint4& lo, const uint4& hi) { return i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w}; };
     if constexpr (KIND == K_I8) {

@@ -27,8 +27,8 @@
 // History (profiles/r04_qconv2d_*.jsonl, r05_qconv2d_*.jsonl): first form - four pixels per thread, a counted (c, i, j) walk and four compares per
 // element, four waves (inside qmm_mfma.hip) - 3.7 us per K-tile whatever M was; the table on four waves 2.0; eight waves 1.85 (r4); buffer-load
 // gather, pixel pairs, magic-number table, 8-byte epilogue stores (r5): ~1.2 us per K-tile; DESIGN.md 4.8.
-// What the tap gather shares with qconv_a8.hip (the same gather over one-byte elements) lives in qh_conv.h: LDS layout, tap table, validity test,
-// partial-tile store, split plan and reduce, the geometry (ConvGeom) and its rule.
+// What the tap gather shares with qconv_a8.hip (the same gather over one-byte elements) lives in qh_conv.h: tap table, validity test,
+// partial-tile store, split plan and reduce, the geometry (ConvGeom) and its rule; the LDS layout (tile_lds_off) and the weight converters in qh_mfma.h.
 #include <type_traits>
 
 #include "qh_conv.h"
@@ -46,11 +46,13 @@ constexpr int BM = 128, BN = 128, BK = 64, NT = 512;
 constexpr int TILE_BYTES = BM * BK * 2;  // one operand tile in LDS (16 KiB)
 constexpr int LDS_BYTES = 2 * 2 * TILE_BYTES + 2 * BK * 8;
 
-enum WFmt { W_I8 = 0, W_F8E4M3 = 1, W_F8E5M2 = 2, W_I4R = 3, W_I2R = 4, W_DENSE16 = 5 };  // W_DENSE16 (row form only): a weight already in the activation dtype
+using namespace w8;  // qh_mfma.h: W_I8, W_F8E4M3, W_F8E5M2, convert16, byte_dtype
+enum { W_I4R = 3, W_I2R = 4, W_DENSE16 = 5 };  // this unit's own formats, behind the three 8-bit ones.  W_DENSE16 (row form only): a weight already in the activation dtype
 constexpr int planes_of(int fmt) { return fmt == W_I4R ? 2 : (fmt == W_I2R ? 4 : 1); }  // values per packed byte
 
-static_assert(BK * 2 == kConvRowBytes, "a K-tile of two-byte elements is one LDS row of conv_lds_off");
+static_assert(BK * 2 == kTileRowBytes, "a K-tile of two-byte elements is one LDS row of tile_lds_off");
 
+// The twin of qh::pack_rne (qh_mfma.h), in the wording this unit's listing was built from (either wording changes the other user's): a fix to one belongs in the other.
 template <int DT>
 __device__ __forceinline__ uint32_t pack_rne(float a, float b) {
   using E = Elem<DT>;
@@ -63,33 +65,6 @@ typedef short s16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack16(short lo, short hi) {
   const s16x2 v = {lo, hi};
   return __builtin_bit_cast(uint32_t, v);
-}
-
-// 16 one-byte weights -> 16 elements of the activation dtype (every int8 / fp8 value is exact in bf16 and fp16)
-template <int DT, int FMT>
-__device__ __forceinline__ void convert16(const uint4& w, uint4& c0, uint4& c1) {
-  const uint32_t in[4] = {w.x, w.y, w.z, w.w};
-  uint32_t out[8];
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    float f0, f1, f2, f3;
-    if constexpr (FMT == W_I8) {
-      f0 = (float)(int8_t)(in[d] & 0xFFu);
-      f1 = (float)(int8_t)((in[d] >> 8) & 0xFFu);
-      f2 = (float)(int8_t)((in[d] >> 16) & 0xFFu);
-      f3 = (float)(int8_t)(in[d] >> 24);
-    } else if constexpr (FMT == W_F8E4M3) {
-      const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)in[d], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)in[d], true);
-      f0 = lo.x; f1 = lo.y; f2 = hi.x; f3 = hi.y;
-    } else {
-      const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)in[d], false), hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)in[d], true);
-      f0 = lo.x; f1 = lo.y; f2 = hi.x; f3 = hi.y;
-    }
-    out[2 * d] = pack_exact<DT>(f0, f1);
-    out[2 * d + 1] = pack_exact<DT>(f2, f3);
-  }
-  c0 = make_uint4(out[0], out[1], out[2], out[3]);
-  c1 = make_uint4(out[4], out[5], out[6], out[7]);
 }
 
 // 8 packed bytes -> 8 low-nibble and 8 high-nibble weights dequantized as the reference does: T(T(s q) - z) for float shifts, T(s (q - zp)) for
@@ -404,38 +379,38 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_mfma_kernel(const Args a) {
       for (int q = 0; q < 8; ++q) d[q] = __builtin_amdgcn_perm(g_pair[q], 0u, g_sel[q]);  // [first pixel | second pixel] of tap q, realigned, padding zeroed
       const int row = 2 * (tid & 63);
       // first pixel: the low halves of the eight dwords; second pixel: the high halves
-      *reinterpret_cast<uint4*>(sa + conv_lds_off(row, wave)) =
+      *reinterpret_cast<uint4*>(sa + tile_lds_off(row, wave)) =
           make_uint4(__builtin_amdgcn_perm(d[1], d[0], 0x05040100u), __builtin_amdgcn_perm(d[3], d[2], 0x05040100u),
                      __builtin_amdgcn_perm(d[5], d[4], 0x05040100u), __builtin_amdgcn_perm(d[7], d[6], 0x05040100u));
-      *reinterpret_cast<uint4*>(sa + conv_lds_off(row + 1, wave)) =
+      *reinterpret_cast<uint4*>(sa + tile_lds_off(row + 1, wave)) =
           make_uint4(__builtin_amdgcn_perm(d[1], d[0], 0x07060302u), __builtin_amdgcn_perm(d[3], d[2], 0x07060302u),
                      __builtin_amdgcn_perm(d[5], d[4], 0x07060302u), __builtin_amdgcn_perm(d[7], d[6], 0x07060302u));
     } else {
 #pragma unroll
       for (int j = 0; j < 2; ++j)
-        *reinterpret_cast<uint4*>(sa + conv_lds_off(tid & 127, (tid >> 7) + 4 * j)) =
+        *reinterpret_cast<uint4*>(sa + tile_lds_off(tid & 127, (tid >> 7) + 4 * j)) =
             make_uint4(pack16(g_raw[j][0], g_raw[j][1]), pack16(g_raw[j][2], g_raw[j][3]), pack16(g_raw[j][4], g_raw[j][5]), pack16(g_raw[j][6], g_raw[j][7]));
     }
     if constexpr (PL == 2) {
       uint4 lo, hi;
       convert8_i4r<DT, INT_SHIFT>(make_uint2(rw.x, rw.y), rs[0], rz[0], rs[1], rz[1], lo, hi);
       const int row = tid >> 3, part = tid & 7;
-      *reinterpret_cast<uint4*>(sb + conv_lds_off(row, part)) = lo;
-      *reinterpret_cast<uint4*>(sb + conv_lds_off(64 + row, part)) = hi;
+      *reinterpret_cast<uint4*>(sb + tile_lds_off(row, part)) = lo;
+      *reinterpret_cast<uint4*>(sb + tile_lds_off(64 + row, part)) = hi;
     } else if constexpr (PL == 4) {
       if (tid < RPT * 8) {
         uint4 o[4];
         convert8_i2r<DT, INT_SHIFT>(make_uint2(rw.x, rw.y), rs, rz, o);
         const int row = tid >> 3, part = tid & 7;
 #pragma unroll
-        for (int pl = 0; pl < 4; ++pl) *reinterpret_cast<uint4*>(sb + conv_lds_off(pl * RPT + row, part)) = o[pl];
+        for (int pl = 0; pl < 4; ++pl) *reinterpret_cast<uint4*>(sb + tile_lds_off(pl * RPT + row, part)) = o[pl];
       }
     } else {
       uint4 c0, c1;
       convert16<DT, FMT>(rw, c0, c1);
       const int row = tid >> 2, part = tid & 3;
-      *reinterpret_cast<uint4*>(sb + conv_lds_off(row, 2 * part)) = c0;
-      *reinterpret_cast<uint4*>(sb + conv_lds_off(row, 2 * part + 1)) = c1;
+      *reinterpret_cast<uint4*>(sb + tile_lds_off(row, 2 * part)) = c0;
+      *reinterpret_cast<uint4*>(sb + tile_lds_off(row, 2 * part + 1)) = c1;
     }
   };
 
@@ -463,9 +438,9 @@ __global__ void __launch_bounds__(NT, 2) qconv2d_mfma_kernel(const Args a) {
       V8 fa[4], fb[2];
       const int kc = kk * 4 + (lane >> 4);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const V8*>(sa + conv_lds_off(wm * 64 + i * 16 + (lane & 15), kc));
+      for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const V8*>(sa + tile_lds_off(wm * 64 + i * 16 + (lane & 15), kc));
 #pragma unroll
-      for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const V8*>(sb + conv_lds_off(wn * 32 + j * 16 + (lane & 15), kc));
+      for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const V8*>(sb + tile_lds_off(wn * 32 + j * 16 + (lane & 15), kc));
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -516,27 +491,6 @@ constexpr int LDS_BYTES = 2 * OP_BYTES;
 }  // namespace rows
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-template <int FMT>
-__device__ __forceinline__ float byte_to_f32(uint32_t d, int b) {  // b: a literal after unrolling
-  if constexpr (FMT == W_I8) {
-    return (float)(int8_t)((d >> (8 * b)) & 0xFFu);
-  } else if constexpr (FMT == W_F8E4M3) {
-    switch (b) {
-      case 0: return __builtin_amdgcn_cvt_f32_fp8((int)d, 0);
-      case 1: return __builtin_amdgcn_cvt_f32_fp8((int)d, 1);
-      case 2: return __builtin_amdgcn_cvt_f32_fp8((int)d, 2);
-      default: return __builtin_amdgcn_cvt_f32_fp8((int)d, 3);
-    }
-  } else {
-    switch (b) {
-      case 0: return __builtin_amdgcn_cvt_f32_bf8((int)d, 0);
-      case 1: return __builtin_amdgcn_cvt_f32_bf8((int)d, 1);
-      case 2: return __builtin_amdgcn_cvt_f32_bf8((int)d, 2);
-      default: return __builtin_amdgcn_cvt_f32_bf8((int)d, 3);
-    }
-  }
-}
 
 // SINGLE (r5): ONE output pixel per thread (tile row tid & 127) and EIGHT window rows (8 (tid >> 7) ..): any stride along the width and odd OW -
 // the downsampling 3 x 3 layers and 7 x 7 / 13 x 13 feature maps the pair form cannot take.  An 8-byte window still brings the pixel's three taps
@@ -675,7 +629,7 @@ __global__ void __launch_bounds__(NT, DB ? 1 : 2) qconv2d_rows_kernel(const Args
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
       const int e0 = 3 * (2 * h) + j, e1 = 3 * (2 * h + 1) + j;
-      o[h] = pack_exact<DT>(byte_to_f32<FMT>(in[e0 >> 2], e0 & 3), byte_to_f32<FMT>(in[e1 >> 2], e1 & 3));
+      o[h] = pack_exact<DT>(byte_f32<byte_dtype(FMT)>(in[e0 >> 2], e0 & 3), byte_f32<byte_dtype(FMT)>(in[e1 >> 2], e1 & 3));
     }
     cw[j] = make_uint4(o[0], o[1], o[2], o[3]);
   };

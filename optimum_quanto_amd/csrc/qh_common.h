@@ -91,33 +91,84 @@ __device__ __forceinline__ uint32_t fnuz_pair_f16(uint32_t word, int p) {
   return fnuz_fix_pair<0x5B80u, 0x7E00u>(c, word, p);
 }
 
-template <int DT>
-__device__ __forceinline__ float decode8(uint8_t b);
-template <>
-__device__ __forceinline__ float decode8<QUANTO_HIP_I8>(uint8_t b) {
-  return (float)(int8_t)b;
+// The one family of byte decoders, by the QUANTO_HIP_* code of the stored element: every kernel that turns 8-bit codes into fp32 goes through it.
+// byte `i` (a literal after unrolling) of a dword -> fp32.  fp8 / bf8: the byte select of v_cvt_f32_fp8 / v_cvt_f32_bf8 is an immediate.
+template <int QDT>
+__device__ __forceinline__ float byte_f32(uint32_t d, int i) {
+  const uint32_t b = (d >> (8 * i)) & 0xFFu;
+  if constexpr (QDT == QUANTO_HIP_I8) {
+    return (float)(int8_t)b;
+  } else if constexpr (QDT == QUANTO_HIP_U8) {
+    return (float)b;  // v_cvt_f32_ubyteN
+  } else if constexpr (QDT == QUANTO_HIP_F8_E4M3FN) {
+    switch (i) {
+      case 0: return __builtin_amdgcn_cvt_f32_fp8((int)d, 0);
+      case 1: return __builtin_amdgcn_cvt_f32_fp8((int)d, 1);
+      case 2: return __builtin_amdgcn_cvt_f32_fp8((int)d, 2);
+      default: return __builtin_amdgcn_cvt_f32_fp8((int)d, 3);
+    }
+  } else if constexpr (QDT == QUANTO_HIP_F8_E5M2) {
+    switch (i) {
+      case 0: return __builtin_amdgcn_cvt_f32_bf8((int)d, 0);
+      case 1: return __builtin_amdgcn_cvt_f32_bf8((int)d, 1);
+      case 2: return __builtin_amdgcn_cvt_f32_bf8((int)d, 2);
+      default: return __builtin_amdgcn_cvt_f32_bf8((int)d, 3);
+    }
+  } else {
+    static_assert(QDT == QUANTO_HIP_F8_E4M3FNUZ, "byte_f32: 8-bit element types only");
+    return decode_e4m3fnuz(b);
+  }
 }
-template <>
-__device__ __forceinline__ float decode8<QUANTO_HIP_U8>(uint8_t b) {
-  return (float)b;
+// the four bytes of a dword -> four fp32.  fp8 / bf8: two v_cvt_pk_f32_fp8 / bf8; e4m3fnuz: the fn value / 2 + the three patched patterns
+template <int QDT>
+__device__ __forceinline__ void dword_f32(uint32_t w, float (&f)[4]) {
+  if constexpr (QDT == QUANTO_HIP_F8_E4M3FN || QDT == QUANTO_HIP_F8_E4M3FNUZ) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+    const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+    if constexpr (QDT == QUANTO_HIP_F8_E4M3FN) {
+      f[0] = lo.x; f[1] = lo.y; f[2] = hi.x; f[3] = hi.y;
+    } else {
+      f[0] = fnuz_fix_f32(lo.x * 0.5f, w & 0xFFu);
+      f[1] = fnuz_fix_f32(lo.y * 0.5f, (w >> 8) & 0xFFu);
+      f[2] = fnuz_fix_f32(hi.x * 0.5f, (w >> 16) & 0xFFu);
+      f[3] = fnuz_fix_f32(hi.y * 0.5f, w >> 24);
+    }
+  } else if constexpr (QDT == QUANTO_HIP_F8_E5M2) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, false);
+    const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, true);
+    f[0] = lo.x; f[1] = lo.y; f[2] = hi.x; f[3] = hi.y;
+  } else {
+    static_assert(QDT == QUANTO_HIP_I8, "dword_f32: int8, e4m3fn, e5m2, e4m3fnuz");
+    f[0] = (float)(int8_t)(w & 0xFFu);
+    f[1] = (float)(int8_t)((w >> 8) & 0xFFu);
+    f[2] = (float)(int8_t)((w >> 16) & 0xFFu);
+    f[3] = (float)(int8_t)(w >> 24);
+  }
 }
-template <>
-__device__ __forceinline__ float decode8<QUANTO_HIP_F8_E4M3FN>(uint8_t b) {
-  return __builtin_amdgcn_cvt_f32_fp8((int)b, 0);
-}
-template <>
-__device__ __forceinline__ float decode8<QUANTO_HIP_F8_E5M2>(uint8_t b) {
-  return __builtin_amdgcn_cvt_f32_bf8((int)b, 0);
-}
-template <>
-__device__ __forceinline__ float decode8<QUANTO_HIP_F8_E4M3FNUZ>(uint8_t b) {
-  return decode_e4m3fnuz(b);
+// one stored byte -> fp32
+template <int QDT>
+__device__ __forceinline__ float decode8(uint8_t b) {
+  return byte_f32<QDT>(b, 0);
 }
 
 // ---- wave-level sum (64 lanes) ------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ float dpp_f(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
+}
+// the same sum on the DPP ladder (six v_add_f32_dpp, no LDS crossbar); only lane 63 holds the total
+__device__ __forceinline__ float wave_sum_lane63(float v) {
+  v += dpp_f<0xB1>(v);        // quad_perm [1,0,3,2]
+  v += dpp_f<0x4E>(v);        // quad_perm [2,3,0,1]
+  v += dpp_f<0x141>(v);       // row_half_mirror
+  v += dpp_f<0x140>(v);       // row_mirror  -> every lane of a 16-lane row holds the row sum
+  v += dpp_f<0x142, 0xA>(v);  // row_bcast15 into rows 1 and 3
+  v += dpp_f<0x143, 0xC>(v);  // row_bcast31 into rows 2 and 3 -> lane 63 holds the total
   return v;
 }
 

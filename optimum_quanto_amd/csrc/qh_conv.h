@@ -75,11 +75,6 @@ struct __attribute__((packed, aligned(1))) U4u { uint32_t x, y, z, w; };
 struct __attribute__((packed, aligned(1))) U2u { uint32_t x, y; };
 struct __attribute__((packed, aligned(1))) U1u { uint32_t x; };
 
-// An operand tile in LDS: 128-byte rows (BK elements of ES bytes) of eight 16-byte chunks; chunk kc of row r sits at position kc ^ (r & 7): the
-// fragment reads (16 rows x 4 chunks) and the staging writes are conflict-free
-constexpr int kConvRowBytes = 128;
-__device__ __forceinline__ int conv_lds_off(int row, int kc) { return row * kConvRowBytes + ((kc ^ (row & 7)) << 4); }
-
 // n / d and its remainder for a small run-time d: q = mulhi(n, ceil(2^32 / d)), exact for n < 2^24 and d <= 127 (n (M d - 2^32) < 2^24 * 127 < 2^32);
 // the magic numbers come from the host (div_magic; 0: d = 1).  As integer divisions they were ~60 instructions per table entry.
 __device__ __forceinline__ int conv_div_small(int n, int d, uint32_t magic, int& rem) {

@@ -1,5 +1,5 @@
 // Building blocks shared by the MFMA kernels: the 16x16x32 bf16 / fp16 MFMA trait, LDS-DMA issue, the vmcnt ladder, the split-K
-// tail and the 8-bit pair converter.
+// tail, the 16-bit packers and the 8-bit format codes with their converters to 16-bit operands.
 #pragma once
 #include "qh_common.h"
 
@@ -25,7 +25,7 @@ struct Mma<QUANTO_HIP_F16> {
 };
 
 // two floats that are EXACT in the 16-bit type (int8 / fp8 codes) -> one dword with one instruction (v_cvt_pk_bf16_f32 / v_cvt_pkrtz_f16_f32).
-// The fp16 form rounds toward zero: not for values that need rounding (qbits_mfma_large.hip has its own round-to-nearest pack).
+// The fp16 form rounds toward zero: not for values that need rounding (pack_rne below).
 template <int DT>
 __device__ __forceinline__ uint32_t pack_exact(float a, float b) {
   if constexpr (DT == QUANTO_HIP_BF16) {
@@ -37,6 +37,28 @@ __device__ __forceinline__ uint32_t pack_exact(float a, float b) {
     return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
   }
 }
+// two fp32 -> one dword of the 16-bit type, round to nearest even: dequantized sub-byte weights (qbits_mfma_large.hip).  qconv_mfma.hip keeps a twin
+// in its own wording (conv::pack_rne: this wording changes its listing, its wording changes qbits_mfma_large's): a fix to one belongs in the other.
+template <int DT>
+__device__ __forceinline__ uint32_t pack_rne(float a, float b) {
+  if constexpr (DT == QUANTO_HIP_BF16) {
+    bf16x2 r;
+    r.x = (__bf16)a;
+    r.y = (__bf16)b;
+    return __builtin_bit_cast(uint32_t, r);
+  } else {
+    f16x2 r;
+    r.x = (_Float16)a;
+    r.y = (_Float16)b;
+    return __builtin_bit_cast(uint32_t, r);
+  }
+}
+
+// ---- an operand tile staged through registers into LDS (qmm_mfma.hip, qconv_mfma.hip, qconv_a8.hip) --------------------------------
+// 128-byte rows (one K-tile of a row) of eight 16-byte chunks; chunk kc of row r sits at position kc ^ (r & 7): the fragment reads (16 rows x 4
+// chunks) and the staging writes are conflict-free
+constexpr int kTileRowBytes = 128;
+__device__ __forceinline__ int tile_lds_off(int row, int kc) { return row * kTileRowBytes + ((kc ^ (row & 7)) << 4); }
 
 // ---- LDS-DMA, 16 bytes per lane (inline asm: through the builtin hipcc puts a vmcnt(0) in front of every ds_read that follows) ----
 // M0 is written and not restored: on gfx9+ the compiler only needs M0 for constructs these kernels do not contain (movrel, GWS,
@@ -162,11 +184,16 @@ __device__ __forceinline__ void wait_vmcnt(int younger_tiles) {
     }                                                                                                                            \
   }
 
-// ---- 8-bit weight codes -> 16-bit MFMA operands (qbytes_skinny.hip, qmm_mfma_large.hip) ------------------------------------
-// The format is a template argument of the kernels: these numbers are part of their names.
+// ---- 8-bit weight codes -> 16-bit MFMA operands (qbytes_skinny.hip, qmm_mfma_large.hip, qmm_mfma.hip, qconv_mfma.hip) ----------
+// The format is a template argument of the kernels: these numbers are part of their names.  A unit's own enum continues them with the formats
+// only it has (qmm_mfma.hip: W_I4; qconv_mfma.hip: W_I4R ..).
 namespace w8 {
 
 enum { W_I8 = 0, W_F8E4M3 = 1, W_F8E5M2 = 2, W_DENSE = 3, W_F8E4M3FNUZ = 4 };  // W_DENSE: weights already in the activation dtype (qmm_mfma_large.hip's weights-direct loop only; no convert_pair)
+// the QUANTO_HIP_* code of a format's bytes, which the byte decoders of qh_common.h take
+constexpr int byte_dtype(int fmt) {
+  return fmt == W_I8 ? QUANTO_HIP_I8 : fmt == W_F8E4M3 ? QUANTO_HIP_F8_E4M3FN : fmt == W_F8E4M3FNUZ ? QUANTO_HIP_F8_E4M3FNUZ : QUANTO_HIP_F8_E5M2;
+}
 
 // bytes (2p, 2p+1) of `word` -> two 16-bit elements.  int8: 3 VALU ops (2 x v_cvt_f32_i32 with SDWA byte select + one packed
 // conversion).  fp8 / bf8: ONE op - gfx950's v_cvt_scalef32_pk_{bf16,f16}_{fp8,bf8} converts a pair straight to the 16-bit type
@@ -195,6 +222,24 @@ __device__ __forceinline__ uint32_t convert_pair(uint32_t word, int p) {
       return __builtin_bit_cast(uint32_t, p == 0 ? __builtin_amdgcn_cvt_scalef32_pk_f16_bf8((int)word, 1.0f, false)
                                                  : __builtin_amdgcn_cvt_scalef32_pk_f16_bf8((int)word, 1.0f, true));
   }
+}
+
+// 16 one-byte weights -> 16 elements of the activation dtype, two 16-byte LDS chunks (qmm_mfma.hip, qconv_mfma.hip): through fp32
+// (qh_common.h: dword_f32), every int8 / fp8 value is exact in bf16 and fp16
+template <int DT, int FMT>
+__device__ __forceinline__ void convert16(const uint4& w, uint4& c0, uint4& c1) {
+  static_assert(FMT == W_I8 || FMT == W_F8E4M3 || FMT == W_F8E5M2, "convert16: int8, e4m3fn, e5m2");
+  const uint32_t in[4] = {w.x, w.y, w.z, w.w};
+  uint32_t out[8];
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    float f[4];
+    dword_f32<byte_dtype(FMT)>(in[d], f);
+    out[2 * d] = pack_exact<DT>(f[0], f[1]);
+    out[2 * d + 1] = pack_exact<DT>(f[2], f[3]);
+  }
+  c0 = make_uint4(out[0], out[1], out[2], out[3]);
+  c1 = make_uint4(out[4], out[5], out[6], out[7]);
 }
 
 }  // namespace w8

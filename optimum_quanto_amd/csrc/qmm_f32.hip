@@ -38,44 +38,17 @@ struct Args {
   int C, G;              // group size along K and groups per row (per-channel: C = K, G = 1)
 };
 
-// byte i (0..3) of a dword as the fp32 value of the stored element
-template <int FMT>
-__device__ __forceinline__ float byte_value(uint32_t word, int i) {
-  const uint32_t b = (word >> (8 * i)) & 0xFFu;
-  if constexpr (FMT == W_I8) return (float)(int8_t)b;
-  else if constexpr (FMT == W_F8E4M3) {  // the byte select of the converter is an immediate
-    return i == 0 ? __builtin_amdgcn_cvt_f32_fp8((int)word, 0) : i == 1 ? __builtin_amdgcn_cvt_f32_fp8((int)word, 1)
-         : i == 2 ? __builtin_amdgcn_cvt_f32_fp8((int)word, 2) : __builtin_amdgcn_cvt_f32_fp8((int)word, 3);
-  } else if constexpr (FMT == W_F8E5M2) {
-    return i == 0 ? __builtin_amdgcn_cvt_f32_bf8((int)word, 0) : i == 1 ? __builtin_amdgcn_cvt_f32_bf8((int)word, 1)
-         : i == 2 ? __builtin_amdgcn_cvt_f32_bf8((int)word, 2) : __builtin_amdgcn_cvt_f32_bf8((int)word, 3);
-  }
-  else if constexpr (FMT == W_F8FNUZ) return decode_e4m3fnuz(b);
-  else return (float)b;  // already masked plane bytes (v_cvt_f32_ubyteN)
-}
-// the four elements of plane h held by a dword of packed bytes (qbits), or the dword's four 8-bit elements
+// the four elements of plane h held by a dword of packed bytes (qbits), or the dword's four 8-bit elements, as fp32 (qh_common.h: byte_f32;
+// the masked plane bytes convert as unsigned bytes)
 template <int FMT>
 __device__ __forceinline__ void unpack4(uint32_t word, int h, float (&out)[4]) {
+  constexpr int QDT = FMT == W_I8 ? QUANTO_HIP_I8 : FMT == W_F8E4M3 ? QUANTO_HIP_F8_E4M3FN : FMT == W_F8E5M2 ? QUANTO_HIP_F8_E5M2
+                    : FMT == W_F8FNUZ ? QUANTO_HIP_F8_E4M3FNUZ : QUANTO_HIP_U8;
   uint32_t v = word;
   if constexpr (FMT == W_I4) v = (word >> (4 * h)) & 0x0F0F0F0Fu;
   if constexpr (FMT == W_I2) v = (word >> (2 * h)) & 0x03030303u;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) out[i] = byte_value<FMT>(v, i);
-}
-
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ float dpp_add(float v) {
-  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
-}
-// sum over the 64 lanes; lane 63 holds the total (same ladder as qbits_gemv.hip)
-__device__ __forceinline__ float wave_sum_lane63(float v) {
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  v = dpp_add<0x141>(v);
-  v = dpp_add<0x140>(v);
-  v = dpp_add<0x142, 0xA>(v);
-  v = dpp_add<0x143, 0xC>(v);
-  return v;
+  for (int i = 0; i < 4; ++i) out[i] = byte_f32<QDT>(v, i);
 }
 
 // ================================================================================================================================

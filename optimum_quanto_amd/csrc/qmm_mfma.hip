@@ -19,39 +19,12 @@
 
 namespace qh {
 
-enum WFmt { W_I8 = 0, W_F8E4M3 = 1, W_F8E5M2 = 2, W_I4 = 3 };
+using namespace w8;  // qh_mfma.h: W_I8, W_F8E4M3, W_F8E5M2, convert16
+enum { W_I4 = 3 };    // this unit's own format, behind the three 8-bit ones
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_BYTES = BM * BK * 2;  // one operand tile in LDS (16 KiB)
-
-__device__ __forceinline__ int lds_off(int row, int kc) { return row * (BK * 2) + ((kc ^ (row & 7)) << 4); }
-
-// 16 one-byte weights -> 16 elements of the activation dtype (two 16-byte LDS chunks)
-template <int DT, int FMT>
-__device__ __forceinline__ void convert16(const uint4& w, uint4& c0, uint4& c1) {
-  const uint32_t in[4] = {w.x, w.y, w.z, w.w};
-  uint32_t out[8];
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    float f0, f1, f2, f3;
-    if constexpr (FMT == W_I8) {
-      f0 = (float)(int8_t)(in[d] & 0xFFu);
-      f1 = (float)(int8_t)((in[d] >> 8) & 0xFFu);
-      f2 = (float)(int8_t)((in[d] >> 16) & 0xFFu);
-      f3 = (float)(int8_t)(in[d] >> 24);
-    } else if constexpr (FMT == W_F8E4M3) {
-      const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)in[d], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)in[d], true);
-      f0 = lo.x; f1 = lo.y; f2 = hi.x; f3 = hi.y;
-    } else {
-      const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)in[d], false), hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)in[d], true);
-      f0 = lo.x; f1 = lo.y; f2 = hi.x; f3 = hi.y;
-    }
-    out[2 * d] = pack_exact<DT>(f0, f1);
-    out[2 * d + 1] = pack_exact<DT>(f2, f3);
-  }
-  c0 = make_uint4(out[0], out[1], out[2], out[3]);
-  c1 = make_uint4(out[4], out[5], out[6], out[7]);
-}
+static_assert(BK * 2 == kTileRowBytes, "a K-tile of two-byte elements is one LDS row of tile_lds_off");
 
 // 16 packed bytes -> 16 low-nibble and 16 high-nibble weights as (OFFSET + q) in the activation dtype
 template <int DT>
@@ -134,24 +107,24 @@ __global__ void __launch_bounds__(256, 2) qmm_mfma_kernel(const MmaArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int c = tid + 256 * j, row = c >> 3, kc = c & 7;
-      *reinterpret_cast<uint4*>(sa + lds_off(row, kc)) = ra[j];
+      *reinterpret_cast<uint4*>(sa + tile_lds_off(row, kc)) = ra[j];
     }
     if constexpr (FMT == W_I4) {
       uint4 lo[2], hi[2];
       convert16_i4<DT>(rw[0], lo, hi);
       const int row = tid >> 2, part = tid & 3;
-      *reinterpret_cast<uint4*>(sb + lds_off(row, 2 * part)) = lo[0];
-      *reinterpret_cast<uint4*>(sb + lds_off(row, 2 * part + 1)) = lo[1];
-      *reinterpret_cast<uint4*>(sb + lds_off(64 + row, 2 * part)) = hi[0];
-      *reinterpret_cast<uint4*>(sb + lds_off(64 + row, 2 * part + 1)) = hi[1];
+      *reinterpret_cast<uint4*>(sb + tile_lds_off(row, 2 * part)) = lo[0];
+      *reinterpret_cast<uint4*>(sb + tile_lds_off(row, 2 * part + 1)) = lo[1];
+      *reinterpret_cast<uint4*>(sb + tile_lds_off(64 + row, 2 * part)) = hi[0];
+      *reinterpret_cast<uint4*>(sb + tile_lds_off(64 + row, 2 * part + 1)) = hi[1];
     } else {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int c = tid + 256 * j, row = c >> 2, part = c & 3;
         uint4 c0, c1;
         convert16<DT, FMT>(rw[j], c0, c1);
-        *reinterpret_cast<uint4*>(sb + lds_off(row, 2 * part)) = c0;
-        *reinterpret_cast<uint4*>(sb + lds_off(row, 2 * part + 1)) = c1;
+        *reinterpret_cast<uint4*>(sb + tile_lds_off(row, 2 * part)) = c0;
+        *reinterpret_cast<uint4*>(sb + tile_lds_off(row, 2 * part + 1)) = c1;
       }
     }
   };
@@ -193,9 +166,9 @@ __global__ void __launch_bounds__(256, 2) qmm_mfma_kernel(const MmaArgs a) {
       V8 fa[4], fb[4];
       const int kc = kk * 4 + (lane >> 4);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const V8*>(sa + lds_off(wm * 64 + i * 16 + (lane & 15), kc));
+      for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const V8*>(sa + tile_lds_off(wm * 64 + i * 16 + (lane & 15), kc));
 #pragma unroll
-      for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const V8*>(sb + lds_off(wn * 64 + j * 16 + (lane & 15), kc));
+      for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const V8*>(sb + tile_lds_off(wn * 64 + j * 16 + (lane & 15), kc));
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll

@@ -12,17 +12,13 @@
 //     buffers, one barrier per 128 bytes of K, fp8 on the K = 128 MX-format MFMA (unit scales), split-K with a sliced tail.  Serves every
 //     K * element size that is a multiple of 128, i.e. all the measured shapes (w8a8 / fp8a8, the dense 16-bit GEMM behind int4 prefill);
 //   * qbytes_native8_kernel (first): the r1-r4 kernel - K-tiles of 64 bytes per row for both operands, four stages of 32 KiB, 12 ds_read_b128,
-//     4 DMA issues and 32 (int8) or 64 (fp8, 16x16x32) MFMAs per wave and K-tile.  It still serves K * element size = 64 (mod 128) and
-//     QUANTO_HIP_NATIVE8_ROW128=0; its PAIRED loop is built by probes only (-DQH_N8_EXPERIMENTS).
+//     4 DMA issues and 32 (int8) or 64 (fp8, 16x16x32) MFMAs per wave and K-tile.  It serves K * element size = 64 (mod 128) and
+//     QUANTO_HIP_NATIVE8_ROW128=0.
 #include <cstdlib>
 #include <type_traits>
 
 #include "qmm_large_common.h"
 #include "qh_quantize.h"
-
-#ifndef QH_N8_ABLATE
-#define QH_N8_ABLATE 0  // timing experiments only: 1 = no DMA inside the K loop
-#endif
 
 namespace qh {
 namespace n8 {
@@ -50,6 +46,28 @@ template <>
 struct Acc<K_I8> {
   using V = i32x4;
 };
+
+// c += w x x for 64 bytes of K per row (the lane's 16 bytes of both operands): one MFMA, two of the 16x16x32 fp8 / bf8 ones
+template <int KIND>
+__device__ __forceinline__ void mma(typename Acc<KIND>::V& c, const uint4& w, const uint4& x) {
+  if constexpr (KIND == K_I8) {
+    c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, w), __builtin_bit_cast(i32x4, x), c, 0, 0, 0);
+  } else if constexpr (KIND == K_BF16) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
+  } else if constexpr (KIND == K_F16) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
+  } else {
+    const long wlo = (long)(((unsigned long)w.y << 32) | w.x), whi = (long)(((unsigned long)w.w << 32) | w.z);
+    const long xlo = (long)(((unsigned long)x.y << 32) | x.x), xhi = (long)(((unsigned long)x.w << 32) | x.z);
+    if constexpr (KIND == K_F8E4M3) {
+      c = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(wlo, xlo, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(whi, xhi, c, 0, 0, 0);
+    } else {
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(wlo, xlo, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(whi, xhi, c, 0, 0, 0);
+    }
+  }
+}
 
 // lt::Args (x / w: 1 byte per element, 2 for the dense 16-bit kinds; `partials` carries int32 or fp32 quads) plus the poll limit of the split-K tail below:
 // S workgroups per tile (128-byte-row kernel), workgroup (tile, sp) multiplies the K range sp of S; workspace contract of the split-K tail in qh_mfma.h
@@ -373,11 +391,9 @@ __device__ __forceinline__ void splitk_reduce(const Args& a, uint8_t* smem, cons
   complete();
 }
 
-// PAIRED (fp8 kinds, K % 128 == 0): K-tiles are consumed two at a time by the K = 128 MX-format MFMA (unit scales), which runs
-// at twice the rate of the 16x16x32 fp8 MFMA - see the paired loop below.
 // SMALL: 128x128 tile with four waves of 128 x 32 (16 KiB stages: two workgroups share a CU) for shapes whose 256-tiles cannot
 // occupy the chip; otherwise 256x256 with eight waves of 128 x 64.
-template <int ODT, int KIND, bool PAIRED = false, bool SMALL = false, bool QOUT = false>
+template <int ODT, int KIND, bool SMALL = false, bool QOUT = false>
 __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_kernel(const Args a) {
   using AV = typename Acc<KIND>::V;
   constexpr int BM = SMALL ? 128 : 256, BN = BM;
@@ -471,177 +487,74 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_kernel(co
   uint4 xf[8], wq[2][NJ];
   auto read_x = [&](const uint8_t* st, int i) -> uint4 { return *reinterpret_cast<const uint4*>(st + aoff0 + i * 1024); };
   auto read_w = [&](const uint8_t* st, int j) -> uint4 { return *reinterpret_cast<const uint4*>(st + boff0 + j * 1024); };
-  auto mma = [&](AV& c, const uint4& w, const uint4& x) {
-    if constexpr (KIND == K_I8) {
-      c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, w), __builtin_bit_cast(i32x4, x), c, 0, 0, 0);
-    } else if constexpr (KIND == K_BF16) {
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-    } else if constexpr (KIND == K_F16) {
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-    } else {
-      const long wlo = (long)(((unsigned long)w.y << 32) | w.x), whi = (long)(((unsigned long)w.w << 32) | w.z);
-      const long xlo = (long)(((unsigned long)x.y << 32) | x.x), xhi = (long)(((unsigned long)x.w << 32) | x.z);
-      if constexpr (KIND == K_F8E4M3) {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(wlo, xlo, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(whi, xhi, c, 0, 0, 0);
-      } else {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(wlo, xlo, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(whi, xhi, c, 0, 0, 0);
-      }
-    }
-  };
 
-  if constexpr (PAIRED) {
-    // ---- fp8 x fp8 on v_mfma_scale_f32_16x16x128_f8f6f4 --------------------------------------------------------------------
-    // An operand is 32 bytes per lane: the lane's 16 bytes of tile 2p (k = 16g..16g+15 of that tile) followed by its 16 bytes
-    // of tile 2p+1 - the same k assignment in both operands.  Pair p = 32 MFMAs per wave in two halves:
-    //   half A: token fragments 0..3 x weight fragments 0..3, while X[4..7] of THIS pair are fetched;
-    //   (own DMA share of tiles 2p+2, 2p+3 landed -> barrier -> refill the stages of tiles 2p, 2p+1 with tiles 2p+4, 2p+5)
-    //   half B: weight-fragment-major over token fragments 4..7; X[0..3] and each W[j], dead after its last MFMA, are
-    //           refetched for pair p+1.
-    typedef __attribute__((ext_vector_type(8))) int i32x8;
-    constexpr int FMTSEL = KIND == K_F8E5M2 ? 1 : 0;  // cbsz / blgp: 0 = fp8 (e4m3), 1 = bf8 (e5m2)
-    i32x8 X[8], W[NJ];
-    auto load_pair = [&](i32x8& dst, const uint8_t* s0, const uint8_t* s1, int off) {
-      const uint4 lo = *reinterpret_cast<const uint4*>(s0 + off), hi = *reinterpret_cast<const uint4*>(s1 + off);
-      dst = i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
-    };
-    auto mma128 = [&](AV& c, const i32x8& w, const i32x8& x) {
-      if constexpr (KIND == K_F8E4M3 || KIND == K_F8E5M2) {
-        c = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, x, c, FMTSEL, FMTSEL, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);  // scales 2^0
-      } else {  // other kinds: the two tiles of the pair as two MFMAs (same schedule, half as many barriers as the per-tile loop)
-        const uint4 wl = make_uint4(w[0], w[1], w[2], w[3]), wh = make_uint4(w[4], w[5], w[6], w[7]);
-        const uint4 xl = make_uint4(x[0], x[1], x[2], x[3]), xh = make_uint4(x[4], x[5], x[6], x[7]);
-        mma(c, wl, xl);
-        mma(c, wh, xh);
-      }
-    };
-    const int np = nk >> 1;
-    // prologue: tiles 0..3 in flight, pair 0 visible, its W and X[0..3] in registers
+  // prologue: tiles 0, 1, 2 in flight; tiles 0 and 1 visible (tile 1 feeds the prefetches issued during tile 0)
+  issue(0, 0);
+  if (nk > 1) issue(1, 1);
+  if (nk > 2) {
+    issue(2, 2);
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  } else {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  ftab.park(smem + RING_BYTES, tid);
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
-      if (t < nk) issue(t, t);
-    if (nk > 2)
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ftab.park(smem + RING_BYTES, tid);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+  for (int j = 0; j < NJ; ++j) wq[0][j] = read_w(smem, j);
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) load_pair(W[j], smem, smem + STAGE_BYTES, boff0 + j * 1024);
+  for (int i = 0; i < 8; ++i) xf[i] = read_x(smem, i);
+
+  // tile kt (stage kt & 3): refill the stage of tile kt-1 with tile kt+3, prefetch from the stage of tile kt+1, and before
+  // the closing barrier wait for the own DMA share of tile kt+2 (tile kt+3 may stay in flight)
+  auto tile = [&](int kt, auto stage_tag, bool dma, int wait_mode /* 2: vmcnt(4), 1: vmcnt(0), 0: none */, bool barrier) {
+    constexpr int ST = decltype(stage_tag)::value, P = ST & 1, SN = (ST + 1) & 3, SF = (ST + 3) & 3;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) load_pair(X[i], smem, smem + STAGE_BYTES, aoff0 + i * 1024);
-    // (this loop keeps run-time stage pointers: unrolled over the pair parity it spills - 8-register operand tuples - and a
-    // pair of 32 K = 128 MFMAs amortises the bookkeeping)
-    for (int p = 0; p < np; ++p) {
-      const uint8_t* c0 = smem + ((2 * p) & 3) * STAGE_BYTES;
-      const uint8_t* c1 = smem + ((2 * p + 1) & 3) * STAGE_BYTES;
-      const uint8_t* n0s = smem + ((2 * p + 2) & 3) * STAGE_BYTES;
-      const uint8_t* n1s = smem + ((2 * p + 3) & 3) * STAGE_BYTES;
-      // ---- half A ----
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          mma128(acc[j][i], W[j], X[i]);
-          if (j == 1) load_pair(X[4 + i], c0, c1, aoff0 + (4 + i) * 1024);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      if (p + 1 < np) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tiles 2p+2, 2p+3 (issued one pair ago; nothing younger is in flight)
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // X[4..7] returned: this wave is done reading tiles 2p, 2p+1
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (2 * p + 4 < nk) issue(2 * p + 4, (2 * p) & 3);
-      if (2 * p + 5 < nk) issue(2 * p + 5, (2 * p + 1) & 3);
-      // ---- half B ----
+    for (int i = 0; i < 8; ++i) {
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-        for (int i = 4; i < 8; ++i) {
-          mma128(acc[j][i], W[j], X[i]);
-          // X[0..3] of the next pair (dead since half A): 4 / NJ of them behind each weight fragment's MFMAs
-          if (i - 4 < 4 / NJ) load_pair(X[j * (4 / NJ) + (i - 4)], n0s, n1s, aoff0 + (j * (4 / NJ) + (i - 4)) * 1024);
-          if (i == 7) load_pair(W[j], n0s, n1s, boff0 + j * 1024);            // W[j] of the next pair: its last MFMA was just issued
-          __builtin_amdgcn_sched_barrier(0);
+        mma<KIND>(acc[j][i], wq[P][j], xf[i]);
+        if (j == 1 % NJ) {
+          if (i < NJ) wq[P ^ 1][i] = *reinterpret_cast<const uint4*>(wbs(SN) + i * 1024);
         }
+        if (j == 2 % NJ) {
+          if (i >= 4 && dma) issue_piece_to(kt + 3, mdst[SF], i - 4);
+        }
+        if (j == NJ - 1) xf[i] = *reinterpret_cast<const uint4*>(xbs(SN) + i * 1024);  // same fragment of the next tile
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
-  } else {
-  // prologue: tiles 0, 1, 2 in flight; tiles 0 and 1 visible (tile 1 feeds the prefetches issued during tile 0)
-    issue(0, 0);
-    if (nk > 1) issue(1, 1);
-    if (nk > 2) {
-      issue(2, 2);
+    if (wait_mode == 2)
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else {
+    else if (wait_mode == 1)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (barrier) {
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
     }
-    ftab.park(smem + RING_BYTES, tid);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) wq[0][j] = read_w(smem, j);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) xf[i] = read_x(smem, i);
-
-    // tile kt (stage kt & 3): refill the stage of tile kt-1 with tile kt+3, prefetch from the stage of tile kt+1, and before
-    // the closing barrier wait for the own DMA share of tile kt+2 (tile kt+3 may stay in flight)
-    auto tile = [&](int kt, auto stage_tag, bool dma, int wait_mode /* 2: vmcnt(4), 1: vmcnt(0), 0: none */, bool barrier) {
-      constexpr int ST = decltype(stage_tag)::value, P = ST & 1, SN = (ST + 1) & 3, SF = (ST + 3) & 3;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          mma(acc[j][i], wq[P][j], xf[i]);
-          if (j == 1 % NJ) {
-            if (i < NJ) wq[P ^ 1][i] = *reinterpret_cast<const uint4*>(wbs(SN) + i * 1024);
-          }
-          if (j == 2 % NJ) {
-#if QH_N8_ABLATE != 1
-            if (i >= 4 && dma) issue_piece_to(kt + 3, mdst[SF], i - 4);
-#endif
-          }
-          if (j == NJ - 1) xf[i] = *reinterpret_cast<const uint4*>(xbs(SN) + i * 1024);  // same fragment of the next tile
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      if (wait_mode == 2)
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else if (wait_mode == 1)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (barrier) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-    };
-    using st0 = std::integral_constant<int, 0>;
-    using st1 = std::integral_constant<int, 1>;
-    using st2 = std::integral_constant<int, 2>;
-    using st3 = std::integral_constant<int, 3>;
-    int kt = 0;
-    for (; kt + 6 < nk; kt += 4) {  // steady state: every one of the four tiles still has a tile kt+3 to fetch
-      tile(kt, st0{}, true, 2, true);
-      tile(kt + 1, st1{}, true, 2, true);
-      tile(kt + 2, st2{}, true, 2, true);
-      tile(kt + 3, st3{}, true, 2, true);
-    }
-    // at most six tiles left (kt is a multiple of 4): nothing, or less, to prefetch - straight-line so the stage stays static
-#define QH_TAIL_TILE(J, STAGE)                                                                                           \
-    if (kt + (J) < nk)                                                                                                     \
-      tile(kt + (J), STAGE{}, kt + (J) + 3 < nk, kt + (J) + 3 < nk ? 2 : (kt + (J) + 2 < nk ? 1 : 0), kt + (J) + 1 < nk)
-    QH_TAIL_TILE(0, st0);
-    QH_TAIL_TILE(1, st1);
-    QH_TAIL_TILE(2, st2);
-    QH_TAIL_TILE(3, st3);
-    QH_TAIL_TILE(4, st0);
-    QH_TAIL_TILE(5, st1);
-#undef QH_TAIL_TILE
-
+  };
+  using st0 = std::integral_constant<int, 0>;
+  using st1 = std::integral_constant<int, 1>;
+  using st2 = std::integral_constant<int, 2>;
+  using st3 = std::integral_constant<int, 3>;
+  int kt = 0;
+  for (; kt + 6 < nk; kt += 4) {  // steady state: every one of the four tiles still has a tile kt+3 to fetch
+    tile(kt, st0{}, true, 2, true);
+    tile(kt + 1, st1{}, true, 2, true);
+    tile(kt + 2, st2{}, true, 2, true);
+    tile(kt + 3, st3{}, true, 2, true);
   }
+  // at most six tiles left (kt is a multiple of 4): nothing, or less, to prefetch - straight-line so the stage stays static
+#define QH_TAIL_TILE(J, STAGE)                                                                                           \
+  if (kt + (J) < nk)                                                                                                     \
+    tile(kt + (J), STAGE{}, kt + (J) + 3 < nk, kt + (J) + 3 < nk ? 2 : (kt + (J) + 2 < nk ? 1 : 0), kt + (J) + 1 < nk)
+  QH_TAIL_TILE(0, st0);
+  QH_TAIL_TILE(1, st1);
+  QH_TAIL_TILE(2, st2);
+  QH_TAIL_TILE(3, st3);
+  QH_TAIL_TILE(4, st0);
+  QH_TAIL_TILE(5, st1);
+#undef QH_TAIL_TILE
 
   epilogue<ODT, KIND, NJ, BM, BN, 8, QOUT>(a, acc, smem, smem + RING_BYTES, m0, n0, wm, wn, wave, lane);
 }
@@ -659,7 +572,8 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_kernel(co
 //     place), with the buffer bookkeeping per pair: even step = second half of the current buffer, odd step = first half of the
 //     other buffer + the 8 DMA pieces of pair p+2 into the buffer that was just read out.  ONE barrier per pair (before the odd
 //     step: it publishes pair p+1 and retires the reads of pair p), half as many as before;
-//   * fp8: one v_mfma_scale_f32_16x16x128_f8f6f4 per fragment pair and 128-byte tile, as in the paired loop above.
+//   * fp8: one v_mfma_scale_f32_16x16x128_f8f6f4 (the K = 128 MX-format MFMA with unit scales, twice the rate of the 16x16x32 fp8 MFMA) per
+//     fragment pair and 128-byte tile, in two halves of 16 MFMAs around the pair's one barrier (described at the loop).
 // Needs K * element size % 128 == 0; everything else stays on the 64-byte-row kernel (QUANTO_HIP_NATIVE8_ROW128=0 forces that one).
 // =============================================================================================================================
 __device__ __forceinline__ int swz128(int row) { return (row >> 1) & 7; }
@@ -817,15 +731,6 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_r128_kern
     // ---- int8 / 16-bit: k-steps of 64 bytes; xf is refilled in place, the weight fragments ping-pong between two register sets ----
     uint4 xf[8], wq[2][NJ];
     auto rd = [&](const uint8_t* p) -> uint4 { return *reinterpret_cast<const uint4*>(p); };
-    auto mma = [&](AV& c, const uint4& w, const uint4& x) {
-      if constexpr (KIND == K_I8) {
-        c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, w), __builtin_bit_cast(i32x4, x), c, 0, 0, 0);
-      } else if constexpr (KIND == K_BF16) {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-      } else {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-      }
-    };
     // fragment bases per half: loop constants in registers (the 16-bit offset field of ds_read carries buffer and fragment index)
     const uint8_t* xh[2] = {smem + aoff, smem + (aoff ^ 64)};
     const uint8_t* wh[2] = {smem + boff, smem + (boff ^ 64)};
@@ -845,7 +750,7 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_r128_kern
       for (int i = 0; i < 8; ++i) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-          mma(acc[j][i], wq[0][j], xf[i]);
+          mma<KIND>(acc[j][i], wq[0][j], xf[i]);
           if (j == 1 % NJ) {
             if (i < NJ) wq[1][i] = rd(wp(B, 1) + i * FR);
           }
@@ -863,7 +768,7 @@ __global__ void __launch_bounds__(SMALL ? 256 : 512, 1) qbytes_native8_r128_kern
       for (int i = 0; i < 8; ++i) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-          mma(acc[j][i], wq[1][j], xf[i]);
+          mma<KIND>(acc[j][i], wq[1][j], xf[i]);
           if (j == 1 % NJ) {
             if (i < NJ && has_next) wq[0][i] = rd(wp(B ^ 1, 0) + i * FR);
           }
@@ -924,14 +829,13 @@ static int raster_group() {
   return g < 1 ? 1 : g;
 }
 
-template <int ODT, int KIND, bool PAIRED, bool SMALL, bool QOUT>
+template <int ODT, int KIND, bool SMALL, bool QOUT>
 static int launch_cfg(const Args& a, hipStream_t stream) {
   constexpr int T = SMALL ? 128 : 256;
   constexpr int need = STAGES * 2 * T * BK + FeatureTable<ODT, T>::BYTES;  // 128 KiB (64 KiB for the 128-tile: two workgroups per CU; the epilogue parks in it) + scale / bias table
   const int tiles = ((a.N + T - 1) / T) * ((a.M + T - 1) / T);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_native8_kernel<ODT, KIND, PAIRED, SMALL, QOUT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, need);
-  hipLaunchKernelGGL((qbytes_native8_kernel<ODT, KIND, PAIRED, SMALL, QOUT>), dim3(tiles), dim3(SMALL ? 256 : 512), need, stream, a);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qbytes_native8_kernel<ODT, KIND, SMALL, QOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, need);
+  hipLaunchKernelGGL((qbytes_native8_kernel<ODT, KIND, SMALL, QOUT>),dim3(tiles), dim3(SMALL ? 256 : 512), need, stream, a);
   return launch_status();
 }
 
@@ -1001,15 +905,8 @@ static int launch(Args a, void* workspace, size_t workspace_bytes, hipStream_t s
   // 128-byte rows (full-line vector-L1 fills, one barrier per 128 bytes of K) whenever K allows
   if ((a.K * ES) % 128 == 0 && env_int("QUANTO_HIP_NATIVE8_ROW128", 1) != 0)
     return small ? launch_r128<ODT, KIND, true, QOUT>(a, stream) : launch_r128<ODT, KIND, false, QOUT>(a, stream);
-  // 64-byte rows: K * element size = 64 (mod 128).  (r6: the PAIRED instantiations of this kernel - two 64-byte tiles per K = 128 MX-format MFMA - were
-  // reachable only where the 128-byte-row kernel applies as well, i.e. through QUANTO_HIP_NATIVE8_ROW128=0, and left the product library; the
-  // loop stays in the source for probes built with -DQH_N8_EXPERIMENTS)
-#ifdef QH_N8_EXPERIMENTS
-  constexpr bool FP8 = KIND == K_F8E4M3 || KIND == K_F8E5M2;
-  if (FP8 && (a.K * ES) % 128 == 0 && env_int("QUANTO_HIP_PAIRED", 1) != 0)
-    return small ? launch_cfg<ODT, KIND, true, true, QOUT>(a, stream) : launch_cfg<ODT, KIND, true, false, QOUT>(a, stream);
-#endif
-  return small ? launch_cfg<ODT, KIND, false, true, QOUT>(a, stream) : launch_cfg<ODT, KIND, false, false, QOUT>(a, stream);
+  // 64-byte rows: K * element size = 64 (mod 128), or the 128-byte-row kernel switched off
+  return small ? launch_cfg<ODT, KIND, true, QOUT>(a, stream) : launch_cfg<ODT, KIND, false, QOUT>(a, stream);
 }
 
 }  // namespace n8
