@@ -8,7 +8,8 @@ header ([QUANTO_HIP_WS_COUNTER_BYTES of arrival counters, zero on entry and rest
 
 Every row calls the C ABI through ``quanto_hip.lib._c`` with pointers into a ``containment.Arena``: the test owns the output and the workspace.  Per entry a
 ``Family`` gives the plan (host only, "needs no device"), the problem (host tensors, the outputs' types and the oracle gate the route already has elsewhere in
-the suite - no tolerance is defined here) and the call.
+the suite - no tolerance is defined here) and the call (a ``bias`` region - ``bias0`` ... for the multi entries - is passed where the arena has one: the
+problems of this file have none, tests/exact_cases.py adds them).
 
 Shapes follow the support rules in csrc/: M and N are no multiples of the 64 / 128 / 256 tiles where the rule allows it and the smallest legal multiple plus
 one unit where it does not; K is two to twelve K-tiles.  Where a convolution row forces a K split its K has that many K-tiles (a forced split is clamped to
@@ -23,7 +24,7 @@ from typing import Callable, Dict, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from helpers import (BF16, E4M3, E5M2, F16, F32, I8, TORCH_DT, assert_close_to_exact, make_qbits_problem, make_qbytes_problem, to_numpy,
+from helpers import (BF16, E4M3, E4M3FNUZ, E5M2, F16, F32, I8, TORCH_DT, assert_close_to_exact, make_qbits_problem, make_qbytes_problem, to_numpy,
                      to_torch)
 from optimum_quanto_amd.library import ops
 from optimum_quanto_amd.library.hip import quanto_hip
@@ -34,7 +35,7 @@ OK, EINVAL, ENOTSUP = 0, -1, -2
 AUTO, NAIVE, GEMV, MFMA, MFMA_LARGE, SKINNY, NATIVE8, DEQUANT_MFMA, MFMA_FUSED4, MMV, MFMA_LARGE4 = range(11)
 KERNEL_NAMES = {NAIVE: "naive", GEMV: "gemv", MFMA: "mfma", MFMA_LARGE: "mfma_large", SKINNY: "skinny", NATIVE8: "mfma_native8",
                 DEQUANT_MFMA: "dequant_mfma", MFMA_FUSED4: "mfma_fused4", MMV: "mmv", MFMA_LARGE4: "mfma_large4"}
-DT_CODE = {"fp32": F32, "fp16": F16, "bf16": BF16, "int8": I8, "e4m3fn": E4M3, "e5m2": E5M2}
+DT_CODE = {"fp32": F32, "fp16": F16, "bf16": BF16, "int8": I8, "e4m3fn": E4M3, "e5m2": E5M2, "e4m3fnuz": E4M3FNUZ}
 DT_SIZE = {"fp32": 4, "fp16": 2, "bf16": 2}
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -138,7 +139,7 @@ class QBitsMM:
     def call(row: Row, a, ws_ptr: int, ws_bytes: int) -> int:
         (M, N, K), f = row.shape, row.f
         code = DT_CODE[f["dt"]]
-        return lib().quanto_hip_qbits_mm(a.ptr("x"), a.ptr("packed"), a.ptr("scale"), a.ptr("shift"), None, a.ptr("y"), M, N, K, f["bits"], f["gs"], code,
+        return lib().quanto_hip_qbits_mm(a.ptr("x"), a.ptr("packed"), a.ptr("scale"), a.ptr("shift"), a.ptr("bias") or None, a.ptr("y"), M, N, K, f["bits"], f["gs"], code,
                                          code, row.kernel, ws_ptr or None, ws_bytes, _stream())
 
 
@@ -202,7 +203,7 @@ class QBytesMM:
     def call(row: Row, a, ws_ptr: int, ws_bytes: int) -> int:
         M, N, K = row.shape
         adt, bdt, odt = QBytesMM._codes(row)
-        return lib().quanto_hip_qbytes_mm_ws(a.ptr("a"), a.ptr("b"), a.ptr("scales"), None, a.ptr("y"), M, N, K, adt, bdt, odt, row.kernel, ws_ptr or None,
+        return lib().quanto_hip_qbytes_mm_ws(a.ptr("a"), a.ptr("b"), a.ptr("scales"), a.ptr("bias") or None, a.ptr("y"), M, N, K, adt, bdt, odt, row.kernel, ws_ptr or None,
                                              ws_bytes, _stream())
 
 
@@ -213,6 +214,11 @@ def _i64(values):
 
 def _ptrs(a, names):
     return (ctypes.c_void_p * len(names))(*[a.ptr(n) for n in names])
+
+
+def _bias_ptrs(a, n):
+    """The members' bias regions (bias0, bias1, ...) where the arena has them; NULL for a problem without a bias."""
+    return _ptrs(a, [f"bias{i}" for i in range(n)]) if a.ptr("bias0") else None
 
 
 class QBitsMulti:
@@ -261,7 +267,7 @@ class QBitsMulti:
         (M, Ns, K), f = row.shape, row.f
         n, code = len(Ns), DT_CODE[f["dt"]]
         names = lambda k: [f"{k}{i}" for i in range(n)]  # noqa: E731
-        return lib().quanto_hip_qbits_mm_multi_ws(a.ptr("x"), n, _ptrs(a, names("packed")), _ptrs(a, names("scale")), _ptrs(a, names("shift")), None,
+        return lib().quanto_hip_qbits_mm_multi_ws(a.ptr("x"), n, _ptrs(a, names("packed")), _ptrs(a, names("scale")), _ptrs(a, names("shift")), _bias_ptrs(a, n),
                                                   _ptrs(a, names("y")), _i64(Ns), M, K, f["bits"], f["gs"], code, code, ws_ptr or None, ws_bytes, _stream())
 
 
@@ -301,7 +307,7 @@ class QBytesMulti:
         (M, Ns, K), f = row.shape, row.f
         n, code = len(Ns), DT_CODE[f["dt"]]
         names = lambda k: [f"{k}{i}" for i in range(n)]  # noqa: E731
-        return lib().quanto_hip_qbytes_mm_multi_ws(a.ptr("a"), n, _ptrs(a, names("b")), _ptrs(a, names("scales")), None, _ptrs(a, names("y")), _i64(Ns), M, K,
+        return lib().quanto_hip_qbytes_mm_multi_ws(a.ptr("a"), n, _ptrs(a, names("b")), _ptrs(a, names("scales")), _bias_ptrs(a, n), _ptrs(a, names("y")), _i64(Ns), M, K,
                                                    code, DT_CODE[f["b"]], code, ws_ptr or None, ws_bytes, _stream())
 
 
@@ -340,7 +346,7 @@ class QBitsA8:
     def call(row: Row, a, ws_ptr: int, ws_bytes: int) -> int:
         (M, N, K), f = row.shape, row.f
         code = DT_CODE[f["dt"]]
-        return lib().quanto_hip_qbits_mm_a8(a.ptr("a"), a.ptr("a_scale"), a.ptr("packed"), a.ptr("scale"), a.ptr("shift"), None, a.ptr("y"), M, N, K,
+        return lib().quanto_hip_qbits_mm_a8(a.ptr("a"), a.ptr("a_scale"), a.ptr("packed"), a.ptr("scale"), a.ptr("shift"), a.ptr("bias") or None, a.ptr("y"), M, N, K,
                                             f["bits"], 128, DT_CODE[f["a"]], code, code, ws_ptr or None, ws_bytes, _stream())
 
 
@@ -456,7 +462,7 @@ class QBytesConv2d:
     def call(cls, row: Row, a, ws_ptr: int, ws_bytes: int) -> int:
         g, f = row.shape, row.f
         code = DT_CODE[f["dt"]]
-        args = (a.ptr("x"), a.ptr("w"), a.ptr("scales"), None, a.ptr("y"), *g.args(), code, DT_CODE[f["b"]], code)
+        args = (a.ptr("x"), a.ptr("w"), a.ptr("scales"), a.ptr("bias") or None, a.ptr("y"), *g.args(), code, DT_CODE[f["b"]], code)
         if cls.depthwise:
             return lib().quanto_hip_qbytes_conv2d_depthwise(*args, _stream())
         return lib().quanto_hip_qbytes_conv2d(*args, ws_ptr or None, ws_bytes, _stream())
@@ -492,7 +498,7 @@ class QBitsConv2d:
     def call(row: Row, a, ws_ptr: int, ws_bytes: int) -> int:
         g, f = row.shape, row.f
         code = DT_CODE[f["dt"]]
-        return lib().quanto_hip_qbits_conv2d(a.ptr("x"), a.ptr("packed"), a.ptr("scale"), a.ptr("shift"), None, a.ptr("y"), *g.args(), f["bits"], f["gs"], code,
+        return lib().quanto_hip_qbits_conv2d(a.ptr("x"), a.ptr("packed"), a.ptr("scale"), a.ptr("shift"), a.ptr("bias") or None, a.ptr("y"), *g.args(), f["bits"], f["gs"], code,
                                              code, ws_ptr or None, ws_bytes, _stream())
 
 
@@ -537,7 +543,7 @@ class QBytesConv2dA8:
     @staticmethod
     def call(row: Row, a, ws_ptr: int, ws_bytes: int) -> int:
         g, f = row.shape, row.f
-        return lib().quanto_hip_qbytes_conv2d_a8(a.ptr("x"), a.ptr("a_scale"), a.ptr("w"), a.ptr("w_scale"), None, a.ptr("y"), *g.args(), DT_CODE[f["a"]],
+        return lib().quanto_hip_qbytes_conv2d_a8(a.ptr("x"), a.ptr("a_scale"), a.ptr("w"), a.ptr("w_scale"), a.ptr("bias") or None, a.ptr("y"), *g.args(), DT_CODE[f["a"]],
                                                  DT_CODE[f["b"]], DT_CODE[f["dt"]], ws_ptr or None, ws_bytes, _stream())
 
 
