@@ -8,103 +8,6 @@ void set_last_kernel(const char* name) { g_last_kernel = name; }
 
 int launch_status() { return hipGetLastError() == hipSuccess ? QUANTO_HIP_OK : QUANTO_HIP_ELAUNCH; }
 
-// implemented in the kernel translation units
-int unpack_dispatch(const uint8_t*, uint8_t*, int64_t, int, hipStream_t);
-int dequantize_qbits_dispatch(const uint8_t*, const void*, const void*, void*, const PackedGeom&, int, bool, hipStream_t);
-int qbytes_mm_naive(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, hipStream_t);
-int qbits_mm_naive(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool,
-                   hipStream_t);
-bool qbits_gemv_supported(int64_t, const PackedGeom&, int);
-int qbits_mm_gemv(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool,
-                  hipStream_t);
-int qbits_mm_gemv_multi(const void*, int, const uint8_t* const*, const void* const*, const void* const*, const void* const*, void* const*,
-                        const int64_t*, int64_t, int64_t, int, bool, hipStream_t);
-bool qbytes_gemv_supported(int64_t, int64_t, int64_t, int, int, int);
-int qbytes_mm_gemv(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, hipStream_t);
-bool qbytes_mfma_supported(int64_t, int64_t, int64_t, int, int, int);
-int qbytes_mm_mfma(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, hipStream_t);
-bool qbytes_mfma_large_supported(int64_t, int64_t, int64_t, int, int, int);
-int qbytes_mm_mfma_large(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, void*, size_t, hipStream_t);
-size_t qbytes_mfma_large_workspace(int64_t, int64_t, int64_t);
-int quantize_symmetric(const void*, const void*, void*, int64_t, int64_t, int, int, int, hipStream_t);
-int dequantize_symmetric(const void*, const void*, void*, int64_t, int, int, hipStream_t);
-int quantize_affine(const void*, const void*, const void*, void*, int64_t, int64_t, int, int, bool, hipStream_t);
-int quantize_affine_packed(const void*, const void*, const void*, void*, int64_t, int64_t, int, int, bool, hipStream_t);
-int pack_weights(const uint8_t*, uint8_t*, int64_t, int64_t, int, hipStream_t);
-// convolutions: a call's geometry travels as one ConvGeom (qh_conv.h)
-bool qbits_conv2d_supported(const ConvGeom&, const PackedGeom&, int);
-int qbits_conv2d_mfma(const void*, const uint8_t*, const void*, const void*, const void*, void*, const ConvGeom&, const PackedGeom&, int, bool, void*, size_t,
-                      hipStream_t);
-size_t conv2d_workspace(int64_t, int64_t, int64_t);
-// depthwise convolution with an 8-bit weight (r6, qconv_depthwise.hip)
-int qbytes_conv2d_depthwise(const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, hipStream_t, bool* strip);
-size_t conv2d_dense_weight_bytes(int64_t, int64_t);
-bool conv2d_rows_eligible(const ConvGeom&);
-int qdense_conv2d_rows(const void*, const void*, const void*, void*, const ConvGeom&, int, void*, size_t, hipStream_t);
-// convolution with quantized activations on the 8-bit matrix instructions (qconv_a8.hip)
-int qbytes_conv2d_a8_kind(int, int, int);
-size_t conv2d_a8_workspace(int64_t, int64_t, int64_t);
-// (x, a_scale, w, w_scale, bias, out_scale, y, ...): out_scale == nullptr -> the float output, else the output codes (the three products below alike)
-int qbytes_conv2d_a8(const void*, const void*, const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t,
-                     hipStream_t, int*);
-int qbytes_conv2d_mfma(const void*, const void*, const void*, const void*, void*, const ConvGeom&, int, int, int, void*, size_t, hipStream_t, bool* rows);
-int qbytes_mm_gemv_multi(const void*, int, const void* const*, const void* const*, const void* const*, void* const*, const int64_t*, int64_t,
-                         int64_t, int, int, hipStream_t);
-bool qbytes_skinny_multi_supported(int, const int64_t*, int64_t, int64_t, int, int, int);
-size_t qbytes_skinny_multi_workspace(int, const int64_t*, int64_t, int64_t);
-int qbytes_mm_skinny_multi(const void*, int, const void* const*, const void* const*, const void* const*, void* const*, const int64_t*, int64_t,
-                           int64_t, int, int, int, void*, size_t, hipStream_t);
-bool qbytes_skinny_supported(int64_t, int64_t, int64_t, int, int, int);
-size_t qbytes_skinny_workspace(int64_t, int64_t, int64_t, int, int, int);
-int qbytes_mm_skinny(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, void*, size_t, hipStream_t);
-bool dense_mm_large_supported(int64_t, int64_t, int64_t, int);
-int dense_mm_large(const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, hipStream_t);
-bool dense_mm_wd_supported(int64_t, int64_t, int64_t, int);
-int dense_mm_wd(const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, hipStream_t);
-bool qbytes_native8_supported(int64_t, int64_t, int64_t, int, int, int);
-size_t qbytes_native8_workspace(int64_t, int64_t, int64_t, int, int, int);
-int qbytes_mm_native8(const void*, const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, void*, size_t,
-                      hipStream_t);
-bool qbits_skinny_multi_supported(int, const int64_t*, int64_t, int64_t, int);
-size_t qbits_skinny_multi_workspace(int, const int64_t*, int64_t, int64_t);
-int qbits_mm_skinny_multi(const void*, int, const uint8_t* const*, const void* const*, const void* const*, const void* const*, void* const*,
-                          const int64_t*, int64_t, int64_t, int, bool, void*, size_t, hipStream_t);
-bool qbits_mmv_supported(int64_t, const PackedGeom&, int);
-int qbits_mm_mmv(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool, hipStream_t);
-bool qbits_skinny_supported(int64_t, const PackedGeom&, int);
-size_t qbits_skinny_workspace(int64_t, const PackedGeom&, int);
-int qbits_mm_skinny(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool, void*,
-                    size_t, hipStream_t);
-bool qbits_mfma_supported(int64_t, const PackedGeom&, int);
-size_t qbits_mfma_workspace(int64_t, const PackedGeom&);
-int qbits_mm_mfma(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool, void*,
-                  size_t, hipStream_t);
-
-bool qbits_mfma_fused_supported(int64_t, const PackedGeom&, int);
-bool qbits_mfma_fused_needs_workspace(const PackedGeom&);
-size_t qbits_mfma_fused_workspace(int64_t, const PackedGeom&);
-int qbits_mm_mfma_fused(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool, void*,
-                        size_t, hipStream_t);
-
-bool qbits_mfma_large_supported(int64_t, const PackedGeom&, int);
-int qbits_mm_mfma_large(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool, hipStream_t);
-
-// fp32 activations (r6, qmm_f32.hip)
-bool qbits_gemv_f32_supported(int64_t, const PackedGeom&, int);
-bool qbits_mm_f32_supported(int64_t, const PackedGeom&, int);
-int qbits_mm_gemv_f32(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool, hipStream_t);
-int qbits_mm_f32(const void*, const uint8_t*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, bool, hipStream_t);
-bool qbytes_gemv_f32_supported(int64_t, int64_t, int64_t, int, int, int);
-bool qbytes_mm_f32_supported(int64_t, int64_t, int64_t, int, int, int);
-int qbytes_mm_gemv_f32(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, hipStream_t);
-int qbytes_mm_f32(const void*, const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, int, int, int, hipStream_t);
-
-// quantized activations x int4 / int2 weights (qbits_a8_fused.hip)
-bool qbits_a8_supported(int64_t, const PackedGeom&, int, int);
-size_t qbits_a8_workspace(int64_t, const PackedGeom&);
-int qbits_mm_a8(const void*, const void*, const uint8_t*, const void*, const void*, const void*, const void*, void*, int64_t, const PackedGeom&, int, int, bool,
-                void*, size_t, hipStream_t);
-
 static bool is_float_dtype(int dt) { return dt == QUANTO_HIP_F32 || dt == QUANTO_HIP_F16 || dt == QUANTO_HIP_BF16; }
 
 static int check_qbits(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype, int shift_dtype, bool* int_shift) {
@@ -134,7 +37,16 @@ static bool prefer_gemv(int64_t M) { return M <= QUANTO_HIP_GEMV_MAX_M; }
 //             dense 256x256-tile GEMM: the dequantization cost is amortised over M rows instead of being paid per tile;
 //   the GEMV in passes / the register-staged 128x128 kernel / the naive kernel serve what those reject.
 static bool dequant_mfma_supported(int64_t M, const PackedGeom& g, int dtype) { return dense_mm_large_supported(M, g.N, g.K, dtype); }
-static size_t dequant_mfma_workspace(const PackedGeom& g) { return (size_t)g.N * g.K * 2; }
+static size_t dequant_mfma_workspace(int64_t, const PackedGeom& g, int) { return (size_t)g.N * g.K * 2; }
+static int qbits_mm_dequant_mfma(const QbitsCall& c) {
+  const PackedGeom& g = c.g;
+  if (!dequant_mfma_supported(c.M, g, c.dtype)) return QUANTO_HIP_ENOTSUP;
+  if (!c.workspace || c.workspace_bytes < dequant_mfma_workspace(c.M, g, c.dtype)) return QUANTO_HIP_EINVAL;
+  const int r = dequantize_qbits_dispatch(c.packed, c.scale, c.shift, c.workspace, g, c.dtype, c.int_shift, c.stream);
+  if (r != QUANTO_HIP_OK) return r;
+  return dense_mm_wd_supported(c.M, g.N, g.K, c.dtype) ? dense_mm_wd(c.x, c.workspace, c.bias, c.y, c.M, g.N, g.K, c.dtype, c.stream)
+                                                       : dense_mm_large(c.x, c.workspace, c.bias, c.y, c.M, g.N, g.K, c.dtype, c.stream);
+}
 
 // Fused int4 GEMM (qbits_mfma_fused.hip) vs dequantize + dense GEMM vs the streaming kernel, r3 measurements (us; fused / dequantize +
 // dense / streaming in passes of 64 rows):
@@ -146,7 +58,6 @@ static size_t dequant_mfma_workspace(const PackedGeom& g) { return (size_t)g.N *
 // The fused kernel's time is rounds of tiles x groups (its own model picks 64- or 128-token tiles and the K split, qbits_mfma_fused.hip);
 // dequantize + dense is flat in M up to ~1 k rows (one dequantize pass + a dense GEMM that cannot fill the chip) and wins once the
 // fused kernel needs more than ~1.6 rounds of 128-token tiles (1.2 until two 64-token workgroups shared a CU: (1536,4096,4096) 71.5 / 81.4).  QUANTO_HIP_FUSED4_MAX_COST (x 100) / _MIN_M override the limits in experiments.
-float qbits_mfma_fused_cost(int64_t, const PackedGeom&);
 // r5: the dense kernel behind dequantize + dense got faster (128-byte rows, qmm_native8.hip) and gains most on wide outputs (more tiles per round):
 // off the fitted grid AUTO was 1.31 x behind at (1024, K = 11008, N = 5120) (fused 193 vs 147 us) and 1.11 x at (1024,5120,5120) (87.8 vs 79.1),
 // while N = 4096 still hands over at ~1.6 rounds ((1536,4096,4096) 72.2 vs 83.9, (1536,14336,4096) 250 vs 256; profiles/r05_auto_vs_best.jsonl,
@@ -211,34 +122,54 @@ struct Plan {
   int64_t workspace;  // bytes the kernel needs for this call (0: none, or the kernel does not take the call)
 };
 
-static int64_t qbits_kernel_workspace(int kernel, int64_t M, const PackedGeom& g, int dtype) {
-  switch (kernel) {
-    case QUANTO_HIP_KERNEL_SKINNY: return (int64_t)qbits_skinny_workspace(M, g, dtype);  // one plan: 0 when not served
-    case QUANTO_HIP_KERNEL_MFMA: return qbits_mfma_supported(M, g, dtype) ? (int64_t)qbits_mfma_workspace(M, g) : 0;
-    case QUANTO_HIP_KERNEL_DEQUANT_MFMA: return dequant_mfma_supported(M, g, dtype) ? (int64_t)dequant_mfma_workspace(g) : 0;
-    case QUANTO_HIP_KERNEL_MFMA_FUSED4: return qbits_mfma_fused_supported(M, g, dtype) ? (int64_t)qbits_mfma_fused_workspace(M, g) : 0;
-  }
-  return 0;
+// What a qbits_mm kernel is, one row per (kernel id, activations): the rule its launcher checks (nullptr: whatever check_qbits lets through), the
+// workspace of a served problem (nullptr: none), whether it writes that workspace from offset 0 - scratch over the split-K counter words - the
+// launcher, and the name quanto_hip_last_kernel reports.  f32 rows serve fp32 activations only and stand in front of their id's other row.
+struct QbitsRoute {
+  int id;
+  bool f32;
+  const char* name;
+  QbitsRule* supported;
+  QbitsWorkspace* workspace;
+  bool scratch_from_zero;
+  QbitsLaunch* launch;
+};
+static const QbitsRoute kQbitsRoutes[] = {
+    {QUANTO_HIP_KERNEL_NAIVE, false, "naive", nullptr, nullptr, false, qbits_mm_naive},
+    {QUANTO_HIP_KERNEL_GEMV, true, "gemv_f32", qbits_gemv_f32_supported, nullptr, false, qbits_mm_gemv_f32},
+    {QUANTO_HIP_KERNEL_GEMV, false, "gemv", qbits_gemv_supported, nullptr, false, qbits_mm_gemv},
+    {QUANTO_HIP_KERNEL_MFMA, true, "mfma_f32", qbits_mm_f32_supported, nullptr, false, qbits_mm_f32},  // MFMA tiles without a workspace
+    {QUANTO_HIP_KERNEL_MFMA, false, "mfma", qbits_mfma_supported, qbits_mfma_workspace, true, qbits_mm_mfma},
+    {QUANTO_HIP_KERNEL_DEQUANT_MFMA, false, "dequant_mfma", dequant_mfma_supported, dequant_mfma_workspace, true, qbits_mm_dequant_mfma},
+    {QUANTO_HIP_KERNEL_SKINNY, false, "skinny", qbits_skinny_supported, qbits_skinny_workspace, false, qbits_mm_skinny},
+    {QUANTO_HIP_KERNEL_MMV, false, "mmv", qbits_mmv_supported, nullptr, false, qbits_mm_mmv},
+    {QUANTO_HIP_KERNEL_MFMA_FUSED4, false, "mfma_fused4", qbits_mfma_fused_supported, qbits_mfma_fused_workspace, false, qbits_mm_mfma_fused},
+    {QUANTO_HIP_KERNEL_MFMA_LARGE4, false, "mfma_large4", qbits_mfma_large_supported, nullptr, false, qbits_mm_mfma_large},
+};
+
+// the row of a kernel id for these activations; nullptr: AUTO, or an id that is no kernel of the product
+template <class Route, size_t ROWS>
+static const Route* find_route(const Route (&routes)[ROWS], int kernel, bool f32) {
+  for (const Route& r : routes)
+    if (r.id == kernel && (f32 || !r.f32)) return &r;
+  return nullptr;
+}
+// Whether a FORCED kernel serves a problem, by the rule its launcher checks: the size and plan entries answer QUANTO_HIP_ENOTSUP for a shape beyond
+// that rule instead of a workspace size (QUANTO_HIP_EINVAL for an id that is no kernel); and the workspace the kernel needs (0: none, or not served).
+template <class Route, class... Problem>
+static int route_serves(const Route* r, int kernel, int64_t M, const Problem&... p) {
+  if (kernel == QUANTO_HIP_KERNEL_AUTO) return QUANTO_HIP_OK;
+  if (!r) return QUANTO_HIP_EINVAL;
+  return !r->supported || r->supported(p...) || M == 0 ? QUANTO_HIP_OK : QUANTO_HIP_ENOTSUP;
+}
+template <class Route, class... Problem>
+static int64_t route_workspace(const Route* r, const Problem&... p) {
+  return r && r->workspace && r->supported(p...) ? (int64_t)r->workspace(p...) : 0;
 }
 
-// Whether a FORCED kernel serves this qbits_mm problem, by the rule its launcher checks: the size and plan entries answer QUANTO_HIP_ENOTSUP
-// for a shape beyond that rule instead of a workspace size (QUANTO_HIP_EINVAL for an id that is no kernel).
+static const QbitsRoute* qbits_route(int kernel, int dtype) { return find_route(kQbitsRoutes, kernel, dtype == QUANTO_HIP_F32); }
 static int qbits_kernel_serves(int kernel, int64_t M, const PackedGeom& g, int dtype) {
-  const bool f32 = dtype == QUANTO_HIP_F32;
-  bool ok = false;
-  switch (kernel) {
-    case QUANTO_HIP_KERNEL_AUTO:
-    case QUANTO_HIP_KERNEL_NAIVE: ok = true; break;
-    case QUANTO_HIP_KERNEL_GEMV: ok = f32 ? qbits_gemv_f32_supported(M, g, dtype) : qbits_gemv_supported(M, g, dtype); break;
-    case QUANTO_HIP_KERNEL_MFMA: ok = f32 ? qbits_mm_f32_supported(M, g, dtype) : qbits_mfma_supported(M, g, dtype); break;
-    case QUANTO_HIP_KERNEL_DEQUANT_MFMA: ok = dequant_mfma_supported(M, g, dtype); break;
-    case QUANTO_HIP_KERNEL_SKINNY: ok = qbits_skinny_supported(M, g, dtype); break;
-    case QUANTO_HIP_KERNEL_MMV: ok = qbits_mmv_supported(M, g, dtype); break;
-    case QUANTO_HIP_KERNEL_MFMA_FUSED4: ok = qbits_mfma_fused_supported(M, g, dtype); break;
-    case QUANTO_HIP_KERNEL_MFMA_LARGE4: ok = qbits_mfma_large_supported(M, g, dtype); break;
-    default: return QUANTO_HIP_EINVAL;
-  }
-  return ok || M == 0 ? QUANTO_HIP_OK : QUANTO_HIP_ENOTSUP;
+  return route_serves(qbits_route(kernel, dtype), kernel, M, M, g, dtype);
 }
 
 // The kernel a qbits_mm call runs and the workspace it needs.  AUTO picks for a caller with (have_workspace) or without a workspace, then
@@ -246,11 +177,11 @@ static int qbits_kernel_serves(int kernel, int64_t M, const PackedGeom& g, int d
 static Plan plan_qbits(int64_t M, const PackedGeom& g, int dtype, int kernel, bool have_workspace, size_t workspace_bytes) {
   if (kernel == QUANTO_HIP_KERNEL_AUTO) {
     kernel = pick_qbits_kernel(M, g, dtype, have_workspace);
-    if (kernel == QUANTO_HIP_KERNEL_DEQUANT_MFMA && workspace_bytes < dequant_mfma_workspace(g))
+    if (kernel == QUANTO_HIP_KERNEL_DEQUANT_MFMA && workspace_bytes < dequant_mfma_workspace(M, g, dtype))
       kernel = qbits_mfma_supported(M, g, dtype) ? QUANTO_HIP_KERNEL_MFMA : QUANTO_HIP_KERNEL_NAIVE;
-    if (kernel == QUANTO_HIP_KERNEL_MFMA && dtype != QUANTO_HIP_F32 && workspace_bytes < qbits_mfma_workspace(M, g)) kernel = QUANTO_HIP_KERNEL_NAIVE;
+    if (kernel == QUANTO_HIP_KERNEL_MFMA && dtype != QUANTO_HIP_F32 && workspace_bytes < qbits_mfma_workspace(M, g, dtype)) kernel = QUANTO_HIP_KERNEL_NAIVE;
   }
-  return {kernel, qbits_kernel_workspace(kernel, M, g, dtype)};
+  return {kernel, route_workspace(qbits_route(kernel, dtype), M, g, dtype)};
 }
 
 // The LDS-DMA pipelined kernel (256x256 or 128x128 tiles, picked inside) whenever its 128-tiles can occupy a good part of
@@ -314,33 +245,35 @@ int quanto_hip_dequantize_qbits(const uint8_t* packed, const void* scale, const 
   return dequantize_qbits_dispatch(packed, scale, shift, out, g, dtype, int_shift, reinterpret_cast<hipStream_t>(stream));
 }
 
-int64_t quanto_hip_qbits_mm_workspace_size(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype, int kernel) {
+// the three query entries: the argument check, whether a forced kernel serves the problem, then the plan of a caller with any workspace
+static int query_qbits(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype, int kernel, Plan* p) {
   bool int_shift = false;
   const int st = check_qbits(M, N, K, bits, group_size, dtype, dtype, &int_shift);
   if (st != QUANTO_HIP_OK) return st;
   const PackedGeom g = make_geom(N, K, bits, group_size);
   const int serves = qbits_kernel_serves(kernel, M, g, dtype);
-  if (serves != QUANTO_HIP_OK) return serves;
-  return plan_qbits(M, g, dtype, kernel, true, SIZE_MAX).workspace;
+  if (serves == QUANTO_HIP_OK) *p = plan_qbits(M, g, dtype, kernel, true, SIZE_MAX);
+  return serves;
+}
+
+int64_t quanto_hip_qbits_mm_workspace_size(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype, int kernel) {
+  Plan p;
+  const int st = query_qbits(M, N, K, bits, group_size, dtype, kernel, &p);
+  return st != QUANTO_HIP_OK ? st : p.workspace;
 }
 
 int quanto_hip_qbits_mm_pick(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype) {
-  bool int_shift = false;
-  const int st = check_qbits(M, N, K, bits, group_size, dtype, dtype, &int_shift);
-  if (st != QUANTO_HIP_OK) return st;
-  return plan_qbits(M, make_geom(N, K, bits, group_size), dtype, QUANTO_HIP_KERNEL_AUTO, true, SIZE_MAX).kernel;
+  Plan p;
+  const int st = query_qbits(M, N, K, bits, group_size, dtype, QUANTO_HIP_KERNEL_AUTO, &p);
+  return st != QUANTO_HIP_OK ? st : p.kernel;
 }
 
 int quanto_hip_qbits_mm_plan(int64_t M, int64_t N, int64_t K, int bits, int group_size, int dtype, int kernel, int* kernel_out,
                              int64_t* workspace_bytes_out) {
   if (!kernel_out || !workspace_bytes_out) return QUANTO_HIP_EINVAL;
-  bool int_shift = false;
-  const int st = check_qbits(M, N, K, bits, group_size, dtype, dtype, &int_shift);
+  Plan p;
+  const int st = query_qbits(M, N, K, bits, group_size, dtype, kernel, &p);
   if (st != QUANTO_HIP_OK) return st;
-  const PackedGeom g = make_geom(N, K, bits, group_size);
-  const int serves = qbits_kernel_serves(kernel, M, g, dtype);
-  if (serves != QUANTO_HIP_OK) return serves;
-  const Plan p = plan_qbits(M, g, dtype, kernel, true, SIZE_MAX);
   *kernel_out = p.kernel;
   *workspace_bytes_out = p.workspace;
   return QUANTO_HIP_OK;
@@ -354,57 +287,15 @@ int quanto_hip_qbits_mm(const void* x, const uint8_t* packed, const void* scale,
   if (st != QUANTO_HIP_OK) return st;
   if (M == 0) return QUANTO_HIP_OK;
   if (!x || !packed || !scale || !shift || !y) return QUANTO_HIP_EINVAL;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const PackedGeom g = make_geom(N, K, bits, group_size);
+  const QbitsCall c{x, /*a_scale*/ nullptr, packed, scale, shift, bias, /*out_scale*/ nullptr, y, M, make_geom(N, K, bits, group_size), /*a_dtype*/ 0, dtype,
+                    int_shift, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream_)};
   // the fast kernels need 16-byte aligned x / packed (views into larger buffers may not be): AUTO then takes the kernel that copes
   if (kernel == QUANTO_HIP_KERNEL_AUTO && (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16)
     kernel = QUANTO_HIP_KERNEL_NAIVE;
-  kernel = plan_qbits(M, g, dtype, kernel, workspace != nullptr, workspace_bytes).kernel;
-  const bool f32 = dtype == QUANTO_HIP_F32;
-  int r = QUANTO_HIP_EINVAL;
-  const char* name = "";
-  switch (kernel) {
-    case QUANTO_HIP_KERNEL_NAIVE:
-      r = qbits_mm_naive(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-      name = "naive";
-      break;
-    case QUANTO_HIP_KERNEL_GEMV:
-      r = f32 ? qbits_mm_gemv_f32(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream)
-              : qbits_mm_gemv(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-      name = f32 ? "gemv_f32" : "gemv";
-      break;
-    case QUANTO_HIP_KERNEL_MFMA:  // fp32: MFMA tiles without a workspace
-      r = f32 ? qbits_mm_f32(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream)
-              : qbits_mm_mfma(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, workspace, workspace_bytes, stream);
-      name = f32 ? "mfma_f32" : "mfma";
-      break;
-    case QUANTO_HIP_KERNEL_DEQUANT_MFMA:
-      if (!dequant_mfma_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
-      if (!workspace || workspace_bytes < dequant_mfma_workspace(g)) return QUANTO_HIP_EINVAL;
-      r = dequantize_qbits_dispatch(packed, scale, shift, workspace, g, dtype, int_shift, stream);
-      if (r != QUANTO_HIP_OK) return r;
-      r = dense_mm_wd_supported(M, g.N, g.K, dtype) ? dense_mm_wd(x, workspace, bias, y, M, g.N, g.K, dtype, stream)
-                                                    : dense_mm_large(x, workspace, bias, y, M, g.N, g.K, dtype, stream);
-      name = "dequant_mfma";
-      break;
-    case QUANTO_HIP_KERNEL_SKINNY:
-      r = qbits_mm_skinny(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, workspace, workspace_bytes, stream);
-      name = "skinny";
-      break;
-    case QUANTO_HIP_KERNEL_MMV:
-      r = qbits_mm_mmv(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-      name = "mmv";
-      break;
-    case QUANTO_HIP_KERNEL_MFMA_FUSED4:
-      r = qbits_mm_mfma_fused(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, workspace, workspace_bytes, stream);
-      name = "mfma_fused4";
-      break;
-    case QUANTO_HIP_KERNEL_MFMA_LARGE4:
-      r = qbits_mm_mfma_large(x, packed, scale, shift, bias, y, M, g, dtype, int_shift, stream);
-      name = "mfma_large4";
-      break;
-  }
-  if (r == QUANTO_HIP_OK) set_last_kernel(name);
+  const QbitsRoute* route = qbits_route(plan_qbits(M, c.g, dtype, kernel, workspace != nullptr, workspace_bytes).kernel, dtype);
+  if (!route) return QUANTO_HIP_EINVAL;
+  const int r = route->launch(c);
+  if (r == QUANTO_HIP_OK) set_last_kernel(route->name);
   return r;
 }
 
@@ -432,8 +323,8 @@ static int qbits_mm_a8_entry(bool codes, const void* a, const void* a_scale, con
   if (codes && !qbits_a8_supported(M > 0 ? M : 1, g, a_dtype, dtype)) return QUANTO_HIP_ENOTSUP;
   if (M == 0) return QUANTO_HIP_OK;
   if (!a || !a_scale || !packed || !scale || !shift || !y || (codes && !out_scale)) return QUANTO_HIP_EINVAL;
-  const int r = qbits_mm_a8(a, a_scale, packed, scale, shift, bias, codes ? out_scale : nullptr, y, M, g, a_dtype, dtype, int_shift, workspace,
-                            workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  const int r = qbits_mm_a8(QbitsCall{a, a_scale, packed, scale, shift, bias, codes ? out_scale : nullptr, y, M, g, a_dtype, dtype, int_shift, workspace,
+                                      workspace_bytes, reinterpret_cast<hipStream_t>(stream)});
   if (r == QUANTO_HIP_OK) {
     static const char* const names[2][2][3] = {{{"a8_fused_int8", "a8_fused_fp8", "a8_fused_bf8"}, {"a8_fused_int8_w2", "a8_fused_fp8_w2", "a8_fused_bf8_w2"}},
                                                {{"a8_fused_int8_q", "a8_fused_fp8_q", "a8_fused_bf8_q"},
@@ -504,25 +395,26 @@ int quanto_hip_qbits_mm_multi_ws(const void* x, int count, const uint8_t* const*
   }
   if (M == 0) return QUANTO_HIP_OK;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const QbitsMultiCall c{x, count, packed, scale, shift, bias, y, N, M, K, dtype, int_shift, workspace, workspace_bytes, stream};
   if (one_launch) {
-    const int r = qbits_mm_gemv_multi(x, count, packed, scale, shift, bias, y, N, M, K, dtype, int_shift, stream);
+    const int r = qbits_mm_gemv_multi(c);
     if (r == QUANTO_HIP_OK) set_last_kernel("gemv_multi");
     if (r != QUANTO_HIP_EALIGN) return r;  // misaligned views: the separate calls below pick a kernel that copes
   } else if (skinny_multi_applies(count, N, M, K, bits, group_size, dtype)) {
-    const int r = qbits_mm_skinny_multi(x, count, packed, scale, shift, bias, y, N, M, K, dtype, int_shift, workspace, workspace_bytes, stream);
+    const int r = qbits_mm_skinny_multi(c);
     if (r == QUANTO_HIP_OK) set_last_kernel("skinny_multi");
     if (r != QUANTO_HIP_EALIGN) return r;
   }
-  // Separate calls that share ONE workspace.  The kernels that use it as scratch (dequantized weight, row sums) write from offset 0,
-  // i.e. over the counter words the split-K kernels expect to find zero: the counter region is zeroed again behind every such
+  // Separate calls that share ONE workspace.  The kernels that use it as scratch (dequantized weight, row sums: scratch_from_zero) write
+  // over the counter words the split-K kernels expect to find zero: the counter region is zeroed again behind every such
   // member, so that whichever member comes next (and the caller's next call) sees the "zero on entry" contract.
   for (int i = 0; i < count; ++i) {
     const PackedGeom g = make_geom(N[i], K, bits, group_size);
-    const int picked = workspace ? pick_qbits_kernel(M, g, dtype, true) : QUANTO_HIP_KERNEL_NAIVE;
+    const QbitsRoute* picked = workspace ? qbits_route(pick_qbits_kernel(M, g, dtype, true), dtype) : nullptr;
     const int r = quanto_hip_qbits_mm(x, packed[i], scale[i], shift[i], bias ? bias[i] : nullptr, y[i], M, N[i], K, bits, group_size, dtype,
                                       shift_dtype, QUANTO_HIP_KERNEL_AUTO, workspace, workspace_bytes, stream_);
     if (r != QUANTO_HIP_OK) return r;
-    if (workspace && (picked == QUANTO_HIP_KERNEL_DEQUANT_MFMA || picked == QUANTO_HIP_KERNEL_MFMA)) {
+    if (picked && picked->scratch_from_zero) {
       const size_t nz = workspace_bytes < (size_t)QUANTO_HIP_WS_COUNTER_BYTES ? workspace_bytes : (size_t)QUANTO_HIP_WS_COUNTER_BYTES;
       if (hipMemsetAsync(workspace, 0, nz, stream) != hipSuccess) return QUANTO_HIP_ELAUNCH;
     }
@@ -543,129 +435,100 @@ int quanto_hip_qbits_mm_multi(const void* x, int count, const uint8_t* const* pa
 //   enough 128-tiles to occupy the chip -> pipelined large-tile kernel (M = 256: 35 us vs 68 us streaming);
 //   M <= 256  streaming kernel in passes of 64 rows (few, long tiles: (256, 4096, 14336) 107 us vs 127 us tiled);
 //   else the large-tile kernel whenever it applies, the register-staged 128x128 kernel, the naive kernel.
-static int pick_qbytes_kernel(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  if (a_dtype == QUANTO_HIP_F32 && out_dtype == QUANTO_HIP_F32) {  // fp32 activations (r6, qmm_f32.hip)
-    if (qbytes_gemv_f32_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_KERNEL_GEMV;
-    if (qbytes_mm_f32_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_KERNEL_MFMA;
+static int pick_qbytes_kernel(const QbytesShape& s) {
+  const int64_t M = s.M, N = s.N, K = s.K;
+  if (s.a_dtype == QUANTO_HIP_F32 && s.out_dtype == QUANTO_HIP_F32) {  // fp32 activations (r6, qmm_f32.hip)
+    if (qbytes_gemv_f32_supported(s)) return QUANTO_HIP_KERNEL_GEMV;
+    if (qbytes_mm_f32_supported(s)) return QUANTO_HIP_KERNEL_MFMA;
     return QUANTO_HIP_KERNEL_NAIVE;
   }
-  if (M <= 2 && qbytes_gemv_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_KERNEL_GEMV;
-  if (qbytes_native8_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_KERNEL_NATIVE8;
-  const bool skinny = qbytes_skinny_supported(M, N, K, a_dtype, b_dtype, out_dtype);
-  const bool large = qbytes_mfma_large_supported(M, N, K, a_dtype, b_dtype, out_dtype);
+  if (M <= 2 && qbytes_gemv_supported(s)) return QUANTO_HIP_KERNEL_GEMV;
+  if (qbytes_native8_supported(s)) return QUANTO_HIP_KERNEL_NATIVE8;
+  const bool skinny = qbytes_skinny_supported(s);
+  const bool large = qbytes_mfma_large_supported(s);
   if (skinny && M <= 64) return QUANTO_HIP_KERNEL_SKINNY;
   if (large && prefer_large_tile(M, N, K)) return QUANTO_HIP_KERNEL_MFMA_LARGE;
   if (skinny) return QUANTO_HIP_KERNEL_SKINNY;
-  if (prefer_gemv(M) && qbytes_gemv_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_KERNEL_GEMV;
+  if (prefer_gemv(M) && qbytes_gemv_supported(s)) return QUANTO_HIP_KERNEL_GEMV;
   if (large) return QUANTO_HIP_KERNEL_MFMA_LARGE;
-  if (qbytes_mfma_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_KERNEL_MFMA;
+  if (qbytes_mfma_supported(s)) return QUANTO_HIP_KERNEL_MFMA;
   return QUANTO_HIP_KERNEL_NAIVE;
 }
 
-// qbits_kernel_serves for qbytes_mm
-static int qbytes_kernel_serves(int kernel, int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  const bool f32 = a_dtype == QUANTO_HIP_F32 && out_dtype == QUANTO_HIP_F32;
-  bool ok = false;
-  switch (kernel) {
-    case QUANTO_HIP_KERNEL_AUTO:
-    case QUANTO_HIP_KERNEL_NAIVE: ok = true; break;
-    case QUANTO_HIP_KERNEL_GEMV:
-      ok = f32 ? qbytes_gemv_f32_supported(M, N, K, a_dtype, b_dtype, out_dtype) : qbytes_gemv_supported(M, N, K, a_dtype, b_dtype, out_dtype);
-      break;
-    case QUANTO_HIP_KERNEL_MFMA:
-      ok = f32 ? qbytes_mm_f32_supported(M, N, K, a_dtype, b_dtype, out_dtype) : qbytes_mfma_supported(M, N, K, a_dtype, b_dtype, out_dtype);
-      break;
-    case QUANTO_HIP_KERNEL_SKINNY: ok = qbytes_skinny_supported(M, N, K, a_dtype, b_dtype, out_dtype); break;
-    case QUANTO_HIP_KERNEL_MFMA_LARGE: ok = qbytes_mfma_large_supported(M, N, K, a_dtype, b_dtype, out_dtype); break;
-    case QUANTO_HIP_KERNEL_NATIVE8: ok = qbytes_native8_supported(M, N, K, a_dtype, b_dtype, out_dtype); break;
-    default: return QUANTO_HIP_EINVAL;
-  }
-  return ok || M == 0 ? QUANTO_HIP_OK : QUANTO_HIP_ENOTSUP;
+// QbitsRoute for qbytes_mm; f32 rows: fp32 activations AND output.  (No kernel of this product uses its workspace as scratch.)
+struct QbytesRoute {
+  int id;
+  bool f32;
+  const char* name;
+  QbytesRule* supported;
+  QbytesWorkspace* workspace;
+  QbytesLaunch* launch;
+};
+static const QbytesRoute kQbytesRoutes[] = {
+    {QUANTO_HIP_KERNEL_NAIVE, false, "naive", nullptr, nullptr, qbytes_mm_naive},
+    {QUANTO_HIP_KERNEL_GEMV, true, "gemv_f32", qbytes_gemv_f32_supported, nullptr, qbytes_mm_gemv_f32},
+    {QUANTO_HIP_KERNEL_GEMV, false, "gemv", qbytes_gemv_supported, nullptr, qbytes_mm_gemv},
+    {QUANTO_HIP_KERNEL_MFMA, true, "mfma_f32", qbytes_mm_f32_supported, nullptr, qbytes_mm_f32},
+    {QUANTO_HIP_KERNEL_MFMA, false, "mfma", qbytes_mfma_supported, nullptr, qbytes_mm_mfma},
+    {QUANTO_HIP_KERNEL_SKINNY, false, "skinny", qbytes_skinny_supported, qbytes_skinny_workspace, qbytes_mm_skinny},
+    {QUANTO_HIP_KERNEL_MFMA_LARGE, false, "mfma_large", qbytes_mfma_large_supported, qbytes_mfma_large_workspace, qbytes_mm_mfma_large},
+    {QUANTO_HIP_KERNEL_NATIVE8, false, "mfma_native8", qbytes_native8_supported, qbytes_native8_workspace, qbytes_mm_native8},
+};
+static const QbytesRoute* qbytes_route(int kernel, const QbytesShape& s) {
+  return find_route(kQbytesRoutes, kernel, s.a_dtype == QUANTO_HIP_F32 && s.out_dtype == QUANTO_HIP_F32);
 }
 
 // The kernel a qbytes_mm call runs and the workspace it needs (the kernels that split K run unsplit without one)
-static Plan plan_qbytes(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel) {
-  if (kernel == QUANTO_HIP_KERNEL_AUTO) kernel = pick_qbytes_kernel(M, N, K, a_dtype, b_dtype, out_dtype);
-  int64_t ws = 0;
-  if (kernel == QUANTO_HIP_KERNEL_SKINNY)
-    ws = (int64_t)qbytes_skinny_workspace(M, N, K, a_dtype, b_dtype, out_dtype);  // one plan: 0 when not served
-  else if (kernel == QUANTO_HIP_KERNEL_MFMA_LARGE && qbytes_mfma_large_supported(M, N, K, a_dtype, b_dtype, out_dtype))
-    ws = (int64_t)qbytes_mfma_large_workspace(M, N, K);
-  else if (kernel == QUANTO_HIP_KERNEL_NATIVE8)
-    ws = (int64_t)qbytes_native8_workspace(M, N, K, a_dtype, b_dtype, out_dtype);
-  return {kernel, ws};
+static Plan plan_qbytes(const QbytesShape& s, int kernel) {
+  if (kernel == QUANTO_HIP_KERNEL_AUTO) kernel = pick_qbytes_kernel(s);
+  return {kernel, route_workspace(qbytes_route(kernel, s), s)};
 }
 
-static int check_qbytes(int64_t M, int64_t N, int64_t K, int out_dtype) {
-  if (M < 0 || N <= 0 || K <= 0) return QUANTO_HIP_EINVAL;
-  return is_float_dtype(out_dtype) ? QUANTO_HIP_OK : QUANTO_HIP_ENOTSUP;
+// sizes, the output dtype, then whether a forced kernel serves the problem (qbits_kernel_serves for qbytes_mm)
+static int check_qbytes(const QbytesShape& s, int kernel) {
+  if (s.M < 0 || s.N <= 0 || s.K <= 0) return QUANTO_HIP_EINVAL;
+  if (!is_float_dtype(s.out_dtype)) return QUANTO_HIP_ENOTSUP;
+  return route_serves(qbytes_route(kernel, s), kernel, s.M, s);
 }
 
 int quanto_hip_qbytes_mm_pick(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  const int st = check_qbytes(M, N, K, out_dtype);
-  return st != QUANTO_HIP_OK ? st : plan_qbytes(M, N, K, a_dtype, b_dtype, out_dtype, QUANTO_HIP_KERNEL_AUTO).kernel;
+  const QbytesShape s{M, N, K, a_dtype, b_dtype, out_dtype};
+  const int st = check_qbytes(s, QUANTO_HIP_KERNEL_AUTO);
+  return st != QUANTO_HIP_OK ? st : plan_qbytes(s, QUANTO_HIP_KERNEL_AUTO).kernel;
 }
 
 int64_t quanto_hip_qbytes_mm_workspace_size(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel) {
-  int st = check_qbytes(M, N, K, out_dtype);
-  if (st == QUANTO_HIP_OK) st = qbytes_kernel_serves(kernel, M, N, K, a_dtype, b_dtype, out_dtype);
-  return st != QUANTO_HIP_OK ? st : plan_qbytes(M, N, K, a_dtype, b_dtype, out_dtype, kernel).workspace;
+  const QbytesShape s{M, N, K, a_dtype, b_dtype, out_dtype};
+  const int st = check_qbytes(s, kernel);
+  return st != QUANTO_HIP_OK ? st : plan_qbytes(s, kernel).workspace;
 }
 
 int quanto_hip_qbytes_mm_plan(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype, int kernel, int* kernel_out,
                               int64_t* workspace_bytes_out) {
   if (!kernel_out || !workspace_bytes_out) return QUANTO_HIP_EINVAL;
-  int st = check_qbytes(M, N, K, out_dtype);
-  if (st == QUANTO_HIP_OK) st = qbytes_kernel_serves(kernel, M, N, K, a_dtype, b_dtype, out_dtype);
+  const QbytesShape s{M, N, K, a_dtype, b_dtype, out_dtype};
+  const int st = check_qbytes(s, kernel);
   if (st != QUANTO_HIP_OK) return st;
-  const Plan p = plan_qbytes(M, N, K, a_dtype, b_dtype, out_dtype, kernel);
+  const Plan p = plan_qbytes(s, kernel);
   *kernel_out = p.kernel;
   *workspace_bytes_out = p.workspace;
   return QUANTO_HIP_OK;
 }
 
 int quanto_hip_qbytes_mm_ws(const void* a, const void* b, const void* scales, const void* bias, void* y, int64_t M, int64_t N, int64_t K,
-                            int a_dtype, int b_dtype, int out_dtype, int kernel, void* workspace, size_t workspace_bytes, void* stream_) {
-  const int st = check_qbytes(M, N, K, out_dtype);
+                            int a_dtype, int b_dtype, int out_dtype, int kernel, void* workspace, size_t workspace_bytes, void* stream) {
+  const QbytesCall c{{M, N, K, a_dtype, b_dtype, out_dtype}, a, b, scales, bias, /*out_scale*/ nullptr, y, workspace, workspace_bytes,
+                     reinterpret_cast<hipStream_t>(stream)};
+  const int st = check_qbytes(c, QUANTO_HIP_KERNEL_AUTO);  // (a forced kernel that does not serve the call: its launcher refuses)
   if (st != QUANTO_HIP_OK) return st;
   if (M == 0) return QUANTO_HIP_OK;
   if (!a || !b || !scales || !y) return QUANTO_HIP_EINVAL;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   // misaligned views: AUTO takes the kernel that has no alignment requirement
   if (kernel == QUANTO_HIP_KERNEL_AUTO && (reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) % 16) kernel = QUANTO_HIP_KERNEL_NAIVE;
-  kernel = plan_qbytes(M, N, K, a_dtype, b_dtype, out_dtype, kernel).kernel;
-  const bool f32 = a_dtype == QUANTO_HIP_F32 && out_dtype == QUANTO_HIP_F32;
-  int r = QUANTO_HIP_EINVAL;
-  const char* name = "";
-  switch (kernel) {
-    case QUANTO_HIP_KERNEL_NAIVE:
-      r = qbytes_mm_naive(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream);
-      name = "naive";
-      break;
-    case QUANTO_HIP_KERNEL_GEMV:
-      r = f32 ? qbytes_mm_gemv_f32(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream)
-              : qbytes_mm_gemv(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream);
-      name = f32 ? "gemv_f32" : "gemv";
-      break;
-    case QUANTO_HIP_KERNEL_SKINNY:
-      r = qbytes_mm_skinny(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
-      name = "skinny";
-      break;
-    case QUANTO_HIP_KERNEL_MFMA:
-      r = f32 ? qbytes_mm_f32(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream)
-              : qbytes_mm_mfma(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, stream);
-      name = f32 ? "mfma_f32" : "mfma";
-      break;
-    case QUANTO_HIP_KERNEL_MFMA_LARGE:
-      r = qbytes_mm_mfma_large(a, b, scales, bias, y, M, N, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
-      name = "mfma_large";
-      break;
-    case QUANTO_HIP_KERNEL_NATIVE8:
-      r = qbytes_mm_native8(a, b, scales, bias, nullptr, y, M, N, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
-      name = "mfma_native8";
-      break;
-  }
-  if (r == QUANTO_HIP_OK) set_last_kernel(name);
+  const QbytesRoute* route = qbytes_route(plan_qbytes(c, kernel).kernel, c);
+  if (!route) return QUANTO_HIP_EINVAL;
+  const int r = route->launch(c);
+  if (r == QUANTO_HIP_OK) set_last_kernel(route->name);
   return r;
 }
 
@@ -676,8 +539,9 @@ static int qbytes_multi_kernel(int count, const int64_t* N, int64_t M, int64_t K
   if (count < 2) return QUANTO_HIP_KERNEL_AUTO;
   bool gemv = M >= 1 && M <= 2, lone_skinny = true;
   for (int i = 0; i < count; ++i) {
-    gemv = gemv && qbytes_gemv_supported(M, N[i], K, a_dtype, b_dtype, out_dtype);
-    lone_skinny = lone_skinny && pick_qbytes_kernel(M, N[i], K, a_dtype, b_dtype, out_dtype) == QUANTO_HIP_KERNEL_SKINNY;
+    const QbytesShape member{M, N[i], K, a_dtype, b_dtype, out_dtype};
+    gemv = gemv && qbytes_gemv_supported(member);
+    lone_skinny = lone_skinny && pick_qbytes_kernel(member) == QUANTO_HIP_KERNEL_SKINNY;
   }
   if (gemv) return QUANTO_HIP_KERNEL_GEMV;
   if (lone_skinny && M <= env_int("QUANTO_HIP_SKINNY_MULTI_MAX_M", 64) && qbytes_skinny_multi_supported(count, N, M, K, a_dtype, b_dtype, out_dtype))
@@ -703,14 +567,14 @@ int quanto_hip_qbytes_mm_multi_ws(const void* a, int count, const void* const* b
   for (int i = 0; i < count; ++i)
     if (N[i] <= 0 || (M > 0 && (!a || !b[i] || !scales[i] || !y[i]))) return QUANTO_HIP_EINVAL;
   if (M == 0) return QUANTO_HIP_OK;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const QbytesMultiCall c{a, count, b, scales, bias, y, N, M, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream_)};
   const int kernel = qbytes_multi_kernel(count, N, M, K, a_dtype, b_dtype, out_dtype);
   if (kernel == QUANTO_HIP_KERNEL_GEMV) {
-    const int r = qbytes_mm_gemv_multi(a, count, b, scales, bias, y, N, M, K, b_dtype, out_dtype, stream);
+    const int r = qbytes_mm_gemv_multi(c);
     if (r == QUANTO_HIP_OK) set_last_kernel("gemv_multi");
     if (r != QUANTO_HIP_EALIGN) return r;  // misaligned views: the separate calls below cope
   } else if (kernel == QUANTO_HIP_KERNEL_SKINNY) {
-    const int r = qbytes_mm_skinny_multi(a, count, b, scales, bias, y, N, M, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
+    const int r = qbytes_mm_skinny_multi(c);
     if (r == QUANTO_HIP_OK) set_last_kernel("skinny_multi");
     if (r != QUANTO_HIP_EALIGN) return r;
   }
@@ -729,34 +593,37 @@ int quanto_hip_qbytes_mm(const void* a, const void* b, const void* scales, const
 
 // ---- qbytes_mm with the layer's output quantization in the epilogue: one route (NATIVE8), everything else is the caller's two-op sequence ----
 // sizes -> EINVAL; then every reason not to serve -> ENOTSUP, ahead of any look at the data pointers
-static int check_qbytes_q(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int mid_dtype, int kernel) {
-  if (M < 0 || N <= 0 || K <= 0) return QUANTO_HIP_EINVAL;
+static int check_qbytes_q(const QbytesShape& s, int kernel) {  // s.out_dtype: the layer's float dtype (mid_dtype)
+  if (s.M < 0 || s.N <= 0 || s.K <= 0) return QUANTO_HIP_EINVAL;
   if (kernel < QUANTO_HIP_KERNEL_AUTO || kernel > QUANTO_HIP_KERNEL_MFMA_LARGE4) return QUANTO_HIP_EINVAL;
   if (kernel != QUANTO_HIP_KERNEL_AUTO && kernel != QUANTO_HIP_KERNEL_NATIVE8) return QUANTO_HIP_ENOTSUP;  // no other kernel stores codes
-  if (mid_dtype != QUANTO_HIP_BF16 && mid_dtype != QUANTO_HIP_F16) return QUANTO_HIP_ENOTSUP;              // fp32 layers (and non-float dtypes)
+  if (s.out_dtype != QUANTO_HIP_BF16 && s.out_dtype != QUANTO_HIP_F16) return QUANTO_HIP_ENOTSUP;          // fp32 layers (and non-float dtypes)
   // equal operand pairs, K a multiple of 64, operand sizes below 2^31 bytes: the rule of the unfused route
-  return qbytes_native8_supported(M > 0 ? M : 1, N, K, a_dtype, b_dtype, mid_dtype) ? QUANTO_HIP_OK : QUANTO_HIP_ENOTSUP;
+  QbytesShape rows = s;
+  if (rows.M == 0) rows.M = 1;
+  return qbytes_native8_supported(rows) ? QUANTO_HIP_OK : QUANTO_HIP_ENOTSUP;
 }
 
 int quanto_hip_qbytes_mm_q_plan(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int mid_dtype, int kernel, int* kernel_out,
                                 int64_t* workspace_bytes_out) {
   if (!kernel_out || !workspace_bytes_out) return QUANTO_HIP_EINVAL;
-  const int st = check_qbytes_q(M, N, K, a_dtype, b_dtype, mid_dtype, kernel);
+  const QbytesShape s{M, N, K, a_dtype, b_dtype, mid_dtype};
+  const int st = check_qbytes_q(s, kernel);
   if (st != QUANTO_HIP_OK) return st;
-  const Plan p = plan_qbytes(M, N, K, a_dtype, b_dtype, mid_dtype, QUANTO_HIP_KERNEL_NATIVE8);  // the planner of the unfused entry: same split, same scratch
+  const Plan p = plan_qbytes(s, QUANTO_HIP_KERNEL_NATIVE8);  // the planner of the unfused entry: same split, same scratch
   *kernel_out = p.kernel;
   *workspace_bytes_out = p.workspace;
   return QUANTO_HIP_OK;
 }
 
 int quanto_hip_qbytes_mm_q_ws(const void* a, const void* b, const void* scales, const void* bias, const void* out_scale, void* yq, int64_t M, int64_t N,
-                              int64_t K, int a_dtype, int b_dtype, int mid_dtype, int kernel, void* workspace, size_t workspace_bytes, void* stream_) {
-  const int st = check_qbytes_q(M, N, K, a_dtype, b_dtype, mid_dtype, kernel);
+                              int64_t K, int a_dtype, int b_dtype, int mid_dtype, int kernel, void* workspace, size_t workspace_bytes, void* stream) {
+  const QbytesCall c{{M, N, K, a_dtype, b_dtype, mid_dtype}, a, b, scales, bias, out_scale, yq, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream)};
+  const int st = check_qbytes_q(c, kernel);
   if (st != QUANTO_HIP_OK) return st;
   if (M == 0) return QUANTO_HIP_OK;
   if (!a || !b || !scales || !out_scale || !yq) return QUANTO_HIP_EINVAL;
-  const int r = qbytes_mm_native8(a, b, scales, bias, out_scale, yq, M, N, K, a_dtype, b_dtype, mid_dtype, workspace, workspace_bytes,
-                                  reinterpret_cast<hipStream_t>(stream_));
+  const int r = qbytes_mm_native8(c);
   if (r == QUANTO_HIP_OK) set_last_kernel("mfma_native8_q");
   return r;
 }
@@ -842,6 +709,14 @@ int64_t quanto_hip_qbits_conv2d_workspace_size_geom(int64_t B, int64_t cin, int6
   return split + (qbits_conv2d_takes_rows(g) ? (int64_t)conv2d_dense_weight_bytes(OC, K) : 0);
 }
 
+// what every convolution entry puts into its ConvCall; the operands (and int4 / int2: wg, int_shift) are the entry's to name
+static ConvCall conv_call(const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  ConvCall c{};
+  c.g = g, c.a_dtype = a_dtype, c.b_dtype = b_dtype, c.out_dtype = out_dtype;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = reinterpret_cast<hipStream_t>(stream);
+  return c;
+}
+
 // the one place where the ABI's positional geometry becomes a ConvGeom (*g, valid when QUANTO_HIP_OK comes back)
 static int check_conv2d_args(int64_t B, int64_t cin, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int stride_h,
                              int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, ConvGeom* g) {
@@ -863,7 +738,9 @@ int quanto_hip_qbytes_conv2d(const void* x, const void* w, const void* scales, c
   if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
   if (!x || !w || !scales || !y) return QUANTO_HIP_EINVAL;
   bool rows = false;
-  const int r = qbytes_conv2d_mfma(x, w, scales, bias, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), &rows);
+  ConvCall c = conv_call(g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
+  c.x = x, c.w = w, c.scale = scales, c.bias = bias, c.y = y;
+  const int r = qbytes_conv2d_mfma(c, &rows);
   if (r == QUANTO_HIP_OK) set_last_kernel(rows ? "conv2d_mfma_rows" : "conv2d_mfma");
   return r;
 }
@@ -895,8 +772,9 @@ static int qbytes_conv2d_a8_entry(bool codes, const void* x, const void* a_scale
   if (codes && !conv_geometry_ok(g)) return QUANTO_HIP_ENOTSUP;
   if (!x || !a_scale || !w || !w_scale || !y || (codes && !out_scale)) return QUANTO_HIP_EINVAL;
   int kind = -1;
-  const int r = qbytes_conv2d_a8(x, a_scale, w, w_scale, bias, codes ? out_scale : nullptr, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes,
-                                 reinterpret_cast<hipStream_t>(stream), &kind);
+  ConvCall c = conv_call(g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
+  c.x = x, c.a_scale = a_scale, c.w = w, c.scale = w_scale, c.bias = bias, c.out_scale = codes ? out_scale : nullptr, c.y = y;
+  const int r = qbytes_conv2d_a8(c, &kind);
   static const char* const names[2][3] = {{"conv2d_a8_int8", "conv2d_a8_fp8", "conv2d_a8_fp8_w8"}, {"conv2d_a8_int8_q", "conv2d_a8_fp8_q", "conv2d_a8_fp8_w8_q"}};
   if (r == QUANTO_HIP_OK) set_last_kernel(names[codes][kind]);
   return r;
@@ -929,7 +807,9 @@ int quanto_hip_qbytes_conv2d_depthwise(const void* x, const void* w, const void*
   if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
   if (!x || !w || !scales || !y) return QUANTO_HIP_EINVAL;
   bool strip = false;  // 16-byte row chunks; otherwise quads
-  const int r = qbytes_conv2d_depthwise(x, w, scales, bias, y, g, a_dtype, b_dtype, out_dtype, reinterpret_cast<hipStream_t>(stream), &strip);
+  ConvCall c = conv_call(g, a_dtype, b_dtype, out_dtype, nullptr, 0, stream);
+  c.x = x, c.w = w, c.scale = scales, c.bias = bias, c.y = y;
+  const int r = qbytes_conv2d_depthwise(c, &strip);
   if (r == QUANTO_HIP_OK) set_last_kernel(strip ? "conv2d_depthwise_strip" : "conv2d_depthwise");
   return r;
 }
@@ -947,22 +827,26 @@ int quanto_hip_qbits_conv2d(const void* x, const uint8_t* packed, const void* sc
   if (st != QUANTO_HIP_OK) return st;
   if (B == 0 || OH == 0 || OW == 0) return QUANTO_HIP_OK;
   if (!x || !packed || !scale || !shift || !y) return QUANTO_HIP_EINVAL;
-  const PackedGeom g = make_geom(OC, K, bits, group_size);
-  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+  ConvCall c = conv_call(cg, dtype, 0, dtype, workspace, workspace_bytes, stream);
+  c.x = x, c.w = packed, c.scale = scale, c.shift = shift, c.bias = bias, c.y = y;
+  c.wg = make_geom(OC, K, bits, group_size), c.int_shift = int_shift;
   const size_t dense = conv2d_dense_weight_bytes(OC, K);
   if (qbits_conv2d_takes_rows(cg) && workspace &&
       workspace_bytes >= dense && reinterpret_cast<uintptr_t>(workspace) % 16 == 0 && is_float_dtype(dtype) && dtype != QUANTO_HIP_F32) {
     // three-tap-wide windows at stride 1: dequantize once (the reference's own dense weight), then the row form of the convolution on it
-    int r = dequantize_qbits_dispatch(packed, scale, shift, workspace, g, dtype, int_shift, hs);
-    if (r == QUANTO_HIP_OK)
-      r = qdense_conv2d_rows(x, workspace, bias, y, cg, dtype, reinterpret_cast<uint8_t*>(workspace) + dense, workspace_bytes - dense, hs);
+    int r = dequantize_qbits_dispatch(packed, scale, shift, workspace, c.wg, dtype, int_shift, c.stream);
+    if (r == QUANTO_HIP_OK) {
+      ConvCall rows = conv_call(cg, dtype, dtype, dtype, reinterpret_cast<uint8_t*>(workspace) + dense, workspace_bytes - dense, stream);
+      rows.x = x, rows.w = workspace, rows.bias = bias, rows.y = y;
+      r = qdense_conv2d_rows(rows);
+    }
     if (r == QUANTO_HIP_OK) {
       set_last_kernel(bits == 4 ? "conv2d_rows_dequant_int4" : "conv2d_rows_dequant_int2");
       return r;
     }
     if (r != QUANTO_HIP_ENOTSUP) return r;
   }
-  const int r = qbits_conv2d_mfma(x, packed, scale, shift, bias, y, cg, g, dtype, int_shift, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  const int r = qbits_conv2d_mfma(c);
   if (r == QUANTO_HIP_OK) set_last_kernel(bits == 4 ? "conv2d_mfma_int4" : "conv2d_mfma_int2");
   return r;
 }

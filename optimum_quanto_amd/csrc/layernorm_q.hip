@@ -22,6 +22,7 @@
 // last unit of a row is always read element by element up to the row's last one, a unit behind the end not at all.  Codes leave as one 8-byte store per
 // unit, two 4-byte stores, or bytes - by the alignment of yq and n, chosen on the host; the ragged unit stores a dword while four codes remain, then
 // bytes.  No load or store touches a byte outside its row.  No atomics, no workspace, no MFMA.
+#include "qh_kernels.h"
 #include "qh_quantize.h"
 
 namespace qh {

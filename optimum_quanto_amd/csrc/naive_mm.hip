@@ -1,7 +1,7 @@
 // Shape-agnostic correctness kernels: one thread per output element, fp32 accumulation over K.
 // Used for shapes the fast kernels reject (odd K, int2, fp32 activations, e4m3fnuz, ...), and as the
 // on-device cross-check in the parity tests.  Not a performance path.
-#include "qh_common.h"
+#include "qh_kernels.h"
 
 namespace qh {
 
@@ -151,12 +151,11 @@ static int qbytes_naive_a(const void* a, const void* b, const void* s, const voi
   return QUANTO_HIP_ENOTSUP;
 }
 
-int qbytes_mm_naive(const void* a, const void* b, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
-                    int b_dtype, int out_dtype, hipStream_t stream) {
-  switch (out_dtype) {
-    case QUANTO_HIP_F32: return qbytes_naive_a<QUANTO_HIP_F32>(a, b, s, bias, y, M, N, K, a_dtype, b_dtype, stream);
-    case QUANTO_HIP_F16: return qbytes_naive_a<QUANTO_HIP_F16>(a, b, s, bias, y, M, N, K, a_dtype, b_dtype, stream);
-    case QUANTO_HIP_BF16: return qbytes_naive_a<QUANTO_HIP_BF16>(a, b, s, bias, y, M, N, K, a_dtype, b_dtype, stream);
+int qbytes_mm_naive(const QbytesCall& c) {
+  switch (c.out_dtype) {
+    case QUANTO_HIP_F32: return qbytes_naive_a<QUANTO_HIP_F32>(c.a, c.b, c.scales, c.bias, c.y, c.M, c.N, c.K, c.a_dtype, c.b_dtype, c.stream);
+    case QUANTO_HIP_F16: return qbytes_naive_a<QUANTO_HIP_F16>(c.a, c.b, c.scales, c.bias, c.y, c.M, c.N, c.K, c.a_dtype, c.b_dtype, c.stream);
+    case QUANTO_HIP_BF16: return qbytes_naive_a<QUANTO_HIP_BF16>(c.a, c.b, c.scales, c.bias, c.y, c.M, c.N, c.K, c.a_dtype, c.b_dtype, c.stream);
   }
   return QUANTO_HIP_ENOTSUP;
 }
@@ -181,12 +180,11 @@ static int qbits_naive_dt(const void* x, const uint8_t* packed, const void* scal
                    : qbits_naive_launch<DT, 2, false>(x, packed, scale, shift, bias, y, M, g, stream);
 }
 
-int qbits_mm_naive(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                   const PackedGeom& g, int dtype, bool int_shift, hipStream_t stream) {
-  switch (dtype) {
-    case QUANTO_HIP_F32: return qbits_naive_dt<QUANTO_HIP_F32>(x, packed, scale, shift, bias, y, M, g, int_shift, stream);
-    case QUANTO_HIP_F16: return qbits_naive_dt<QUANTO_HIP_F16>(x, packed, scale, shift, bias, y, M, g, int_shift, stream);
-    case QUANTO_HIP_BF16: return qbits_naive_dt<QUANTO_HIP_BF16>(x, packed, scale, shift, bias, y, M, g, int_shift, stream);
+int qbits_mm_naive(const QbitsCall& c) {
+  switch (c.dtype) {
+    case QUANTO_HIP_F32: return qbits_naive_dt<QUANTO_HIP_F32>(c.x, c.packed, c.scale, c.shift, c.bias, c.y, c.M, c.g, c.int_shift, c.stream);
+    case QUANTO_HIP_F16: return qbits_naive_dt<QUANTO_HIP_F16>(c.x, c.packed, c.scale, c.shift, c.bias, c.y, c.M, c.g, c.int_shift, c.stream);
+    case QUANTO_HIP_BF16: return qbits_naive_dt<QUANTO_HIP_BF16>(c.x, c.packed, c.scale, c.shift, c.bias, c.y, c.M, c.g, c.int_shift, c.stream);
   }
   return QUANTO_HIP_ENOTSUP;
 }

@@ -27,6 +27,7 @@
 // stays e4m3, the activation operand (B) is read as bf8 (blgp = 1) in the product and in the all-ones group sum; an e5m2 value times an integer below 16 is
 // exact in fp32, as for e4m3.  Instantiated: {bf16, fp16} x {int8, e4m3, e5m2} x {float shift, zero-point} x {64, 128 tokens} x {int4, int2}, each
 // storing y or (QOUT) the codes of y at the layer's output scale.
+#include "qh_kernels.h"
 #include "qh_group_fused.h"
 
 namespace qh {
@@ -332,31 +333,26 @@ size_t qbits_a8_workspace(int64_t M, const PackedGeom& g) {
 
 // out_scale == nullptr: y = dtype[M, N]; otherwise the code-storing kernels: y = a_dtype[M, N] codes at the per-tensor scale out_scale[0], 16-byte aligned
 template <bool QOUT>
-static int mm_a8(const void* act, const void* act_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
-                 const void* out_scale, void* y, int64_t M, const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace,
-                 size_t workspace_bytes, hipStream_t stream) {
-  if (!qbits_a8_supported(M, g, a_dtype, dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(packed) | (QOUT ? reinterpret_cast<uintptr_t>(y) : 0)) % 16) return QUANTO_HIP_EALIGN;
+static int mm_a8(const QbitsCall& c) {
+  const int64_t M = c.M;
+  const PackedGeom& g = c.g;
+  if (!qbits_a8_supported(M, g, c.a_dtype, c.dtype)) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(c.x) | reinterpret_cast<uintptr_t>(c.packed) | (QOUT ? reinterpret_cast<uintptr_t>(c.y) : 0)) % 16) return QUANTO_HIP_EALIGN;
   const gf::Unit unit = a8::unit(g.bits);
   gf::Plan p = gf::make_plan(unit, M, g.N, (int)g.G);
-  if (!gf::settle_for_workspace(unit, p, M, g.N, (int)g.G, workspace, workspace_bytes)) return QUANTO_HIP_EINVAL;
-  const a8::Args a{reinterpret_cast<const uint8_t*>(act), act_scale, packed, scale, shift, bias, y, (int)M, (int)g.N, (int)g.K, (int)g.G, p.S,
-                   reinterpret_cast<int*>(workspace),
-                   p.S > 1 ? ws_partials(workspace) : nullptr,
+  if (!gf::settle_for_workspace(unit, p, M, g.N, (int)g.G, c.workspace, c.workspace_bytes)) return QUANTO_HIP_EINVAL;
+  const a8::Args a{reinterpret_cast<const uint8_t*>(c.x), c.a_scale, c.packed, c.scale, c.shift, c.bias, c.y, (int)M, (int)g.N, (int)g.K, (int)g.G, p.S,
+                   reinterpret_cast<int*>(c.workspace),
+                   p.S > 1 ? ws_partials(c.workspace) : nullptr,
                    env_int("QUANTO_HIP_A8_ABLATE", 0),
-                   out_scale};
-  return dtype == QUANTO_HIP_BF16 ? a8::launch_bits<QUANTO_HIP_BF16, QOUT>(a, g.bits, a_dtype, p.bm, int_shift, stream)
-                                  : a8::launch_bits<QUANTO_HIP_F16, QOUT>(a, g.bits, a_dtype, p.bm, int_shift, stream);
+                   c.out_scale};
+  return c.dtype == QUANTO_HIP_BF16 ? a8::launch_bits<QUANTO_HIP_BF16, QOUT>(a, g.bits, c.a_dtype, p.bm, c.int_shift, c.stream)
+                                    : a8::launch_bits<QUANTO_HIP_F16, QOUT>(a, g.bits, c.a_dtype, p.bm, c.int_shift, c.stream);
 }
 
-// y = dtype[M, N]; or, with an out_scale, the product with the output quantization of the layer in its epilogue (gf::epilogue_codes): y = a_dtype[M, N]
-// codes of the dtype-rounded product at the per-tensor scale out_scale[0] - bit-identical to quantize_symmetric of the float form.  Same gate, same
-// plan, same workspace.
-int qbits_mm_a8(const void* act, const void* act_scale, const uint8_t* packed, const void* scale, const void* shift, const void* bias,
-                const void* out_scale, void* y, int64_t M, const PackedGeom& g, int a_dtype, int dtype, bool int_shift, void* workspace,
-                size_t workspace_bytes, hipStream_t stream) {
-  if (!out_scale) return mm_a8<false>(act, act_scale, packed, scale, shift, bias, nullptr, y, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes, stream);
-  return mm_a8<true>(act, act_scale, packed, scale, shift, bias, out_scale, y, M, g, a_dtype, dtype, int_shift, workspace, workspace_bytes, stream);
-}
+// c.x = the activation codes (a_dtype) at a_scale.  y = dtype[M, N]; or, with an out_scale, the product with the output quantization of the layer in its
+// epilogue (gf::epilogue_codes): y = a_dtype[M, N] codes of the dtype-rounded product at the per-tensor scale out_scale[0] - bit-identical to
+// quantize_symmetric of the float form.  Same gate, same plan, same workspace.
+int qbits_mm_a8(const QbitsCall& c) { return !c.out_scale ? mm_a8<false>(c) : mm_a8<true>(c); }
 
 }  // namespace qh

@@ -24,7 +24,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "qh_common.h"
+#include "qh_kernels.h"
 
 namespace qh {
 
@@ -558,24 +558,22 @@ static int gemv_dispatch(const void* x, const GemvProblem& pb, int M, int K, int
   return int_shift ? gemv_launch_m<QUANTO_HIP_F16, true>(x, pb, M, K, stream) : gemv_launch_m<QUANTO_HIP_F16, false>(x, pb, M, K, stream);
 }
 
-int qbits_mm_gemv(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                  const PackedGeom& g, int dtype, bool int_shift, hipStream_t stream) {
-  if (!qbits_gemv_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
-  const void* w = packed;
-  const GemvProblem pb{gather_linears(x, 1, &w, &scale, &shift, &bias, &y, &g.N), g.C == g.K && g.C != 128 ? 0 : (int)g.C, g.bits};
+int qbits_mm_gemv(const QbitsCall& c) {
+  const PackedGeom& g = c.g;
+  if (!qbits_gemv_supported(c.M, g, c.dtype)) return QUANTO_HIP_ENOTSUP;
+  const void* w = c.packed;
+  const GemvProblem pb{gather_linears(c.x, 1, &w, &c.scale, &c.shift, &c.bias, &c.y, &g.N), g.C == g.K && g.C != 128 ? 0 : (int)g.C, g.bits};
   if (pb.l.align % 16) return QUANTO_HIP_EALIGN;
-  return gemv_dispatch(x, pb, (int)M, (int)g.K, dtype, int_shift, stream);
+  return gemv_dispatch(c.x, pb, (int)c.M, (int)g.K, c.dtype, c.int_shift, c.stream);
 }
 
 // nseg (2..QUANTO_HIP_MAX_MULTI) int4 g128 Linears with the same K applied to the same x in one launch per pass of rows.
 // The caller has checked qbits_gemv_supported for every segment.
-int qbits_mm_gemv_multi(const void* x, int nseg, const uint8_t* const* packed, const void* const* scale, const void* const* shift,
-                        const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, int dtype, bool int_shift,
-                        hipStream_t stream) {
-  if (nseg < 1 || nseg > MAX_SEGS) return QUANTO_HIP_EINVAL;
-  const GemvProblem pb{gather_linears(x, nseg, reinterpret_cast<const void* const*>(packed), scale, shift, bias, y, N), 128, 4};
+int qbits_mm_gemv_multi(const QbitsMultiCall& c) {
+  if (c.count < 1 || c.count > MAX_SEGS) return QUANTO_HIP_EINVAL;
+  const GemvProblem pb{gather_linears(c.x, c.count, reinterpret_cast<const void* const*>(c.packed), c.scale, c.shift, c.bias, c.y, c.N), 128, 4};
   if (pb.l.align % 16) return QUANTO_HIP_EALIGN;
-  return gemv_dispatch(x, pb, (int)M, (int)K, dtype, int_shift, stream);
+  return gemv_dispatch(c.x, pb, (int)c.M, (int)c.K, c.dtype, c.int_shift, c.stream);
 }
 
 }  // namespace qh

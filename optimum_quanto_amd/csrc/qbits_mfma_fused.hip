@@ -25,6 +25,7 @@
 // in front of the first tiles' DMA).  Split-K where the scale table does not fit (K = 14336 with 128-token tiles) and, with 64-token
 // tiles, to fill the chip: fp32 partial tiles through the workspace, write-through stores, arrival counter, the last workgroup adds
 // them in split order - the split-K tail of qh_mfma.h.  What this kernel has in common with qbits_a8_fused.hip is in qh_group_fused.h.
+#include "qh_kernels.h"
 #include "qh_group_fused.h"
 
 namespace qh {
@@ -342,23 +343,24 @@ bool qbits_mfma_fused_needs_workspace(const PackedGeom& g) {
   return gf::lds_bytes(fused4::kUnit, (int)g.G, 128) > kMaxLdsBytes && gf::lds_bytes(fused4::kUnit, (int)g.G, 64) > kMaxLdsBytes;
 }
 
-size_t qbits_mfma_fused_workspace(int64_t M, const PackedGeom& g) {
+size_t qbits_mfma_fused_workspace(int64_t M, const PackedGeom& g, int) {
   return gf::workspace_bytes(gf::make_plan(fused4::kUnit, M, g.N, (int)g.G), M, g.N);
 }
 
-int qbits_mm_mfma_fused(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                        const PackedGeom& g, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!qbits_mfma_fused_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
+int qbits_mm_mfma_fused(const QbitsCall& c) {
+  const int64_t M = c.M;
+  const PackedGeom& g = c.g;
+  if (!qbits_mfma_fused_supported(M, g, c.dtype)) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(c.x) | reinterpret_cast<uintptr_t>(c.packed)) % 16) return QUANTO_HIP_EALIGN;
   gf::Plan p = gf::make_plan(fused4::kUnit, M, g.N, (int)g.G);
-  if (!gf::settle_for_workspace(fused4::kUnit, p, M, g.N, (int)g.G, workspace, workspace_bytes)) return QUANTO_HIP_EINVAL;
+  if (!gf::settle_for_workspace(fused4::kUnit, p, M, g.N, (int)g.G, c.workspace, c.workspace_bytes)) return QUANTO_HIP_EINVAL;
   const int bm = p.bm, S = p.S;
-  fused4::Args a{x, packed, scale, shift, bias, y, (int)M, (int)g.N, (int)g.K, (int)g.G, S, reinterpret_cast<int*>(workspace),
-                 S > 1 ? ws_partials(workspace) : nullptr,
+  fused4::Args a{c.x, c.packed, c.scale, c.shift, c.bias, c.y, (int)M, (int)g.N, (int)g.K, (int)g.G, S, reinterpret_cast<int*>(c.workspace),
+                 S > 1 ? ws_partials(c.workspace) : nullptr,
                  env_int("QUANTO_HIP_FUSED4_ABLATE", 0)};
-  if (dtype == QUANTO_HIP_BF16)
-    return int_shift ? fused4::launch<QUANTO_HIP_BF16, true>(a, bm, stream) : fused4::launch<QUANTO_HIP_BF16, false>(a, bm, stream);
-  return int_shift ? fused4::launch<QUANTO_HIP_F16, true>(a, bm, stream) : fused4::launch<QUANTO_HIP_F16, false>(a, bm, stream);
+  if (c.dtype == QUANTO_HIP_BF16)
+    return c.int_shift ? fused4::launch<QUANTO_HIP_BF16, true>(a, bm, c.stream) : fused4::launch<QUANTO_HIP_BF16, false>(a, bm, c.stream);
+  return c.int_shift ? fused4::launch<QUANTO_HIP_F16, true>(a, bm, c.stream) : fused4::launch<QUANTO_HIP_F16, false>(a, bm, c.stream);
 }
 
 }  // namespace qh

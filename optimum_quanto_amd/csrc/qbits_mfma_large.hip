@@ -35,6 +35,7 @@
 // tile, as before, with a lane-dependent group index.  int4 only.
 #include <type_traits>
 
+#include "qh_kernels.h"
 #include "qmm_large_common.h"
 
 namespace qh {
@@ -424,14 +425,14 @@ bool qbits_mfma_large_supported(int64_t M, const PackedGeom& g, int dtype) {
          g.C % (l4::BK / 2) == 0 && M >= 1 && M * g.K < (1ll << 30) && g.N * g.K < (1ll << 32) && g.N * g.G < (1ll << 31) && g.N < (1 << 30) && M < (1 << 30);
 }
 
-int qbits_mm_mfma_large(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                        const PackedGeom& g, int dtype, bool int_shift, hipStream_t stream) {
-  if (!qbits_mfma_large_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(y)) % 16) return QUANTO_HIP_EALIGN;
-  l4::Args a{x, packed, scale, shift, bias, y, (int)M, (int)g.N, (int)g.K, (int)g.C, (int)g.G, 1};
-  if (dtype == QUANTO_HIP_BF16)
-    return int_shift ? l4::launch<QUANTO_HIP_BF16, true>(a, stream) : l4::launch<QUANTO_HIP_BF16, false>(a, stream);
-  return int_shift ? l4::launch<QUANTO_HIP_F16, true>(a, stream) : l4::launch<QUANTO_HIP_F16, false>(a, stream);
+int qbits_mm_mfma_large(const QbitsCall& c) {
+  const PackedGeom& g = c.g;
+  if (!qbits_mfma_large_supported(c.M, g, c.dtype)) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(c.x) | reinterpret_cast<uintptr_t>(c.packed) | reinterpret_cast<uintptr_t>(c.y)) % 16) return QUANTO_HIP_EALIGN;
+  l4::Args a{c.x, c.packed, c.scale, c.shift, c.bias, c.y, (int)c.M, (int)g.N, (int)g.K, (int)g.C, (int)g.G, 1};
+  if (c.dtype == QUANTO_HIP_BF16)
+    return c.int_shift ? l4::launch<QUANTO_HIP_BF16, true>(a, c.stream) : l4::launch<QUANTO_HIP_BF16, false>(a, c.stream);
+  return c.int_shift ? l4::launch<QUANTO_HIP_F16, true>(a, c.stream) : l4::launch<QUANTO_HIP_F16, false>(a, c.stream);
 }
 
 }  // namespace qh

@@ -17,6 +17,7 @@
 //   * the four waves' sums are added through LDS in wave order; no workspace, deterministic.
 // Cost: every block reads all of x (M x K x 2 bytes, L2 hits) for 16 FG features - the reason this is for M <= 32 only and
 // why FG grows with N.
+#include "qh_kernels.h"
 #include "qh_mfma.h"
 
 namespace qh {
@@ -290,14 +291,14 @@ bool qbits_mmv_supported(int64_t M, const PackedGeom& g, int dtype) {
          mmv::lds_bytes(2, 2, (int)g.G) <= kMaxLdsBytes;
 }
 
-int qbits_mm_mmv(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                 const PackedGeom& g, int dtype, bool int_shift, hipStream_t stream) {
-  if (!qbits_mmv_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
-  mmv::Args a{x, packed, scale, shift, bias, y, (int)M, (int)g.N, (int)g.K, (int)g.G};
-  if (dtype == QUANTO_HIP_BF16)
-    return int_shift ? mmv::launch_shape<QUANTO_HIP_BF16, true>(a, stream) : mmv::launch_shape<QUANTO_HIP_BF16, false>(a, stream);
-  return int_shift ? mmv::launch_shape<QUANTO_HIP_F16, true>(a, stream) : mmv::launch_shape<QUANTO_HIP_F16, false>(a, stream);
+int qbits_mm_mmv(const QbitsCall& c) {
+  const PackedGeom& g = c.g;
+  if (!qbits_mmv_supported(c.M, g, c.dtype)) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(c.x) | reinterpret_cast<uintptr_t>(c.packed)) % 16) return QUANTO_HIP_EALIGN;
+  mmv::Args a{c.x, c.packed, c.scale, c.shift, c.bias, c.y, (int)c.M, (int)g.N, (int)g.K, (int)g.G};
+  if (c.dtype == QUANTO_HIP_BF16)
+    return c.int_shift ? mmv::launch_shape<QUANTO_HIP_BF16, true>(a, c.stream) : mmv::launch_shape<QUANTO_HIP_BF16, false>(a, c.stream);
+  return c.int_shift ? mmv::launch_shape<QUANTO_HIP_F16, true>(a, c.stream) : mmv::launch_shape<QUANTO_HIP_F16, false>(a, c.stream);
 }
 
 }  // namespace qh

@@ -20,6 +20,7 @@
 // chunk ^ (row & 15).
 #include <cstdlib>
 
+#include "qh_kernels.h"
 #include "qh_mfma.h"
 
 namespace qh {
@@ -674,10 +675,10 @@ bool qbits_skinny_supported(int64_t M, const PackedGeom& g, int dtype) { return 
 // 0 as well when the shape is not served
 size_t qbits_skinny_workspace(int64_t M, const PackedGeom& g, int dtype) { return skinny::make_plan(M, g, dtype, false, SIZE_MAX).workspace; }
 
-int qbits_mm_skinny(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                    const PackedGeom& g, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  const void* w = packed;
-  return skinny::run(x, gather_linears(x, 1, &w, &scale, &shift, &bias, &y, &g.N), M, g, dtype, int_shift, workspace, workspace_bytes, stream);
+int qbits_mm_skinny(const QbitsCall& c) {
+  const void* w = c.packed;
+  return skinny::run(c.x, gather_linears(c.x, 1, &w, &c.scale, &c.shift, &c.bias, &c.y, &c.g.N), c.M, c.g, c.dtype, c.int_shift, c.workspace,
+                     c.workspace_bytes, c.stream);
 }
 
 // ---- several Linears with a shared input in one launch (5 <= M <= 64) --------------------------------------------------------
@@ -705,13 +706,11 @@ size_t qbits_skinny_multi_workspace(int nseg, const int64_t* N, int64_t M, int64
   return multi_geom(nseg, N, M, K, &g) ? skinny::make_plan(M, g, QUANTO_HIP_BF16, true, SIZE_MAX).workspace : 0;
 }
 
-int qbits_mm_skinny_multi(const void* x, int nseg, const uint8_t* const* packed, const void* const* scale, const void* const* shift,
-                          const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, int dtype, bool int_shift,
-                          void* workspace, size_t workspace_bytes, hipStream_t stream) {
+int qbits_mm_skinny_multi(const QbitsMultiCall& c) {
   PackedGeom g;
-  if (!multi_geom(nseg, N, M, K, &g)) return QUANTO_HIP_ENOTSUP;
-  return skinny::run(x, gather_linears(x, nseg, reinterpret_cast<const void* const*>(packed), scale, shift, bias, y, N), M, g, dtype, int_shift, workspace,
-                     workspace_bytes, stream);
+  if (!multi_geom(c.count, c.N, c.M, c.K, &g)) return QUANTO_HIP_ENOTSUP;
+  return skinny::run(c.x, gather_linears(c.x, c.count, reinterpret_cast<const void* const*>(c.packed), c.scale, c.shift, c.bias, c.y, c.N), c.M, g, c.dtype,
+                     c.int_shift, c.workspace, c.workspace_bytes, c.stream);
 }
 
 }  // namespace qh

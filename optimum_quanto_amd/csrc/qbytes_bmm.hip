@@ -31,7 +31,7 @@
 // profiles/r05_packed_fp32_op_sel_next_to_mfma.md.  No split-K, no workspace, no atomics.
 #include <type_traits>
 
-#include "qh_common.h"
+#include "qh_kernels.h"
 
 namespace qh {
 namespace bmm8 {

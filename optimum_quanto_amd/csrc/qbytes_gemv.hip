@@ -4,7 +4,7 @@
 // accumulated in fp32 (int8 -> fp32 by v_cvt_f32_i32 with SDWA byte select, fp8 -> fp32 by
 // v_cvt_pk_f32_fp8) and the per-channel scale is applied once in the epilogue:
 // y[m,n] = scale[n] * sum_k x[m,k] * q[n,k]   (library/qbytes_mm.py:25-33 without materialising scale*W).
-#include "qh_common.h"
+#include "qh_kernels.h"
 
 namespace qh {
 
@@ -190,27 +190,26 @@ static int gemv8_dispatch(const void* a, const Linears& l, int M, int K, int b_d
 #undef QH_CASE
 }
 
-bool qbytes_gemv_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
+bool qbytes_gemv_supported(const QbytesShape& s) {
+  const auto [M, N, K, a_dtype, b_dtype, out_dtype] = s;
   const bool bd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2 || b_dtype == QUANTO_HIP_F8_E4M3FNUZ;
   return bd && a_dtype == out_dtype && (out_dtype == QUANTO_HIP_BF16 || out_dtype == QUANTO_HIP_F16) && M >= 1 &&
          M <= QUANTO_HIP_GEMV_MAX_M && K % 16 == 0 && K <= 16384 && N < (1 << 30);
 }
 
-int qbytes_mm_gemv(const void* a, const void* b, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
-                   int b_dtype, int out_dtype, hipStream_t stream) {
-  if (!qbytes_gemv_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  const Linears l = gather_linears(a, 1, &b, &s, nullptr, &bias, &y, &N);
+int qbytes_mm_gemv(const QbytesCall& c) {
+  if (!qbytes_gemv_supported(c)) return QUANTO_HIP_ENOTSUP;
+  const Linears l = gather_linears(c.a, 1, &c.b, &c.scales, nullptr, &c.bias, &c.y, &c.N);
   if (l.align % 16) return QUANTO_HIP_EALIGN;
-  return gemv8_dispatch(a, l, (int)M, (int)K, b_dtype, out_dtype, stream);
+  return gemv8_dispatch(c.a, l, (int)c.M, (int)c.K, c.b_dtype, c.out_dtype, c.stream);
 }
 
 // up to QUANTO_HIP_MAX_MULTI weights that share the activation, ONE launch (every member must pass qbytes_gemv_supported)
-int qbytes_mm_gemv_multi(const void* a, int nseg, const void* const* b, const void* const* s, const void* const* bias, void* const* y,
-                         const int64_t* N, int64_t M, int64_t K, int b_dtype, int out_dtype, hipStream_t stream) {
-  if (nseg < 1 || nseg > MAX_SEGS8) return QUANTO_HIP_EINVAL;
-  const Linears l = gather_linears(a, nseg, b, s, nullptr, bias, y, N);
+int qbytes_mm_gemv_multi(const QbytesMultiCall& c) {
+  if (c.count < 1 || c.count > MAX_SEGS8) return QUANTO_HIP_EINVAL;
+  const Linears l = gather_linears(c.a, c.count, c.b, c.scales, nullptr, c.bias, c.y, c.N);
   if (l.align % 16) return QUANTO_HIP_EALIGN;
-  return gemv8_dispatch(a, l, (int)M, (int)K, b_dtype, out_dtype, stream);
+  return gemv8_dispatch(c.a, l, (int)c.M, (int)c.K, c.b_dtype, c.out_dtype, c.stream);
 }
 
 }  // namespace qh

@@ -14,6 +14,7 @@
 //     same split-K tail and workspace contract (zeroed arrival counters, system-coherent partial sums: qh_mfma.h).
 #include <cstdlib>
 
+#include "qh_kernels.h"
 #include "qh_mfma.h"
 
 namespace qh {
@@ -374,17 +375,15 @@ static int run(const void* x, const Linears& l, int64_t M, int64_t N, int64_t K,
 
 }  // namespace skinny8
 
-bool qbytes_skinny_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  return skinny8::plan_format(M, N, K, a_dtype, b_dtype, out_dtype, false).served;
-}
+bool qbytes_skinny_supported(const QbytesShape& s) { return skinny8::plan_format(s.M, s.N, s.K, s.a_dtype, s.b_dtype, s.out_dtype, false).served; }
 // 0 as well when the shape is not served
-size_t qbytes_skinny_workspace(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  return skinny8::make_plan(M, N, K, a_dtype, b_dtype, out_dtype, false, SIZE_MAX).workspace;
+size_t qbytes_skinny_workspace(const QbytesShape& s) {
+  return skinny8::make_plan(s.M, s.N, s.K, s.a_dtype, s.b_dtype, s.out_dtype, false, SIZE_MAX).workspace;
 }
 
-int qbytes_mm_skinny(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
-                     int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  return skinny8::run(x, gather_linears(x, 1, &w, &s, nullptr, &bias, &y, &N), M, N, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
+int qbytes_mm_skinny(const QbytesCall& c) {
+  return skinny8::run(c.a, gather_linears(c.a, 1, &c.b, &c.scales, nullptr, &c.bias, &c.y, &c.N), c.M, c.N, c.K, c.a_dtype, c.b_dtype, c.out_dtype,
+                      c.workspace, c.workspace_bytes, c.stream);
 }
 
 // ---- several Linears with a shared input in one launch (3 <= M <= 64), see qbits_skinny.hip ------------------------------------
@@ -409,12 +408,11 @@ size_t qbytes_skinny_multi_workspace(int nseg, const int64_t* N, int64_t M, int6
   return total > 0 ? skinny8::make_plan(M, total, K, QUANTO_HIP_BF16, QUANTO_HIP_I8, QUANTO_HIP_BF16, true, SIZE_MAX).workspace : 0;
 }
 
-int qbytes_mm_skinny_multi(const void* x, int nseg, const void* const* w, const void* const* s, const void* const* bias, void* const* y,
-                           const int64_t* N, int64_t M, int64_t K, int a_dtype, int b_dtype, int out_dtype, void* workspace,
-                           size_t workspace_bytes, hipStream_t stream) {
-  const int64_t total = multi_total(nseg, N, M);
+int qbytes_mm_skinny_multi(const QbytesMultiCall& c) {
+  const int64_t total = multi_total(c.count, c.N, c.M);
   if (total <= 0) return QUANTO_HIP_ENOTSUP;
-  return skinny8::run(x, gather_linears(x, nseg, w, s, nullptr, bias, y, N), M, total, K, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream);
+  return skinny8::run(c.a, gather_linears(c.a, c.count, c.b, c.scales, nullptr, c.bias, c.y, c.N), c.M, total, c.K, c.a_dtype, c.b_dtype, c.out_dtype,
+                      c.workspace, c.workspace_bytes, c.stream);
 }
 
 }  // namespace qh

@@ -392,20 +392,20 @@ size_t conv2d_a8_workspace(int64_t M, int64_t N, int64_t K) { return conv_split_
 // *kind: the conv8::Kind that ran.  The caller has validated the arguments and the format (qbytes_conv2d_a8_kind >= 0, conv_geometry_ok).
 // QOUT: `y` receives a_dtype codes at *out_scale (store_codes); plan, split and workspace do not look at the output.
 template <bool QOUT>
-static int conv2d_a8_run(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, const void* out_scale, void* y,
-                         const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
+static int conv2d_a8_run(const ConvCall& c, int* kind) {
   using namespace conv8;
-  const int k = qbytes_conv2d_a8_kind(a_dtype, b_dtype, out_dtype);
-  if (k < 0 || !conv_geometry_ok(g)) return QUANTO_HIP_ENOTSUP;
+  hipStream_t stream = c.stream;
+  const int k = qbytes_conv2d_a8_kind(c.a_dtype, c.b_dtype, c.out_dtype);
+  if (k < 0 || !conv_geometry_ok(c.g)) return QUANTO_HIP_ENOTSUP;
   Args a{};
-  a.x = reinterpret_cast<const uint8_t*>(x), a.a_scale = a_scale, a.w = reinterpret_cast<const uint8_t*>(w), a.w_scale = w_scale, a.bias = bias, a.y = y;
-  a.out_dtype = out_dtype;
-  a.out_scale = out_scale;
-  conv_set_geometry(a, g);
-  a.S = conv_plan_split<BK, BM, BN>(a.M, a.N, a.K, workspace, workspace_bytes);
-  a.partials = workspace;
+  a.x = reinterpret_cast<const uint8_t*>(c.x), a.a_scale = c.a_scale, a.w = reinterpret_cast<const uint8_t*>(c.w), a.w_scale = c.scale, a.bias = c.bias, a.y = c.y;
+  a.out_dtype = c.out_dtype;
+  a.out_scale = c.out_scale;
+  conv_set_geometry(a, c.g);
+  a.S = conv_plan_split<BK, BM, BN>(a.M, a.N, a.K, c.workspace, c.workspace_bytes);
+  a.partials = c.workspace;
   const int ntiles = (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;
-  const bool ae5 = a_dtype == QUANTO_HIP_F8_E5M2, be5 = b_dtype == QUANTO_HIP_F8_E5M2;
+  const bool ae5 = c.a_dtype == QUANTO_HIP_F8_E5M2, be5 = c.b_dtype == QUANTO_HIP_F8_E5M2;
   if (k == K_I8) {
     launch_w<K_I8, 0, 0, QOUT>(a, ntiles, mtiles, stream);
   } else if (k == K_F8) {
@@ -422,10 +422,6 @@ static int conv2d_a8_run(const void* x, const void* a_scale, const void* w, cons
 
 // out_scale == nullptr: y = out_dtype[B, OC, OH, OW]; otherwise the same convolution with the layer's output quantization in its epilogue: y = a_dtype
 // codes of the out_dtype-rounded output at *out_scale
-int qbytes_conv2d_a8(const void* x, const void* a_scale, const void* w, const void* w_scale, const void* bias, const void* out_scale, void* y,
-                     const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream, int* kind) {
-  if (!out_scale) return conv2d_a8_run<false>(x, a_scale, w, w_scale, bias, nullptr, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream, kind);
-  return conv2d_a8_run<true>(x, a_scale, w, w_scale, bias, out_scale, y, g, a_dtype, b_dtype, out_dtype, workspace, workspace_bytes, stream, kind);
-}
+int qbytes_conv2d_a8(const ConvCall& c, int* kind) { return !c.out_scale ? conv2d_a8_run<false>(c, kind) : conv2d_a8_run<true>(c, kind); }
 
 }  // namespace qh

@@ -264,7 +264,7 @@ static int launch(const Args& a, hipStream_t stream) {
 
 }  // namespace dw
 
-bool qbytes_conv2d_depthwise_supported(const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype) {
+static bool qbytes_conv2d_depthwise_supported(const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype) {
   const bool wd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2;
   const bool ad = (a_dtype == QUANTO_HIP_BF16 || a_dtype == QUANTO_HIP_F16) && out_dtype == a_dtype;
   if (!wd || !ad || g.B < 1 || g.cin < 1 || g.OC < g.cin || g.OC % g.cin != 0 || g.KH < 1 || g.KW < 1 || g.sh < 1 || g.sw < 1 || g.dh < 1 || g.dw < 1 ||
@@ -275,11 +275,13 @@ bool qbytes_conv2d_depthwise_supported(const ConvGeom& g, int a_dtype, int b_dty
 }
 
 // g.cin: the channels C of x (one group each)
-int qbytes_conv2d_depthwise(const void* x, const void* w, const void* scales, const void* bias, void* y, const ConvGeom& g, int a_dtype, int b_dtype,
-                            int out_dtype, hipStream_t stream, bool* strip) {
+int qbytes_conv2d_depthwise(const ConvCall& c, bool* strip) {
   *strip = false;
-  if (!qbytes_conv2d_depthwise_supported(g, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  const dw::Args a{x, reinterpret_cast<const uint8_t*>(w), scales, bias, y, (int)g.B, (int)g.cin, (int)g.H, (int)g.W, (int)g.OC, (int)(g.OC / g.cin), (int)g.KH,
+  const ConvGeom& g = c.g;
+  const int a_dtype = c.a_dtype, b_dtype = c.b_dtype;
+  hipStream_t stream = c.stream;
+  if (!qbytes_conv2d_depthwise_supported(g, a_dtype, b_dtype, c.out_dtype)) return QUANTO_HIP_ENOTSUP;
+  const dw::Args a{c.x, reinterpret_cast<const uint8_t*>(c.w), c.scale, c.bias, c.y, (int)g.B, (int)g.cin, (int)g.H, (int)g.W, (int)g.OC, (int)(g.OC / g.cin), (int)g.KH,
                    (int)g.KW, (int)g.OH, (int)g.OW, g.sh, g.sw, g.ph, g.pw, g.dh, g.dw, (int)((g.OW + dw::PX - 1) / dw::PX)};
 #define QH_DW(DT)                                                                                       \
   if (b_dtype == QUANTO_HIP_I8) return dw::launch<DT, QUANTO_HIP_I8>(a, stream);                         \

@@ -866,7 +866,7 @@ static Args make_args(const void* x, const void* w, const void* scale, const voi
 
 }  // namespace conv
 
-bool qbytes_conv2d_supported(const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype) {
+static bool qbytes_conv2d_supported(const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype) {
   const bool bd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2;
   return bd && a_dtype == out_dtype && (out_dtype == QUANTO_HIP_BF16 || out_dtype == QUANTO_HIP_F16) && conv_geometry_ok(g);
 }
@@ -880,25 +880,26 @@ size_t conv2d_workspace(int64_t M, int64_t N, int64_t K) { return conv_split_wor
 // what the reference does, as two launches, without im2col.  Workspace: [dense weight, 256-byte multiple | K-split partials].
 size_t conv2d_dense_weight_bytes(int64_t N, int64_t K) { return ((size_t)N * K * 2 + 255) / 256 * 256; }
 bool conv2d_rows_eligible(const ConvGeom& g) { return conv::rows_eligible(g) && g.KH * g.KW <= 31 && g.OC * g.K() < (1ll << 30); }
-int qdense_conv2d_rows(const void* x, const void* wdense, const void* bias, void* y, const ConvGeom& g, int dtype, void* workspace, size_t workspace_bytes,
-                       hipStream_t stream) {
-  if (!conv2d_rows_eligible(g) || !conv_geometry_ok(g) || (dtype != QUANTO_HIP_BF16 && dtype != QUANTO_HIP_F16)) return QUANTO_HIP_ENOTSUP;
+int qdense_conv2d_rows(const ConvCall& c) {
+  const int dtype = c.out_dtype;
+  if (!conv2d_rows_eligible(c.g) || !conv_geometry_ok(c.g) || (dtype != QUANTO_HIP_BF16 && dtype != QUANTO_HIP_F16)) return QUANTO_HIP_ENOTSUP;
   using namespace conv;
-  Args a = make_args(x, wdense, nullptr, nullptr, bias, y, 0, 0, g);
-  a.S = conv_plan_split<BK, BM, BN>(a.M, a.N, a.K, workspace, workspace_bytes);
-  a.partials = reinterpret_cast<float*>(workspace);
+  Args a = make_args(c.x, c.w, nullptr, nullptr, c.bias, c.y, 0, 0, c.g);
+  a.S = conv_plan_split<BK, BM, BN>(a.M, a.N, a.K, c.workspace, c.workspace_bytes);
+  a.partials = reinterpret_cast<float*>(c.workspace);
   const int ntiles = (a.N + BN - 1) / BN, mtiles = (a.M + BM - 1) / BM;
-  return dtype == QUANTO_HIP_BF16 ? launch_rows<QUANTO_HIP_BF16, W_DENSE16>(a, ntiles, mtiles, stream) : launch_rows<QUANTO_HIP_F16, W_DENSE16>(a, ntiles, mtiles, stream);
+  return dtype == QUANTO_HIP_BF16 ? launch_rows<QUANTO_HIP_BF16, W_DENSE16>(a, ntiles, mtiles, c.stream)
+                                  : launch_rows<QUANTO_HIP_F16, W_DENSE16>(a, ntiles, mtiles, c.stream);
 }
 
-int qbytes_conv2d_mfma(const void* x, const void* w, const void* s, const void* bias, void* y, const ConvGeom& g, int a_dtype, int b_dtype, int out_dtype,
-                       void* workspace, size_t workspace_bytes, hipStream_t stream, bool* rows) {
+int qbytes_conv2d_mfma(const ConvCall& c, bool* rows) {
   *rows = false;
-  if (!qbytes_conv2d_supported(g, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
+  const int b_dtype = c.b_dtype;
+  if (!qbytes_conv2d_supported(c.g, c.a_dtype, b_dtype, c.out_dtype)) return QUANTO_HIP_ENOTSUP;
   using namespace conv;
-  const Args a = make_args(x, w, s, nullptr, bias, y, 0, 0, g);
-#define QH_CASE(DT, FMT) return launch<DT, FMT, false>(a, g, workspace, workspace_bytes, stream, rows)
-  if (out_dtype == QUANTO_HIP_BF16) {
+  const Args a = make_args(c.x, c.w, c.scale, nullptr, c.bias, c.y, 0, 0, c.g);
+#define QH_CASE(DT, FMT) return launch<DT, FMT, false>(a, c.g, c.workspace, c.workspace_bytes, c.stream, rows)
+  if (c.out_dtype == QUANTO_HIP_BF16) {
     if (b_dtype == QUANTO_HIP_I8) QH_CASE(QUANTO_HIP_BF16, W_I8);
     if (b_dtype == QUANTO_HIP_F8_E4M3FN) QH_CASE(QUANTO_HIP_BF16, W_F8E4M3);
     QH_CASE(QUANTO_HIP_BF16, W_F8E5M2);
@@ -911,17 +912,20 @@ int qbytes_conv2d_mfma(const void* x, const void* w, const void* s, const void* 
 
 // int4 / int2: group sizes that are multiples of 8 (a staging chunk of 8 k must not straddle groups) or per-channel scales; OC a multiple of the
 // values per byte (the planes of the generic packed layout)
-bool qbits_conv2d_supported(const ConvGeom& cg, const PackedGeom& g, int dtype) {
+static bool qbits_conv2d_supported(const ConvGeom& cg, const PackedGeom& g, int dtype) {
   return (g.bits == 4 || g.bits == 2) && g.N == cg.OC && g.K == cg.K() && cg.OC % g.vpi == 0 && (g.C % 8 == 0 || g.G == 1) &&
          (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && cg.OC * g.G < (1ll << 31) && conv_geometry_ok(cg);
 }
 
-int qbits_conv2d_mfma(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, const ConvGeom& cg,
-                      const PackedGeom& g, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+int qbits_conv2d_mfma(const ConvCall& c) {
+  const ConvGeom& cg = c.g;
+  const PackedGeom& g = c.wg;
+  const int dtype = c.out_dtype;
   if (!qbits_conv2d_supported(cg, g, dtype)) return QUANTO_HIP_ENOTSUP;
   using namespace conv;
-  const Args a = make_args(x, packed, scale, shift, bias, y, g.C, g.G, cg);
-#define QH_CASE(DT, FMT) return int_shift ? launch<DT, FMT, true>(a, cg, workspace, workspace_bytes, stream) : launch<DT, FMT, false>(a, cg, workspace, workspace_bytes, stream)
+  const Args a = make_args(c.x, c.w, c.scale, c.shift, c.bias, c.y, g.C, g.G, cg);
+#define QH_CASE(DT, FMT) \
+  return c.int_shift ? launch<DT, FMT, true>(a, cg, c.workspace, c.workspace_bytes, c.stream) : launch<DT, FMT, false>(a, cg, c.workspace, c.workspace_bytes, c.stream)
   if (g.bits == 4) {
     if (dtype == QUANTO_HIP_BF16) QH_CASE(QUANTO_HIP_BF16, W_I4R);
     QH_CASE(QUANTO_HIP_F16, W_I4R);

@@ -274,7 +274,4 @@ inline int fill_segments(int nseg, int (&first)[QUANTO_HIP_MAX_MULTI], Put put, 
   return total;
 }
 
-int launch_status();  // hipGetLastError() -> quanto_hip_status (defined in c_api.hip)
-void set_last_kernel(const char* name);
-
 }  // namespace qh

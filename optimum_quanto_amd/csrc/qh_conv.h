@@ -6,19 +6,12 @@
 #pragma once
 #include <type_traits>
 
-#include "qh_common.h"
+#include "qh_kernels.h"
 
 namespace qh {
 
 // ---- host: geometry ----------------------------------------------------------------------------------------------------------------------------
-// One conv2d call: x [B, cin, H, W], weight [OC, cin (depthwise: 1), KH, KW], y [B, OC, OH, OW]; filled once per C entry, behind check_conv2d_args.
-struct ConvGeom {
-  int64_t B, cin, H, W, OC, KH, KW, OH, OW;
-  int sh, sw, ph, pw, dh, dw;
-  int64_t M() const { return B * OH * OW; }    // GEMM rows: output pixels
-  int64_t K() const { return cin * KH * KW; }  // GEMM depth, in the weight's (c, i, j) order
-};
-
+// (ConvGeom, one conv2d call: qh_kernels.h)
 constexpr int kConvBM = 128;  // pixels per output tile, every implicit-GEMM kernel
 
 // What the implicit-GEMM kernels index: one validity bit per tap (two 64-bit mask words, one bit kept free), k and m below 2^24 (magic-number and

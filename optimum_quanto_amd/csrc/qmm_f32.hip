@@ -14,7 +14,7 @@
 //     the per-channel scale multiplies the fp32 accumulator (library/qbytes_mm.py:25-33 up to the order of one rounding).
 //
 // Reference call sites: tensor/function.py:41-47 (QuantizedLinearFunction), tensor/weights/qbytes.py:68-82, library/qbytes_mm.py:22-33.
-#include "qh_common.h"
+#include "qh_kernels.h"
 
 namespace qh {
 namespace f32k {
@@ -371,36 +371,36 @@ bool qbits_mm_f32_supported(int64_t M, const PackedGeom& g, int dtype) {
   return f32_qbits_common(M, g, dtype) && g.K % f32k::BK == 0 && grid_yz_fits(M, f32k::BM);  // grid.y = M tiles
 }
 
-int qbits_mm_gemv_f32(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                      const PackedGeom& g, int dtype, bool int_shift, hipStream_t stream) {
-  if (!qbits_gemv_f32_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
-  const f32k::Args a{reinterpret_cast<const float*>(x), packed, scale, shift, reinterpret_cast<const float*>(bias), reinterpret_cast<float*>(y),
-                     (int)M, (int)g.N, (int)g.K, (int)g.C, (int)g.G};
-  if (g.bits == 4) return int_shift ? f32k::launch_gemv<f32k::W_I4, true>(a, stream) : f32k::launch_gemv<f32k::W_I4, false>(a, stream);
-  return int_shift ? f32k::launch_gemv<f32k::W_I2, true>(a, stream) : f32k::launch_gemv<f32k::W_I2, false>(a, stream);
+static f32k::Args qbits_f32_args(const QbitsCall& c) {
+  return {reinterpret_cast<const float*>(c.x), c.packed, c.scale, c.shift, reinterpret_cast<const float*>(c.bias), reinterpret_cast<float*>(c.y),
+          (int)c.M, (int)c.g.N, (int)c.g.K, (int)c.g.C, (int)c.g.G};
 }
 
-int qbits_mm_f32(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M, const PackedGeom& g,
-                 int dtype, bool int_shift, hipStream_t stream) {
-  if (!qbits_mm_f32_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) % 16) return QUANTO_HIP_EALIGN;
-  const f32k::Args a{reinterpret_cast<const float*>(x), packed, scale, shift, reinterpret_cast<const float*>(bias), reinterpret_cast<float*>(y),
-                     (int)M, (int)g.N, (int)g.K, (int)g.C, (int)g.G};
-  if (g.bits == 4) return int_shift ? f32k::launch_mm<f32k::W_I4, true>(a, stream) : f32k::launch_mm<f32k::W_I4, false>(a, stream);
-  return int_shift ? f32k::launch_mm<f32k::W_I2, true>(a, stream) : f32k::launch_mm<f32k::W_I2, false>(a, stream);
+int qbits_mm_gemv_f32(const QbitsCall& c) {
+  if (!qbits_gemv_f32_supported(c.M, c.g, c.dtype)) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(c.x) | reinterpret_cast<uintptr_t>(c.packed)) % 16) return QUANTO_HIP_EALIGN;
+  const f32k::Args a = qbits_f32_args(c);
+  if (c.g.bits == 4) return c.int_shift ? f32k::launch_gemv<f32k::W_I4, true>(a, c.stream) : f32k::launch_gemv<f32k::W_I4, false>(a, c.stream);
+  return c.int_shift ? f32k::launch_gemv<f32k::W_I2, true>(a, c.stream) : f32k::launch_gemv<f32k::W_I2, false>(a, c.stream);
+}
+
+int qbits_mm_f32(const QbitsCall& c) {
+  if (!qbits_mm_f32_supported(c.M, c.g, c.dtype)) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(c.x) | reinterpret_cast<uintptr_t>(c.packed)) % 16) return QUANTO_HIP_EALIGN;
+  const f32k::Args a = qbits_f32_args(c);
+  if (c.g.bits == 4) return c.int_shift ? f32k::launch_mm<f32k::W_I4, true>(a, c.stream) : f32k::launch_mm<f32k::W_I4, false>(a, c.stream);
+  return c.int_shift ? f32k::launch_mm<f32k::W_I2, true>(a, c.stream) : f32k::launch_mm<f32k::W_I2, false>(a, c.stream);
 }
 
 // ---- qbytes_mm with fp32 activations ---------------------------------------------------------------------------------------------
-static bool f32_qbytes_common(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
+static bool f32_qbytes_common(const QbytesShape& s) {
+  const auto [M, N, K, a_dtype, b_dtype, out_dtype] = s;
   const bool bd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2 || b_dtype == QUANTO_HIP_F8_E4M3FNUZ;
   return bd && a_dtype == QUANTO_HIP_F32 && out_dtype == QUANTO_HIP_F32 && M >= 1 && M < (1 << 30) && N < (1 << 30) && K < (1 << 30);
 }
-bool qbytes_gemv_f32_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  return f32_qbytes_common(M, N, K, a_dtype, b_dtype, out_dtype) && K % 16 == 0 && M <= QUANTO_HIP_GEMV_F32_MAX_M;
-}
-bool qbytes_mm_f32_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  return f32_qbytes_common(M, N, K, a_dtype, b_dtype, out_dtype) && K % f32k::BK == 0 && grid_yz_fits(M, f32k::BM);  // grid.y = M tiles
+bool qbytes_gemv_f32_supported(const QbytesShape& s) { return f32_qbytes_common(s) && s.K % 16 == 0 && s.M <= QUANTO_HIP_GEMV_F32_MAX_M; }
+bool qbytes_mm_f32_supported(const QbytesShape& s) {
+  return f32_qbytes_common(s) && s.K % f32k::BK == 0 && grid_yz_fits(s.M, f32k::BM);  // grid.y = M tiles
 }
 
 template <bool GEMV>
@@ -413,22 +413,15 @@ static int qbytes_f32_dispatch(const f32k::Args& a, int b_dtype, hipStream_t str
 #undef QH_F32_CASE
 }
 
-int qbytes_mm_gemv_f32(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype,
-                       int out_dtype, hipStream_t stream) {
-  if (!qbytes_gemv_f32_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) % 16) return QUANTO_HIP_EALIGN;
-  const f32k::Args a{reinterpret_cast<const float*>(x), reinterpret_cast<const uint8_t*>(w), s, nullptr, reinterpret_cast<const float*>(bias),
-                     reinterpret_cast<float*>(y), (int)M, (int)N, (int)K, (int)K, 1};
-  return qbytes_f32_dispatch<true>(a, b_dtype, stream);
+template <bool GEMV>
+static int qbytes_f32_run(const QbytesCall& c) {
+  if (!(GEMV ? qbytes_gemv_f32_supported(c) : qbytes_mm_f32_supported(c))) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(c.a) | reinterpret_cast<uintptr_t>(c.b)) % 16) return QUANTO_HIP_EALIGN;
+  const f32k::Args a{reinterpret_cast<const float*>(c.a), reinterpret_cast<const uint8_t*>(c.b), c.scales, nullptr, reinterpret_cast<const float*>(c.bias),
+                     reinterpret_cast<float*>(c.y), (int)c.M, (int)c.N, (int)c.K, (int)c.K, 1};
+  return qbytes_f32_dispatch<GEMV>(a, c.b_dtype, c.stream);
 }
-
-int qbytes_mm_f32(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype,
-                  int out_dtype, hipStream_t stream) {
-  if (!qbytes_mm_f32_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) % 16) return QUANTO_HIP_EALIGN;
-  const f32k::Args a{reinterpret_cast<const float*>(x), reinterpret_cast<const uint8_t*>(w), s, nullptr, reinterpret_cast<const float*>(bias),
-                     reinterpret_cast<float*>(y), (int)M, (int)N, (int)K, (int)K, 1};
-  return qbytes_f32_dispatch<false>(a, b_dtype, stream);
-}
+int qbytes_mm_gemv_f32(const QbytesCall& c) { return qbytes_f32_run<true>(c); }
+int qbytes_mm_f32(const QbytesCall& c) { return qbytes_f32_run<false>(c); }
 
 }  // namespace qh

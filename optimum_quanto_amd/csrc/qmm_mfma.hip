@@ -15,6 +15,7 @@
 //     exact-math product of the reference's integers and scales up to fp32 accumulation order.
 // Weight tiles are read from HBM exactly once per (m-tile, n-tile); the dense dequantized weight the reference
 // materialises on every call (library/qbytes_mm.py:25-33, tensor/qbits.py:27-49) never exists.
+#include "qh_kernels.h"
 #include "qh_mfma.h"
 
 namespace qh {
@@ -265,15 +266,12 @@ __global__ void __launch_bounds__(256) group_sums_kernel(const typename Elem<DT>
   }
 }
 
-int qbits_group_sums(const void* x, float* xs, int M, int K, int C, int Mpad, int dtype, hipStream_t stream) {
+static void group_sums(const void* x, float* xs, int M, int K, int C, int Mpad, int dtype, hipStream_t stream) {  // dtype: BF16 or F16
   const dim3 grid((unsigned)((M + 3) / 4));
   if (dtype == QUANTO_HIP_BF16)
     hipLaunchKernelGGL(group_sums_kernel<QUANTO_HIP_BF16>, grid, dim3(256), 0, stream, reinterpret_cast<const __bf16*>(x), xs, M, K, C, Mpad);
-  else if (dtype == QUANTO_HIP_F16)
-    hipLaunchKernelGGL(group_sums_kernel<QUANTO_HIP_F16>, grid, dim3(256), 0, stream, reinterpret_cast<const _Float16*>(x), xs, M, K, C, Mpad);
   else
-    return QUANTO_HIP_ENOTSUP;
-  return launch_status();
+    hipLaunchKernelGGL(group_sums_kernel<QUANTO_HIP_F16>, grid, dim3(256), 0, stream, reinterpret_cast<const _Float16*>(x), xs, M, K, C, Mpad);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -292,19 +290,20 @@ static int mma_launch(const MmaArgs& a, hipStream_t stream) {
   return launch_status();
 }
 
-bool qbytes_mfma_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
+bool qbytes_mfma_supported(const QbytesShape& s) {
+  const auto [M, N, K, a_dtype, b_dtype, out_dtype] = s;
   const bool bd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2;
   return bd && a_dtype == out_dtype && (out_dtype == QUANTO_HIP_BF16 || out_dtype == QUANTO_HIP_F16) && M >= 1 && K % BK == 0 &&
          K >= BK && M < (1 << 30) && N < (1 << 30) && K < (1 << 30) && grid_yz_fits(M, BM);  // grid.y = M tiles
 }
 
-int qbytes_mm_mfma(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
-                   int b_dtype, int out_dtype, hipStream_t stream) {
-  if (!qbytes_mfma_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) % 16) return QUANTO_HIP_EALIGN;
-  MmaArgs a{x, reinterpret_cast<const uint8_t*>(w), s, nullptr, nullptr, bias, y, (int)M, (int)N, (int)K, 0, 0, 0};
-#define QH_CASE(DT, FMT) return mma_launch<DT, FMT, false>(a, stream)
-  if (out_dtype == QUANTO_HIP_BF16) {
+int qbytes_mm_mfma(const QbytesCall& c) {
+  if (!qbytes_mfma_supported(c)) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(c.a) | reinterpret_cast<uintptr_t>(c.b)) % 16) return QUANTO_HIP_EALIGN;
+  MmaArgs a{c.a, reinterpret_cast<const uint8_t*>(c.b), c.scales, nullptr, nullptr, c.bias, c.y, (int)c.M, (int)c.N, (int)c.K, 0, 0, 0};
+  const int b_dtype = c.b_dtype;
+#define QH_CASE(DT, FMT) return mma_launch<DT, FMT, false>(a, c.stream)
+  if (c.out_dtype == QUANTO_HIP_BF16) {
     if (b_dtype == QUANTO_HIP_I8) QH_CASE(QUANTO_HIP_BF16, W_I8);
     if (b_dtype == QUANTO_HIP_F8_E4M3FN) QH_CASE(QUANTO_HIP_BF16, W_F8E4M3);
     QH_CASE(QUANTO_HIP_BF16, W_F8E5M2);
@@ -320,28 +319,24 @@ bool qbits_mfma_supported(int64_t M, const PackedGeom& g, int dtype) {
          (dtype == QUANTO_HIP_BF16 || dtype == QUANTO_HIP_F16) && M < (1 << 30) && g.N < (1 << 30) && g.K < (1 << 30) && grid_yz_fits(M, BM);
 }
 
-size_t qbits_mfma_workspace(int64_t M, const PackedGeom& g) {
+size_t qbits_mfma_workspace(int64_t M, const PackedGeom& g, int) {
   const int64_t Mpad = (M + BM - 1) / BM * BM;
   return (size_t)g.G * Mpad * sizeof(float);
 }
 
-int qbits_mm_mfma(const void* x, const uint8_t* packed, const void* scale, const void* shift, const void* bias, void* y, int64_t M,
-                  const PackedGeom& g, int dtype, bool int_shift, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!qbits_mfma_supported(M, g, dtype)) return QUANTO_HIP_ENOTSUP;
-  if (workspace == nullptr || workspace_bytes < qbits_mfma_workspace(M, g)) return QUANTO_HIP_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(workspace)) % 16)
+int qbits_mm_mfma(const QbitsCall& c) {
+  const int64_t M = c.M;
+  const PackedGeom& g = c.g;
+  if (!qbits_mfma_supported(M, g, c.dtype)) return QUANTO_HIP_ENOTSUP;
+  if (c.workspace == nullptr || c.workspace_bytes < qbits_mfma_workspace(M, g, c.dtype)) return QUANTO_HIP_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(c.x) | reinterpret_cast<uintptr_t>(c.packed) | reinterpret_cast<uintptr_t>(c.workspace)) % 16)
     return QUANTO_HIP_EALIGN;
   const int Mpad = (int)((M + BM - 1) / BM * BM);
-  MmaArgs a{x, packed, scale, shift, reinterpret_cast<const float*>(workspace), bias, y, (int)M, (int)g.N, (int)g.K, (int)g.C, (int)g.G, Mpad};
-  const dim3 sgrid((unsigned)((M + 3) / 4));
-  if (dtype == QUANTO_HIP_BF16) {
-    hipLaunchKernelGGL(group_sums_kernel<QUANTO_HIP_BF16>, sgrid, dim3(256), 0, stream, reinterpret_cast<const __bf16*>(x),
-                       reinterpret_cast<float*>(workspace), a.M, a.K, a.C, Mpad);
-    return int_shift ? mma_launch<QUANTO_HIP_BF16, W_I4, true>(a, stream) : mma_launch<QUANTO_HIP_BF16, W_I4, false>(a, stream);
-  }
-  hipLaunchKernelGGL(group_sums_kernel<QUANTO_HIP_F16>, sgrid, dim3(256), 0, stream, reinterpret_cast<const _Float16*>(x),
-                     reinterpret_cast<float*>(workspace), a.M, a.K, a.C, Mpad);
-  return int_shift ? mma_launch<QUANTO_HIP_F16, W_I4, true>(a, stream) : mma_launch<QUANTO_HIP_F16, W_I4, false>(a, stream);
+  MmaArgs a{c.x, c.packed, c.scale, c.shift, reinterpret_cast<const float*>(c.workspace), c.bias, c.y, (int)M, (int)g.N, (int)g.K, (int)g.C, (int)g.G, Mpad};
+  group_sums(c.x, reinterpret_cast<float*>(c.workspace), a.M, a.K, a.C, Mpad, c.dtype, c.stream);
+  if (c.dtype == QUANTO_HIP_BF16)
+    return c.int_shift ? mma_launch<QUANTO_HIP_BF16, W_I4, true>(a, c.stream) : mma_launch<QUANTO_HIP_BF16, W_I4, false>(a, c.stream);
+  return c.int_shift ? mma_launch<QUANTO_HIP_F16, W_I4, true>(a, c.stream) : mma_launch<QUANTO_HIP_F16, W_I4, false>(a, c.stream);
 }
 
 }  // namespace qh

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "qh_kernels.h"
 #include "qmm_large_common.h"
 
 namespace qh {
@@ -534,7 +535,8 @@ static int launch(const Args& a, int cfg, hipStream_t stream) {
 
 }  // namespace lt
 
-bool qbytes_mfma_large_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
+bool qbytes_mfma_large_supported(const QbytesShape& s) {
+  const auto [M, N, K, a_dtype, b_dtype, out_dtype] = s;
   const bool bd = b_dtype == QUANTO_HIP_I8 || b_dtype == QUANTO_HIP_F8_E4M3FN || b_dtype == QUANTO_HIP_F8_E5M2 || b_dtype == QUANTO_HIP_F8_E4M3FNUZ;
   return bd && a_dtype == out_dtype && (out_dtype == QUANTO_HIP_BF16 || out_dtype == QUANTO_HIP_F16) && K % lt::BK == 0 &&
          K >= 2 * lt::BK && M >= 1 && M * K < (1ll << 30) && N * K < (1ll << 31) && M < (1 << 30) && N < (1 << 30);
@@ -558,10 +560,10 @@ static int large_split(int64_t M, int64_t N, int64_t K) {
   if (!ws_counters_fit(tiles128)) s = 1;  // one counter per 128-tile
   return s;
 }
-size_t qbytes_mfma_large_workspace(int64_t M, int64_t N, int64_t K) {
-  const int S = large_split(M, N, K);
+size_t qbytes_mfma_large_workspace(const QbytesShape& s) {
+  const int S = large_split(s.M, s.N, s.K);
   if (S == 1) return 0;
-  return QUANTO_HIP_WS_COUNTER_BYTES + (size_t)(((M + 127) / 128) * ((N + 127) / 128)) * S * (128 * 128 * 4);
+  return QUANTO_HIP_WS_COUNTER_BYTES + (size_t)(((s.M + 127) / 128) * ((s.N + 127) / 128)) * S * (128 * 128 * 4);
 }
 
 // Dense 16-bit GEMM y = x @ w^T (+ bias) on the weights-direct 128-tile loop, for grids that leave every workgroup a CU of its
@@ -582,11 +584,11 @@ int dense_mm_wd(const void* x, const void* w, const void* bias, void* y, int64_t
   return lt::launch_cfg<QUANTO_HIP_F16, lt::W_DENSE, 128, 128, 1, 4, 4>(a, stream);
 }
 
-int qbytes_mm_mfma_large(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int a_dtype,
-                      int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!qbytes_mfma_large_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return QUANTO_HIP_ENOTSUP;
+int qbytes_mm_mfma_large(const QbytesCall& c) {
+  if (!qbytes_mfma_large_supported(c)) return QUANTO_HIP_ENOTSUP;
+  const auto [M, N, K, a_dtype, b_dtype, out_dtype] = static_cast<const QbytesShape&>(c);
   int split = large_split(M, N, K);
-  if (split > 1 && !ws_holds(workspace, workspace_bytes, qbytes_mfma_large_workspace(M, N, K))) split = 1;
+  if (split > 1 && !ws_holds(c.workspace, c.workspace_bytes, qbytes_mfma_large_workspace(c))) split = 1;
   // 128-tiles as long as all of them are resident at once (two workgroups per CU: 512), 256-tiles beyond.  Measured,
   // bf16 x int8, K = 4096, us with 256-tiles -> 128-tiles: (512,14336) 87 -> 67, (1024,8192) 85 -> 70, (2048,4096) 79 -> 66;
   // but (1280,8192) 82 -> 99, (2048,8192) 107 -> 125
@@ -597,10 +599,10 @@ int qbytes_mm_mfma_large(const void* x, const void* w, const void* s, const void
   const int cfg256 = b_dtype == QUANTO_HIP_F8_E4M3FNUZ ? lt::CFG_256_1X8 : lt::CFG_256_8W;
   const int cfg = forced >= 0 ? forced : (tiles128 > 512 ? cfg256 : lt::CFG_128_4W);
   if (cfg != lt::CFG_128_4W) split = 1;  // the workspace is sized for 128-tiles
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) % 16) return QUANTO_HIP_EALIGN;
-  lt::Args a{x, reinterpret_cast<const uint8_t*>(w), s, bias, y, (int)M, (int)N, (int)K, 1, split, reinterpret_cast<int*>(workspace),
-             split > 1 ? ws_partials(workspace) : nullptr};
-#define QH_CASE(DT, FMT) return lt::launch<DT, FMT>(a, cfg, stream)
+  if ((reinterpret_cast<uintptr_t>(c.a) | reinterpret_cast<uintptr_t>(c.b)) % 16) return QUANTO_HIP_EALIGN;
+  lt::Args a{c.a, reinterpret_cast<const uint8_t*>(c.b), c.scales, c.bias, c.y, (int)M, (int)N, (int)K, 1, split, reinterpret_cast<int*>(c.workspace),
+             split > 1 ? ws_partials(c.workspace) : nullptr};
+#define QH_CASE(DT, FMT) return lt::launch<DT, FMT>(a, cfg, c.stream)
   if (out_dtype == QUANTO_HIP_BF16) {
     if (b_dtype == QUANTO_HIP_I8) QH_CASE(QUANTO_HIP_BF16, lt::W_I8);
     if (b_dtype == QUANTO_HIP_F8_E4M3FN) QH_CASE(QUANTO_HIP_BF16, lt::W_F8E4M3);

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "qh_kernels.h"
 #include "qmm_large_common.h"
 #include "qh_quantize.h"
 
@@ -926,7 +927,8 @@ int dense_mm_large(const void* x, const void* w, const void* bias, void* y, int6
   return n8::launch<QUANTO_HIP_F16, n8::K_F16>(args, nullptr, 0, stream);
 }
 
-bool qbytes_native8_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
+bool qbytes_native8_supported(const QbytesShape& s) {
+  const auto [M, N, K, a_dtype, b_dtype, out_dtype] = s;
   const bool pair = (a_dtype == QUANTO_HIP_I8 && b_dtype == QUANTO_HIP_I8) ||
                     (a_dtype == QUANTO_HIP_F8_E4M3FN && b_dtype == QUANTO_HIP_F8_E4M3FN) ||
                     (a_dtype == QUANTO_HIP_F8_E5M2 && b_dtype == QUANTO_HIP_F8_E5M2);
@@ -938,10 +940,11 @@ bool qbytes_native8_supported(int64_t M, int64_t N, int64_t K, int a_dtype, int 
 static int native8_kind(int a_dtype) { return a_dtype == QUANTO_HIP_I8 ? n8::K_I8 : a_dtype == QUANTO_HIP_F8_E4M3FN ? n8::K_F8E4M3 : n8::K_F8E5M2; }
 
 // split-K scratch for this problem: [QUANTO_HIP_WS_COUNTER_BYTES of arrival counters, zero on entry and on exit | partial accumulator tiles]; 0 = the plan does not split
-size_t qbytes_native8_workspace(int64_t M, int64_t N, int64_t K, int a_dtype, int b_dtype, int out_dtype) {
-  if (!qbytes_native8_supported(M, N, K, a_dtype, b_dtype, out_dtype)) return 0;
-  n8::Args args{{nullptr, nullptr, nullptr, nullptr, nullptr, (int)M, (int)N, (int)K, 1, 1, nullptr, nullptr}, 0};
-  switch (native8_kind(a_dtype)) {
+size_t qbytes_native8_workspace(const QbytesShape& s) {
+  if (!qbytes_native8_supported(s)) return 0;
+  const int64_t M = s.M, N = s.N;
+  n8::Args args{{nullptr, nullptr, nullptr, nullptr, nullptr, (int)M, (int)N, (int)s.K, 1, 1, nullptr, nullptr}, 0};
+  switch (native8_kind(s.a_dtype)) {
     case n8::K_I8: return n8::plan_workspace<n8::K_I8>(n8::make_plan<n8::K_I8>(args, true), M, N);
     case n8::K_F8E4M3: return n8::plan_workspace<n8::K_F8E4M3>(n8::make_plan<n8::K_F8E4M3>(args, true), M, N);
     default: return n8::plan_workspace<n8::K_F8E5M2>(n8::make_plan<n8::K_F8E5M2>(args, true), M, N);
@@ -952,16 +955,18 @@ size_t qbytes_native8_workspace(int64_t M, int64_t N, int64_t K, int a_dtype, in
 // y[M, N] = codes in a_dtype of the out_dtype-rounded product at the per-tensor scale out_scale[0], 16-byte aligned - bit-identical to quantize_symmetric
 // of the float form.  Serves what qbytes_native8_supported serves with a 16-bit out_dtype; plan, split and workspace are those of the float form (the
 // planner does not look at the output).
-int qbytes_mm_native8(const void* a, const void* b, const void* s, const void* bias, const void* out_scale, void* y, int64_t M, int64_t N, int64_t K,
-                      int a_dtype, int b_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  const bool codes = out_scale != nullptr;
-  if (!qbytes_native8_supported(M, N, K, a_dtype, b_dtype, out_dtype) || (codes && out_dtype == QUANTO_HIP_F32)) return QUANTO_HIP_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | (codes ? reinterpret_cast<uintptr_t>(y) : 0)) % 16) return QUANTO_HIP_EALIGN;
-  n8::Args args{{a, reinterpret_cast<const uint8_t*>(b), s, bias, y, (int)M, (int)N, (int)K, n8::raster_group(), 1, nullptr, nullptr}, 0, out_scale};
-#define QH_KIND(ODT, QOUT)                                                                                                    \
-  if (a_dtype == QUANTO_HIP_I8) return n8::launch<ODT, n8::K_I8, QOUT>(args, workspace, workspace_bytes, stream);             \
-  if (a_dtype == QUANTO_HIP_F8_E4M3FN) return n8::launch<ODT, n8::K_F8E4M3, QOUT>(args, workspace, workspace_bytes, stream);  \
-  return n8::launch<ODT, n8::K_F8E5M2, QOUT>(args, workspace, workspace_bytes, stream)
+int qbytes_mm_native8(const QbytesCall& c) {
+  const bool codes = c.out_scale != nullptr;
+  const int a_dtype = c.a_dtype, out_dtype = c.out_dtype;
+  if (!qbytes_native8_supported(c) || (codes && out_dtype == QUANTO_HIP_F32)) return QUANTO_HIP_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(c.a) | reinterpret_cast<uintptr_t>(c.b) | (codes ? reinterpret_cast<uintptr_t>(c.y) : 0)) % 16) return QUANTO_HIP_EALIGN;
+  n8::Args args{{c.a, reinterpret_cast<const uint8_t*>(c.b), c.scales, c.bias, c.y, (int)c.M, (int)c.N, (int)c.K, n8::raster_group(), 1, nullptr, nullptr},
+                0,
+                c.out_scale};
+#define QH_KIND(ODT, QOUT)                                                                                                          \
+  if (a_dtype == QUANTO_HIP_I8) return n8::launch<ODT, n8::K_I8, QOUT>(args, c.workspace, c.workspace_bytes, c.stream);             \
+  if (a_dtype == QUANTO_HIP_F8_E4M3FN) return n8::launch<ODT, n8::K_F8E4M3, QOUT>(args, c.workspace, c.workspace_bytes, c.stream);  \
+  return n8::launch<ODT, n8::K_F8E5M2, QOUT>(args, c.workspace, c.workspace_bytes, c.stream)
   if (!codes) {
     if (out_dtype == QUANTO_HIP_BF16) { QH_KIND(QUANTO_HIP_BF16, false); }
     if (out_dtype == QUANTO_HIP_F16) { QH_KIND(QUANTO_HIP_F16, false); }

@@ -8,6 +8,7 @@
 // to the tensor dtype T (what aten's div does through its opmath type); integer targets are then rounded half-to-even
 // *in T* (exact: |q| <= 256 after the clamp matters only) and clamped to [-128, 127]; float8 targets are clamped to the
 // finite range and converted with the hardware's round-to-nearest-even OCP converters (v_cvt_pk_fp8_f32 / bf8).
+#include "qh_kernels.h"
 #include "qh_quantize.h"  // clamp_target, pack4, quotient_in: shared with the code-storing GEMM epilogue (qmm_native8.hip)
 
 namespace qh {

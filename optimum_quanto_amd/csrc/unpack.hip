@@ -4,7 +4,7 @@
 // dwordx4 per bit-plane (unpack) or 16 dequantized elements per plane (dequantize).  The reference
 // HIP kernel (library/extensions/hip/unpack.cu:33-97) moves 1 byte per thread on the legacy
 // stream; this one is vectorised and runs on the caller's stream.
-#include "qh_common.h"
+#include "qh_kernels.h"
 
 namespace qh {
 

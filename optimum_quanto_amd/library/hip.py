@@ -900,7 +900,7 @@ class QuantoHipExtension(NativeLibrary):
             root_dir=csrc,
             lib_path=os.path.join(_PKG_DIR, "lib", "libquanto_hip.so"),
             sources=["c_api.hip", "unpack.hip", "naive_mm.hip", "qbits_gemv.hip", "qbytes_gemv.hip", "qmm_mfma.hip", "qconv_mfma.hip", "qconv_a8.hip", "qconv_depthwise.hip", "qmm_mfma_large.hip", "qmm_large_common.h", "qbits_skinny.hip", "qbits_mmv.hip", "qbits_mfma_fused.hip", "qbits_a8_fused.hip", "qbits_mfma_large.hip", "qbytes_skinny.hip", "qmm_native8.hip", "qmm_f32.hip", "quantize.hip", "qbytes_bmm.hip", "layernorm_q.hip",
-                     "qh_common.h", "qh_conv.h", "qh_group_fused.h", "qh_mfma.h", "qh_quantize.h", os.path.join("..", "..", "include", "quanto_hip.h")],
+                     "qh_common.h", "qh_conv.h", "qh_group_fused.h", "qh_kernels.h", "qh_mfma.h", "qh_quantize.h", os.path.join("..", "..", "include", "quanto_hip.h")],
         )
         self._bindings = None
 

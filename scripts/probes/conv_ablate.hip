@@ -21,9 +21,13 @@ int main() {
     hipMemcpy(x, hx.data(), hx.size() * 2, hipMemcpyHostToDevice); hipMemcpy(w, hw.data(), hw.size(), hipMemcpyHostToDevice);
     hipMemcpy(sc, hs.data(), s.OC * 2, hipMemcpyHostToDevice);
     auto run = [&]() {
-      const qh::ConvGeom g{s.B, s.C, s.H, s.H, s.OC, 3, 3, OH, OW, 1, 1, 1, 1, 1, 1};
+      qh::ConvCall c{};
+      c.g = qh::ConvGeom{s.B, s.C, s.H, s.H, s.OC, 3, 3, OH, OW, 1, 1, 1, 1, 1, 1};
+      c.x = x, c.w = w, c.scale = sc, c.y = y;
+      c.a_dtype = c.out_dtype = QUANTO_HIP_BF16, c.b_dtype = QUANTO_HIP_I8;
+      c.workspace = ws, c.workspace_bytes = ws_bytes;
       bool rows;
-      return qh::qbytes_conv2d_mfma(x, w, sc, nullptr, y, g, QUANTO_HIP_BF16, QUANTO_HIP_I8, QUANTO_HIP_BF16, ws, ws_bytes, 0, &rows);
+      return qh::qbytes_conv2d_mfma(c, &rows);
     };
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     int st = 0;

@@ -19,7 +19,10 @@ int main() {
       hipMemcpy(x, ha.data(), ha.size(), hipMemcpyHostToDevice); hipMemcpy(w, hw.data(), hw.size(), hipMemcpyHostToDevice);
       hipMemcpy(sc, hs.data(), N * 2, hipMemcpyHostToDevice);
       const int dt = fp8 ? QUANTO_HIP_F8_E4M3FN : QUANTO_HIP_I8;
-      auto run = [&]() { return qh::qbytes_mm_native8(x, w, sc, nullptr, y, M, N, K, dt, dt, QUANTO_HIP_BF16, nullptr, 0, 0); };  // no workspace: the unsplit plan
+      qh::QbytesCall c{};  // no out_scale: the float output; no workspace: the unsplit plan
+      c.M = M, c.N = N, c.K = K, c.a_dtype = c.b_dtype = dt, c.out_dtype = QUANTO_HIP_BF16;
+      c.a = x, c.b = w, c.scales = sc, c.y = y;
+      auto run = [&]() { return qh::qbytes_mm_native8(c); };
       hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
       int st = 0;
       for (int i = 0; i < 300; ++i) st |= run();

@@ -28,6 +28,7 @@
 // chunk ^ ((row >> 1) & 7), weights (64-byte rows, 4 chunks) chunk ^ ((row >> 2) & 3).
 #include <type_traits>
 
+#include "qh_kernels.h"
 #include "qmm_large_common.h"
 
 namespace qh {
@@ -326,12 +327,12 @@ static int launch(const Args& a, hipStream_t stream) {
 }  // namespace lt32
 
 // same argument contract as qbytes_mm_mfma_large (256-tile configuration, no split-K)
-int qbytes_mm_mfma_large32(const void* x, const void* w, const void* s, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int b_dtype,
-                           int out_dtype, hipStream_t stream) {
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) % 16) return QUANTO_HIP_EALIGN;
-  lt::Args a{x, reinterpret_cast<const uint8_t*>(w), s, bias, y, (int)M, (int)N, (int)K, 1, 1, nullptr, nullptr};
-#define QH_CASE(DT, FMT) return lt32::launch<DT, FMT>(a, stream)
-  if (out_dtype == QUANTO_HIP_BF16) {
+int qbytes_mm_mfma_large32(const QbytesCall& c) {
+  if ((reinterpret_cast<uintptr_t>(c.a) | reinterpret_cast<uintptr_t>(c.b)) % 16) return QUANTO_HIP_EALIGN;
+  lt::Args a{c.a, reinterpret_cast<const uint8_t*>(c.b), c.scales, c.bias, c.y, (int)c.M, (int)c.N, (int)c.K, 1, 1, nullptr, nullptr};
+  const int b_dtype = c.b_dtype;
+#define QH_CASE(DT, FMT) return lt32::launch<DT, FMT>(a, c.stream)
+  if (c.out_dtype == QUANTO_HIP_BF16) {
     if (b_dtype == QUANTO_HIP_I8) QH_CASE(QUANTO_HIP_BF16, lt::W_I8);
     if (b_dtype == QUANTO_HIP_F8_E4M3FN) QH_CASE(QUANTO_HIP_BF16, lt::W_F8E4M3);
     QH_CASE(QUANTO_HIP_BF16, lt::W_F8E5M2);
