@@ -60,10 +60,8 @@ __global__ void __launch_bounds__(256)
     } else {
       for (int64_t k = 0; k < K; ++k) acc = __builtin_fmaf(ALoad<ADT>::ld(a, m * K + k), decode8<BDT>(b[n * K + k]), acc);
     }
-    float r = acc * E::to_f32(scales[n]);
-    asm volatile("" : "+v"(r));  // keep the fp32 rounding of the product (no fused v_fma_mixlo_f16): reference rounds twice
-    if (bias) r = E::to_f32(E::from_f32(r)) + E::to_f32(bias[n]);  // output rounded, then bias added (tensor/weights/qbytes.py:79-81)
-    y[i] = E::from_f32(r);
+    const float sc = E::to_f32(scales[n]);
+    y[i] = bias ? scale_round_add_round<ODT>(acc, sc, true, E::to_f32(bias[n])) : scale_round_add_round<ODT>(acc, sc, false, 0.f);
   }
 }
 
@@ -102,8 +100,7 @@ __global__ void __launch_bounds__(256)
         acc += s * dot - z * xs;
       }
     }
-    if (bias) acc = E::to_f32(E::from_f32(acc)) + E::to_f32(bias[n]);
-    y[i] = E::from_f32(acc);
+    y[i] = bias ? round_add_round<DT>(acc, true, E::to_f32(bias[n])) : round_add_round<DT>(acc, false, 0.f);
   }
 }
 

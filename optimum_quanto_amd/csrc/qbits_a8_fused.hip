@@ -277,7 +277,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_a8_fused_kernel(const Arg
     const float os = E::to_f32(*reinterpret_cast<const T*>(a.out_scale));
     epilogue_codes<DT, ODT, MI>(acc, a.y, a.bias, sx, os, M, m0, fi, N, P, p0 + wave * RW + froff, fplane);
   } else {
-    QH_GF_EPILOGUE(E, MI, acc, a.y, a.bias, m0, fi, N, P, p0 + wave * RW + froff, fplane, m < M, v = v * sx; asm volatile("" : "+v"(v)));
+    QH_GF_EPILOGUE(DT, MI, acc, a.y, a.bias, m0, fi, N, P, p0 + wave * RW + froff, fplane, m < M, v = v * sx; asm volatile("" : "+v"(v)));
   }
 }
 

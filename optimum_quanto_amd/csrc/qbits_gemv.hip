@@ -386,8 +386,8 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
         for (int dr = 0; dr < 4; ++dr) v += red[wave + s][dr][lane];
       const int n = p + h * P;
-      if (bias) v = E::to_f32(E::from_f32(v)) + E::to_f32(__builtin_bit_cast(T, bias[n]));
-      y[(size_t)m * N + n] = __builtin_bit_cast(uint16_t, E::from_f32(v));
+      const T out = bias ? round_add_round<DT>(v, true, E::to_f32(__builtin_bit_cast(T, bias[n]))) : round_add_round<DT>(v, false, 0.f);
+      y[(size_t)m * N + n] = __builtin_bit_cast(uint16_t, out);
     }
   }
 }

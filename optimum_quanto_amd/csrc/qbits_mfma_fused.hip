@@ -302,7 +302,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) qbits_mfma_fused_kernel(const A
   QH_GF_FOR_EACH_TILE(nk_run, tile, final_fold, accgA, accgB);
   if (S > 1) QH_GF_SPLITK(BM, MI, acc, a.partials, a.counters, S, sp, tid, smem);
   // the lane's 4 packed rows wave*8 + 4*(fg & 1) .. + 3 of plane fg >> 1
-  QH_GF_EPILOGUE(E, MI, acc, a.y, a.bias, m0, fi, N, P, p0 + wave * 8 + 4 * (fg & 1), fg >> 1, m < M && !(a.ablate & 2), (void)0);
+  QH_GF_EPILOGUE(DT, MI, acc, a.y, a.bias, m0, fi, N, P, p0 + wave * 8 + 4 * (fg & 1), fg >> 1, m < M && !(a.ablate & 2), (void)0);
 }
 
 // tile times of the time model (r3 sweeps, us per 64- / 128-token tile), the forcing knobs, 2-byte activations

@@ -370,11 +370,7 @@ __global__ void __launch_bounds__(NW * 64, 1) qbits_mfma_large_kernel(const Args
     for (int i = 0; i < MI; ++i) {
       T out[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[j][i][r];
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[r];  // product rounded to T, then the bias, then rounded (tensor/function.py:45-46)
-        out[r] = E::from_f32(v);
-      }
+      for (int r = 0; r < 4; ++r) out[r] = round_add_round<DT>(acc[j][i][r], has_bias, bv[r]);
       const int row = i * 16 + fr;
       *reinterpret_cast<uint2*>(smem + row * OUT_PITCH + (j * BP + wave * 16 + fg * 4) * 2) = *reinterpret_cast<const uint2*>(out);
     }

@@ -238,11 +238,7 @@ __global__ void __launch_bounds__(NW * 64) qbits_mmv_kernel(const Args a) {
       if (m < M) {
         T out[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float f = v[r];
-          if (has_bias) f = E::to_f32(E::from_f32(f)) + bv[r];  // the reference rounds the product, then adds the bias
-          out[r] = E::from_f32(f);
-        }
+        for (int r = 0; r < 4; ++r) out[r] = round_add_round<DT>(v[r], has_bias, bv[r]);
         *reinterpret_cast<uint2*>(yg + (size_t)m * N + n0) = *reinterpret_cast<const uint2*>(out);
       }
     }

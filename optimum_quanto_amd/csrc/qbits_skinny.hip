@@ -434,11 +434,7 @@ __global__ void __launch_bounds__(WAVES * SETS * 64) qbits_skinny_kernel(Args a,
     if (m < M) {
       T out[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[tf][r];
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[r];
-        out[r] = E::from_f32(v);
-      }
+      for (int r = 0; r < 4; ++r) out[r] = round_add_round<DT>(acc[tf][r], has_bias, bv[r]);
       *reinterpret_cast<uint2*>(yg + (size_t)m * N + n0) = *reinterpret_cast<const uint2*>(out);
     }
   }

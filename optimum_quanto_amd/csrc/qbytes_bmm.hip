@@ -101,9 +101,7 @@ __device__ __forceinline__ void store_tile_dt(const Args& g, const i32x4 (&acc)[
     for (int r = 0; r < 4; ++r) {
       const int ml = wave * 16 + (lane >> 4) * 4 + r;
       if (ml >= rows) continue;
-      float v = (float)acc[j][r] * sc;  // v_cvt_f32_i32 (RNE), one multiply
-      asm volatile("" : "+v"(v));       // the product rounded to fp32 first, then once to T (no single-rounding v_fma_mixlo_f16)
-      y[(int64_t)ml * g.N + nl] = E::from_f32(v);
+      y[(int64_t)ml * g.N + nl] = scale_round_add_round<DT>((float)acc[j][r], sc, false, 0.f);  // v_cvt_f32_i32 (RNE), one multiply; no bias in this product
     }
   }
 }

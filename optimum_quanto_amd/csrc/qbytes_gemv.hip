@@ -121,10 +121,9 @@ __global__ void __launch_bounds__(256) qbytes_gemv_kernel(const uint16_t* __rest
     if (n < N) {
       float v = 0.f;
       for (int s = 0; s < wpr; ++s) v += red[wave + s][r][m];
-      v *= E::to_f32(__builtin_bit_cast(T, scales[n]));
-      asm volatile("" : "+v"(v));  // product rounded to fp32 first, with and without bias (no single-rounding v_fma_mixlo_f16)
-      if (bias) v = E::to_f32(E::from_f32(v)) + E::to_f32(__builtin_bit_cast(T, bias[n]));
-      y[(size_t)m * N + n] = __builtin_bit_cast(uint16_t, E::from_f32(v));
+      const float sc = E::to_f32(__builtin_bit_cast(T, scales[n]));
+      const T out = bias ? scale_round_add_round<DT>(v, sc, true, E::to_f32(__builtin_bit_cast(T, bias[n]))) : scale_round_add_round<DT>(v, sc, false, 0.f);
+      y[(size_t)m * N + n] = __builtin_bit_cast(uint16_t, out);
     }
   }
 }

@@ -231,12 +231,7 @@ __global__ void __launch_bounds__(256) qbytes_skinny_kernel(Args a, const Segs s
     if (m < M) {
       T out[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[tf][r] * sc[r];
-        asm volatile("" : "+v"(v));  // product rounded to fp32 first, with and without bias (no single-rounding v_fma_mixlo_f16)
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[r];
-        out[r] = E::from_f32(v);
-      }
+      for (int r = 0; r < 4; ++r) out[r] = scale_round_add_round<DT>(acc[tf][r], sc[r], has_bias, bv[r]);
       if (n0 + 3 < N && (N & 3) == 0) {
         *reinterpret_cast<uint2*>(yg + (size_t)m * N + n0) = *reinterpret_cast<const uint2*>(out);
       } else {

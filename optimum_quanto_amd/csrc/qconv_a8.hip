@@ -87,7 +87,7 @@ __device__ __forceinline__ void store_tile(const Args& a, const AV (&acc)[4][2],
 }
 
 // ---- the same epilogue storing OUTPUT CODES (QOUT).  Per element the two kernels back to back: t = the element conv_store_tile<DT, 1, CONV_EPI_8BIT>
-// stores, by its statements - fp32(acc) * sc[n] behind the asm volatile, rounded to T, the bias added, rounded again - then the rule of qh_quantize.h
+// stores (qh_common.h: scale_round_add_round) - fp32(acc) * sc[n] behind the asm volatile, rounded to T, the bias added, rounded again - then the rule of qh_quantize.h
 // on t: T(fp32(t) / fp32(out_scale)) with a correctly rounded divide, clamp_target, pack4.  ODT: the activation's own type.  A lane's four
 // accumulator rows are four neighbouring pixels of one channel plane = one dword of codes: ONE 4-byte store when they lie in one image, the plane
 // size is a multiple of 4 and yq is 4-byte aligned; per byte otherwise, with conv_store_tile's walk over image ends.

@@ -89,12 +89,7 @@ __global__ void __launch_bounds__(THREADS) qconv2d_depthwise_kernel(const Args a
   const float bv = has_bias ? E::to_f32(reinterpret_cast<const T*>(a.bias)[oc]) : 0.f;
   T out[PX];
 #pragma unroll
-  for (int p = 0; p < PX; ++p) {
-    float v = acc[p] * sc;
-    asm volatile("" : "+v"(v));  // the product is rounded to fp32 before anything else happens to it (no fused multiply-add with the bias)
-    if (has_bias) v = E::to_f32(E::from_f32(v)) + bv;
-    out[p] = E::from_f32(v);
-  }
+  for (int p = 0; p < PX; ++p) out[p] = scale_round_add_round<DT>(acc[p], sc, has_bias, bv);
   T* yp = reinterpret_cast<T*>(a.y) + ((size_t)plane * a.OH + oh) * a.OW + ow0;
   if (ow0 + PX <= a.OW && (reinterpret_cast<uintptr_t>(yp) & 7) == 0) {
     *reinterpret_cast<uint2*>(yp) = *reinterpret_cast<const uint2*>(out);
@@ -196,12 +191,7 @@ __global__ void __launch_bounds__(THREADS) qconv2d_depthwise_strip_kernel(const 
     if (oh >= a.OH) break;
     T out[CO];
 #pragma unroll
-    for (int p = 0; p < CO; ++p) {
-      float v = acc[ro][p] * sc;
-      asm volatile("" : "+v"(v));  // the product is rounded to fp32 before anything else happens to it (no fused multiply-add with the bias)
-      if (has_bias) v = E::to_f32(E::from_f32(v)) + bv;
-      out[p] = E::from_f32(v);
-    }
+    for (int p = 0; p < CO; ++p) out[p] = scale_round_add_round<DT>(acc[ro][p], sc, has_bias, bv);
     T* yp = reinterpret_cast<T*>(a.y) + ((size_t)plane * a.OH + oh) * a.OW + ow0;
     const uintptr_t ya = reinterpret_cast<uintptr_t>(yp);
     if (CO == 8 && ow0 + CO <= a.OW && (ya & 15) == 0) {

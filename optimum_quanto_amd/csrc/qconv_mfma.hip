@@ -52,7 +52,8 @@ constexpr int planes_of(int fmt) { return fmt == W_I4R ? 2 : (fmt == W_I2R ? 4 :
 
 static_assert(BK * 2 == kTileRowBytes, "a K-tile of two-byte elements is one LDS row of tile_lds_off");
 
-// The twin of qh::pack_rne (qh_mfma.h), in the wording this unit's listing was built from (either wording changes the other user's): a fix to one belongs in the other.
+// qh::pack_rne (qh_mfma.h) in the wording this unit needs.  Measured with one copy, four wordings: in qh_mfma.h's (and as a vector of two shorts) this
+// unit's int2 kernels take 14-15 more VGPRs; in this one (and as __builtin_convertvector) qbits_mfma_large.hip's kernels take 4-24 more or spill 5-11.
 template <int DT>
 __device__ __forceinline__ uint32_t pack_rne(float a, float b) {
   using E = Elem<DT>;
@@ -179,12 +180,7 @@ __device__ __forceinline__ void store_tile_lds(const Args& a, const f32x4 (&acc)
     for (int i = 0; i < 4; ++i) {
       T out[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[i][j][r] * sc;
-        asm volatile("" : "+v"(v));  // (store_tile: the product rounded to fp32 first)
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv;
-        out[r] = E::from_f32(v);
-      }
+      for (int r = 0; r < 4; ++r) out[r] = scale_round_add_round<DT>(acc[i][j][r], sc, has_bias, bv);
       *reinterpret_cast<uint2*>(stage + tc * EPI_ROW + (wm * 64 + i * 16 + (lane >> 4) * 4) * 2) = *reinterpret_cast<const uint2*>(out);
     }
   }

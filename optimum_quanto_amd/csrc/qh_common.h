@@ -49,6 +49,26 @@ struct Elem<QUANTO_HIP_BF16> {
   static __device__ __forceinline__ T from_f32(float f) { return (__bf16)f; }  // v_cvt_pk_bf16_f32, RNE
 };
 
+// ---- the output element of every product (include/quanto_hip.h; DESIGN.md "Parity") -----------------
+// THE rounding rule, its one copy: the product rounded to the output type T, the bias added to that in fp32, the sum rounded to T again -
+// the reference's order (tensor/weights/qbytes.py:79-81, tensor/function.py:45-46).  `v`: the product in fp32; `bias` is read only with has_bias.
+// A kernel that holds the bias as a pointer that may be null (the GEMVs, naive_mm.hip) calls it once per case - bias ? f(.., true, bias[n]) :
+// f(.., false, 0.f) - so that the load stays under the test; loading into a value first cost naive_mm.hip's kernels two SGPRs.
+template <int DT>
+__device__ __forceinline__ typename Elem<DT>::T round_add_round(float v, bool has_bias, float bias) {
+  using E = Elem<DT>;
+  if (has_bias) v = E::to_f32(E::from_f32(v)) + bias;
+  return E::from_f32(v);
+}
+// the same on accumulator x scale (library/qbytes_mm.py:47-49): the fp32 product is rounded to fp32 in front of anything else, with and without a
+// bias - the empty asm keeps hipcc from fusing the multiply into a single-rounding form (v_fma_mixlo_f16, or an fma with the bias add)
+template <int DT>
+__device__ __forceinline__ typename Elem<DT>::T scale_round_add_round(float acc, float scale, bool has_bias, float bias) {
+  float v = acc * scale;
+  asm volatile("" : "+v"(v));
+  return round_add_round<DT>(v, has_bias, bias);
+}
+
 // ---- 8-bit weight/activation decoders ---------------------------------------------------------
 // e4m3fnuz has no hardware path on gfx950 (the native fp8 is OCP e4m3fn): decode in software.
 __device__ __forceinline__ float decode_e4m3fnuz(uint32_t b) {

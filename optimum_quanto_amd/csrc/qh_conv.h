@@ -106,8 +106,9 @@ __device__ __forceinline__ int conv_tap_ok(uint64_t w0, uint64_t w1, int tp) {
 // weights): the tile's 128 columns are (128 / PL) packed rows x PL planes; plane pl holds channels pl * P + p.
 // WORDING: the two places where the units' epilogues were written differently - m / L and the test for a channel behind N, down to how the
 // channel sum is parenthesised.  hipcc's listing follows the wording, so each unit keeps its own behind this parameter: with the 8-bit wording
-// qconv_mfma.hip's one-byte-weight kernels come out 12-14 instructions shorter, with the 16-bit wording qconv_a8.hip's 11 longer, and either
-// move changes tuned kernels and wants its own measurement.  CONV_EPI_16BIT: m / L through the fp32 reciprocal, corrected (m < 2^24,
+// qconv_mfma.hip's one-byte-weight kernels come out 12-14 instructions shorter, with the 16-bit wording qconv_a8.hip's 11 longer.  Measured with
+// one wording for both: the 8-bit one costs qconv_mfma.hip's six reduce kernels an SGPR each; the 16-bit one costs qconv_a8.hip no register (16
+// of its kernels use fewer) but moves an instruction in front of their K loops.  CONV_EPI_16BIT: m / L through the fp32 reciprocal, corrected (m < 2^24,
 // conv_geometry_ok), a channel behind N becomes -1.  CONV_EPI_8BIT: integer division, the channel tested directly.
 enum { CONV_EPI_16BIT = 0, CONV_EPI_8BIT = 1 };
 template <int DT, int PL, int WORDING, typename AV, typename A, typename SC>
@@ -165,12 +166,7 @@ __device__ __forceinline__ void conv_store_tile(const A& a, const AV (&acc)[4][2
       if (m >= M) continue;
       T out[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = (float)acc[i][j][r] * sc;
-        asm volatile("" : "+v"(v));  // product rounded to fp32 first, with and without bias (no single-rounding v_fma_mixlo_f16)
-        if (has_bias) v = E::to_f32(E::from_f32(v)) + bv;  // the reference's order: rounded convolution output + bias, rounded again
-        out[r] = E::from_f32(v);
-      }
+      for (int r = 0; r < 4; ++r) out[r] = scale_round_add_round<DT>((float)acc[i][j][r], sc, has_bias, bv);
       T* dst = yg + ((size_t)bq[i] * N + n) * L + lq[i];
       if (vec && m + 3 < M) {  // (L % 4 == 0 and m % 4 == 0: the four pixels are in one image, aligned)
         if constexpr (sizeof(T) == 2)

@@ -125,10 +125,11 @@ __device__ __forceinline__ void fold_slice(f32x4 (&acc)[MI], const GV (&pg)[MI],
 
 // ---- epilogue: 4 consecutive features (packed rows PL .. PL + 3 of plane PLANE) of one token per fragment: 8-byte stores, per element on the ragged
 // edge.  STORE_ROW: the condition under which token m is stored; SCALE: a statement on the fp32 value v in front of everything else (the activation
-// scale of the quantized-activation kernel).  bias: the product rounded to E::T, the bias added, rounded again (the reference's order).
-#define QH_GF_EPILOGUE(E, MI, ACC, Y, BIAS, M0, FI, N, P, PL, PLANE, STORE_ROW, SCALE)                                       \
+// scale of the quantized-activation kernel); the element stored is round_add_round (qh_common.h) of v.
+#define QH_GF_EPILOGUE(DT, MI, ACC, Y, BIAS, M0, FI, N, P, PL, PLANE, STORE_ROW, SCALE)                                      \
   {                                                                                                                         \
-    using qh_T = typename E::T;                                                                                             \
+    using qh_E = qh::Elem<DT>;                                                                                              \
+    using qh_T = typename qh_E::T;                                                                                          \
     qh_T* const qh_y = reinterpret_cast<qh_T*>(Y);                                                                          \
     const bool qh_has_bias = (BIAS) != nullptr;                                                                             \
     const int qh_pl = (PL);                     /* first of the lane's 4 packed rows */                                    \
@@ -136,7 +137,7 @@ __device__ __forceinline__ void fold_slice(f32x4 (&acc)[MI], const GV (&pg)[MI],
     float qh_bv[4] = {0.f, 0.f, 0.f, 0.f};                                                                                  \
     if (qh_has_bias) {                                                                                                      \
       _Pragma("unroll") for (int qh_r = 0; qh_r < 4; ++qh_r)                                                                \
-        qh_bv[qh_r] = qh_pl + qh_r < (P) ? E::to_f32(reinterpret_cast<const qh_T*>(BIAS)[qh_n0 + qh_r]) : 0.f;              \
+        qh_bv[qh_r] = qh_pl + qh_r < (P) ? qh_E::to_f32(reinterpret_cast<const qh_T*>(BIAS)[qh_n0 + qh_r]) : 0.f;           \
     }                                                                                                                       \
     _Pragma("unroll") for (int qh_i = 0; qh_i < (MI); ++qh_i) {                                                             \
       const int m = (M0) + qh_i * 16 + (FI);                                                                                \
@@ -145,8 +146,7 @@ __device__ __forceinline__ void fold_slice(f32x4 (&acc)[MI], const GV (&pg)[MI],
         _Pragma("unroll") for (int qh_r = 0; qh_r < 4; ++qh_r) {                                                            \
           float v = (ACC)[qh_i][qh_r];                                                                                      \
           SCALE;                                                                                                            \
-          if (qh_has_bias) v = E::to_f32(E::from_f32(v)) + qh_bv[qh_r];                                                     \
-          qh_out[qh_r] = E::from_f32(v);                                                                                    \
+          qh_out[qh_r] = qh::round_add_round<DT>(v, qh_has_bias, qh_bv[qh_r]);                                              \
         }                                                                                                                   \
         if (qh_pl + 3 < (P) && ((N) & 3) == 0) {                                                                            \
           *reinterpret_cast<uint2*>(qh_y + (size_t)m * (N) + qh_n0) = *reinterpret_cast<const uint2*>(qh_out);              \

@@ -37,8 +37,8 @@ __device__ __forceinline__ uint32_t pack_exact(float a, float b) {
     return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
   }
 }
-// two fp32 -> one dword of the 16-bit type, round to nearest even: dequantized sub-byte weights (qbits_mfma_large.hip).  qconv_mfma.hip keeps a twin
-// in its own wording (conv::pack_rne: this wording changes its listing, its wording changes qbits_mfma_large's): a fix to one belongs in the other.
+// two fp32 -> one dword of the 16-bit type, round to nearest even: dequantized sub-byte weights (qbits_mfma_large.hip; qconv_mfma.hip has
+// conv::pack_rne in another wording - the register counts that keep the two apart are recorded there)
 template <int DT>
 __device__ __forceinline__ uint32_t pack_rne(float a, float b) {
   if constexpr (DT == QUANTO_HIP_BF16) {

@@ -1,5 +1,5 @@
 // The per-element rule of quanto::quantize_symmetric (library/quantize.py:26-55), one copy for quantize.hip and for the product epilogues that store
-// output codes (epilogue_code below: qh_group_fused.h, qconv_a8.hip; qmm_native8.hip keeps its statements inline, for its listing): code = cast(clamp(round?(T(x / scale)))).
+// output codes (epilogue_code below: qh_group_fused.h, qconv_a8.hip, qmm_native8.hip): code = cast(clamp(round?(T(x / scale)))).
 //
 // Bit-exactness with the torch sequence: the quotient is an fp32 divide, correctly rounded (no reciprocal multiply), rounded to the tensor dtype T -
 // what aten's div does through its opmath type; integer targets are then rounded half-to-even in T (exact: |q| <= 256 after the clamp matters only)
@@ -42,18 +42,12 @@ __device__ __forceinline__ float quotient_in(float x, float s) {
   return E::to_f32(E::from_f32(x / s));
 }
 
-// The output code of a product epilogue, before pack4: the element t the float epilogue would store - accumulator x scale rounded to fp32 in front of
-// anything else (the asm volatile: no single-rounding fused form), rounded to T, the bias added to that, rounded again - then the rule above on t at the
-// output scale os.  DT: the tensor dtype T of the product; ODT: the code type.  The QOUT epilogues are pinned bit for bit against the two-kernel sequence: a
-// rounding fix belongs here and in n8::epilogue_codes (qmm_native8.hip), which holds the same statements inline.
+// The output code of a product epilogue, before pack4: the element the float epilogue would store (qh_common.h: scale_round_add_round), then the rule
+// above on it at the output scale os.  DT: the tensor dtype T of the product; ODT: the code type.  The QOUT epilogues are pinned bit for bit against the
+// two-kernel sequence.
 template <int DT, int ODT>
 __device__ __forceinline__ float epilogue_code(float acc, float scale, bool has_bias, float bias, float os) {
-  using E = Elem<DT>;
-  float v = acc * scale;
-  asm volatile("" : "+v"(v));
-  if (has_bias) v = E::to_f32(E::from_f32(v)) + bias;
-  const typename E::T t = E::from_f32(v);  // the element the float epilogue stores
-  return clamp_target<ODT>(quotient_in<DT>(E::to_f32(t), os));
+  return clamp_target<ODT>(quotient_in<DT>(Elem<DT>::to_f32(scale_round_add_round<DT>(acc, scale, has_bias, bias)), os));
 }
 
 }  // namespace qh

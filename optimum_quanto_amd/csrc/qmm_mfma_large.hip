@@ -391,8 +391,9 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qbytes_mfma_large_kernel(cons
   QH_LT_STAMP(4);
 
   // ---- epilogue: scale (+bias) on the fp32 accumulator; each wave parks MI*16 tokens x 64 features per pass -------------
-  // The same epilogue as n8::epilogue (qmm_native8.hip), which spells it as a function over 2- and 4-byte outputs: a fix to one belongs in the
-  // other.  One shared function (this wording or that one, 8-byte or element reads of the table) changed the listings of both units.
+  // The same park / swizzle / store as n8::epilogue (qmm_native8.hip), which spells it as a function over 2- and 4-byte outputs; the element itself is
+  // the shared rule (qh_common.h).  Measured with one shared function (8-byte, element or struct reads of the table alike): this unit's 128-tile int8
+  // WD = 4 kernels +4 VGPRs / +4 AGPRs, its 256-tile 1 x 8 int8 kernels +2 VGPRs, and instructions in front of the K loop in another order - not taken.
   T* yg = reinterpret_cast<T*>(a.y);
   const bool has_bias = a.bias != nullptr;
   const bool full = (m0 + BM <= M) && (n0 + BN <= N) && (N % 8 == 0);
@@ -439,12 +440,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qbytes_mfma_large_kernel(cons
         for (int i = h * MIH; i < (h + 1) * MIH; ++i) {
           T out[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float v = acc[j][i][r] * sc[jj][r];
-            asm volatile("" : "+v"(v));  // product rounded to fp32 first, with and without bias (no single-rounding v_fma_mixlo_f16)
-            if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[jj][r];
-            out[r] = E::from_f32(v);
-          }
+          for (int r = 0; r < 4; ++r) out[r] = scale_round_add_round<DT>(acc[j][i][r], sc[jj][r], has_bias, bv[jj][r]);
           const int row = i * 16 + (lane & 15);
           const int chunk = (jj * 4 + (lane >> 4)) ^ ((row & (LPR - 1)) << 1);
           *reinterpret_cast<uint2*>(park + row * ROWB + chunk * 8) = *reinterpret_cast<const uint2*>(out);

@@ -83,12 +83,12 @@ using lt::FeatureTable;
 
 // ---- epilogue: (int32 | fp32) accumulator * scale[n] (+ bias), parked per wave in LDS, stored as full 128-byte lines ----
 // (shared by the 64-byte-row and the 128-byte-row kernels; every wave must be done with the operand stages: the barrier below)
-// The same epilogue as the inline one of qmm_mfma_large.hip (2-byte outputs, 8-byte reads of the table, MI * 16 rows per wave): a fix to one belongs
-// in the other.  One shared function changed the listings of both units, whichever of the two wordings it took.
+// The same park / swizzle / store as the inline epilogue of qmm_mfma_large.hip (2-byte outputs, 8-byte reads of the table, MI * 16 rows per wave); one
+// shared function cost registers in both units (numbers there).
 // NI / i0: the token fragments acc[.][0 .. NI-1] are fragments i0 .. i0 + NI - 1 of the wave's 128 rows (the K split hands every workgroup 8 / S of them)
 // ---- the same epilogue storing OUTPUT CODES: what quanto::quantize_symmetric(y, activation dtype, None, out_scale) makes of the T-rounded y ----
 // (nn/qmodule.py:281-299 re-quantizes every output of a quantized-activation layer; here the [M, N] tensor of T never exists.)  Per element exactly the
-// two kernels back to back: t as in the epilogue below - scaled, rounded to T, bias added, rounded again - then the rule of qh_quantize.h on t:
+// two kernels back to back (qh_quantize.h: epilogue_code): t as in the epilogue below - scaled, rounded to T, bias added, rounded again - then on t:
 // T(fp32(t) / fp32(out_scale)) with a correctly rounded divide, clamp_target, pack4.  The code type is the operands' own (int8 / e4m3 / e5m2).
 // Parking: one byte per feature, so a wave's 16 * NJ features are ONE row of ROWB = 64 (256-tile) or 32 (128-tile) bytes and one pass; a lane parks the
 // four codes of its four consecutive features as one dword, LPR = ROWB / 16 lanes read a row back as 16-byte chunks and store them: full 16-byte stores on
@@ -133,15 +133,7 @@ __device__ __forceinline__ void epilogue_codes(const Args& a, typename Acc<KIND>
       for (int i = h * NIH; i < (h + 1) * NIH; ++i) {
         float q[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          // the statements of qh::epilogue_code (qh_quantize.h), inline: as a call this unit's QOUT kernels came out with other registers.  A rounding
-          // fix made there belongs here too.
-          float v = (float)acc[j][i][r] * sc[j][r];  // the statements of the epilogue below: fp32 product, rounded to fp32 ...
-          asm volatile("" : "+v"(v));                // ... and only then to T
-          if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[j][r];
-          const T t = E::from_f32(v);                // the element qbytes_mm_bias stores
-          q[r] = clamp_target<QDT>(quotient_in<ODT>(E::to_f32(t), os));
-        }
+        for (int r = 0; r < 4; ++r) q[r] = epilogue_code<ODT, QDT>((float)acc[j][i][r], sc[j][r], has_bias, bv[j][r], os);  // of the element qbytes_mm_bias stores
         const int row = i * 16 + (lane & 15);
         const int c16 = j ^ ((row / SWR) & (LPR - 1));
         *reinterpret_cast<uint32_t*>(park + row * ROWB + c16 * 16 + (lane >> 4) * 4) = pack4<QDT>(q);
@@ -215,6 +207,10 @@ __device__ __forceinline__ void epilogue(const Args& a, typename Acc<KIND>::V (&
           T out[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
+            // The statements of scale_round_add_round (qh_common.h), kept inline: a rounding fix made there belongs here too.  As a call the listings of
+            // this unit's 16 float-output r128 kernels hold the same instructions in another order behind the K loop, registers unchanged; five
+            // alternating runs each on one MI355X: w8a8, fp8a8, cfg4_w8a8, w8a8_down512, int4_prefill inside the parent's range (medians -0.39 ..
+            // +0.06 %), cfg4_fp8a8 1597.07 TFLOP/s against the parent's 1597.91 .. 1600.42 - below it, so not taken.
             float v = (float)acc[j][i][r] * sc[jj][r];  // library/qbytes_mm.py:47-49: fp32(int32) * fp32(scale), rounded to fp32 ...
             asm volatile("" : "+v"(v));                 // ... and only then to the output dtype (no single-rounding v_fma_mixlo_f16)
             if (has_bias) v = E::to_f32(E::from_f32(v)) + bv[jj][r];

@@ -47,7 +47,9 @@ ROUNDS_BY_DESIGN = [
     dict(what="bias on a 16-bit output",
          applies=lambda dt, bias: bias and dt != "fp32",
          expected="round(round(product) + bias): the product is rounded to the output type, the bias is added in fp32, the sum is rounded again",
-         cites=("csrc/naive_mm.hip:65", "csrc/naive_mm.hip:105", "csrc/qbytes_gemv.hip:126", "csrc/qbits_gemv.hip:389", "csrc/qconv_a8.hip:6"),
+         # round_add_round, the copy of the rule every product epilogue calls - and the one epilogue that keeps the statements inline, for the
+         # measurement its comment records (n8::epilogue).  tests/test_exact_routes_cpu.py: no other file under csrc/ holds the expression.
+         cites=("csrc/qh_common.h:60", "csrc/qmm_native8.hip:216"),
          why="the two-op order of the reference (a product in the output dtype, then `out + bias`: tensor/function.py:45-46, tensor/weights/qbytes.py:79-81), "
              "which include/quanto_hip.h promises bit for bit ('rounded product plus bias, rounded again') and the registered default ops compute; the fp32 "
              "entries add the bias to the fp32 product, which is exact here.  The bias launch is still compared bit for bit, against this order."),

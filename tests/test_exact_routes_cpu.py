@@ -1,7 +1,9 @@
 """Host part of the exact-route tests: the designed problems of tests/exact_cases.py show what they claim, satisfy the bound under which fp32
 accumulation is exact in any order, are planned onto the route their row names - and the registered torch-expression ops, run on them on the host, give
 the expected bits (an independent check of the oracle rule the device file, tests/test_exact_routes_gpu.py, compares against)."""
+import glob
 import os
+import re
 
 import numpy as np
 import pytest
@@ -41,6 +43,16 @@ def test_what_is_rounded_by_design_is_cited():
             path, line = cite.split(":")
             with open(os.path.join(C.ROOT, "optimum_quanto_amd", path)) as fh:
                 assert "bias" in fh.read().splitlines()[int(line) - 1], cite
+    # the rule is written once, in the helper's header: no file under csrc/ but the cited ones holds the round-add-round expression (a cite beyond
+    # the header's is a unit whose measurement kept its statements inline - a finding, recorded in that unit's comment)
+    rule = re.compile(r"to_f32\(E::from_f32\([^()]*(\([^()]*\)[^()]*)*\)\)\s*\+")  # T(v) + ..., v any expression
+    holders = []
+    for path in sorted(glob.glob(os.path.join(C.ROOT, "optimum_quanto_amd", "csrc", "*.h*"))):  # *.h, *.hip
+        with open(path) as fh:
+            if rule.search(fh.read()):
+                holders.append(os.path.basename(path))
+    cited = sorted({os.path.relpath(cite.split(":")[0], "csrc") for cite in E.ROUNDS_BY_DESIGN[0]["cites"]})
+    assert cited == ["qh_common.h", "qmm_native8.hip"] and holders == cited, holders
 
 
 def test_every_exemption_names_a_route_and_a_line():
